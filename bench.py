@@ -3,7 +3,14 @@
 corr_est_cc kernel's HBM-roofline fraction, parity gates against the CPU oracle
 and a CPU baseline.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints one JSON line: the headline
+value, ms_per_step, and the correlator's roofline from the hipEvents of the timed
+steps.  --full adds everything else described below (side measurements, the
+correlator alone, the parity gates against the oracle, the CPU baseline).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(float32 / float64, a fixed sample of the channels: see dump_outputs()).
 
 One "step" = one pass of the chain over one batch: CHANNELS_PER_GPU channels x
 SAMPLES complex samples per GPU, already resident in HBM, through the PRODUCT's
@@ -18,7 +25,7 @@ Workload (BASELINE.json configs[2], the one the metric is quoted on): 4096
 batched channels, 65536 samples each, sps = 4, stock template (N = 896, SURVEY
 D4).  The default chain is the whole flowgraph of python/ais_demod.py:56:
 freq_sync (square -> FFT -> freqest -> NCO mix) -> feedforward agc -> corr_est
--> msk_timing_recovery -> NRZI bit tail; `value` is its throughput.  The same
+-> msk_timing_recovery -> NRZI bit tail; `value` is its throughput.  A --full
 run also times `--chain core` (corr_est -> msk_timing only, the two blocks the
 metric string names) and the correlator alone at BASELINE config 2's shapes
 (256 and 4096 channels, N = 896 and 112) and reports them under
@@ -27,8 +34,8 @@ metric string names) and the correlator alone at BASELINE config 2's shapes
 
 "roofline" is the correlator's main kernel: algorithmic 16 B per sample over its
 launch time by hipEvents on its own stream inside the timed region, next to the
-8 TB/s spec peak and to what the best plain copy sustains on this box
-("copy_ceiling_GBs").  After the timed region the last step of PARITY_CHANNELS
+8 TB/s spec peak and (--full) to what the best plain copy sustains on this box
+("copy_ceiling_GBs").  With --full, after the timed region the last step of PARITY_CHANNELS
 channels is compared with the CPU oracle replaying the same steps on the same
 samples ("parity": tag offsets, peak magnitudes, time_est, decoded bursts --
 BASELINE.md section 3).  "cpu_baseline": the oracle built on this host with -O3
@@ -108,6 +115,40 @@ def burst_infos(c, T, family, sps, rank, stock):
     ip = input_params(family, stock)
     return synth.make_channel(synth.SEED0 + 1000 * rank + (c % NUNIQ), T, family, sps, amp=ip["amp"], cfo_max=ip["cfo_max"],
                               noise=False)[1]
+
+
+DUMP_ROWS_BYTES = 32 << 20  # the sampled rows of bits / y; with produced and the tags the dump stays well under 64 MB
+DUMP_SEED = 1234
+
+
+def dump_outputs(d, nchan, tags, bits=None, produced=None, y=None):
+    """--dump-outputs: what the timed path handed its caller in its last step, as d/<name>.npy, so that two builds can be
+    compared output for output (the inputs are seeded).  channels: a fixed, seeded sample of the channels (all of them
+    when their rows fit DUMP_ROWS_BYTES), ascending; bits: their decoded bits, -1 past each channel's produced count (the
+    rest of a row is not output); produced: every channel's count; y (chain corr): corr_est's output rows of the sample as
+    (re, im); tags: corr_est's tags of the sample as rows (chan, offset, key, value), sorted (the device emits them in no
+    fixed order)."""
+    import torch
+
+    row_bytes = 4 * (bits.shape[1] if bits is not None else 2 * y.shape[1])
+    k = max(1, min(nchan, DUMP_ROWS_BYTES // row_bytes))
+    chans = np.arange(nchan) if k == nchan else np.sort(np.random.default_rng(DUMP_SEED).choice(nchan, k, replace=False))
+    out = {"channels": chans.astype(np.float64)}
+    sel = torch.as_tensor(chans, device=(bits if bits is not None else y).device)
+    if bits is not None:
+        prod = produced.cpu().numpy()
+        b = bits.index_select(0, sel).cpu().numpy().astype(np.float32)
+        b[np.arange(b.shape[1])[None, :] >= prod[chans][:, None]] = -1.0
+        out["bits"] = b
+        out["produced"] = prod.astype(np.float64)
+    if y is not None:
+        out["y"] = torch.view_as_real(y.index_select(0, sel)).cpu().numpy().astype(np.float32)
+    t = tags[np.isin(tags["chan"], chans)]
+    t = t[np.lexsort((t["value"], t["key"], t["offset"], t["chan"]))]
+    out["tags"] = np.stack([t["chan"], t["offset"], t["key"], t["value"]], axis=1).astype(np.float64).reshape(-1, 4)
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def pmc_traffic(nchan, T, N):
@@ -423,22 +464,24 @@ def bench_wideband(args, torch, device, as_dict=False, steps=None):
     opts = dict(samples_per_symbol=sps, bits_per_sec=9600.0, clockrec_gain=0.04, omega_relative_limit=0.01, fftlen=1024)
     dem = ais_amd.ais_demod(opts, nchan=M, max_items=nfr, stages="core", preamble_symbols=tmpl[:1024])
 
+    last = {}
+
     def step():
         lanes = pfb.work(x)
-        dem.work(lanes)
+        last["r"] = dem.work(lanes)
 
     nsteps = steps or args.steps
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
     t0 = time.perf_counter()
     for _ in range(nsteps):
         step()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
-    ev[0].record(); lanes = pfb.work(x); ev[1].record(); dem.work(lanes); ev[2].record()
-    torch.cuda.synchronize()
+    if args.dump_outputs and not as_dict:
+        dump_outputs(args.dump_outputs, M, dem.preamble_detect.tags(allow_overflow=True), bits=last["r"]["bits"],
+                     produced=last["r"]["produced"])
     line = {
         "metric": "wideband complex MS/s through polyphase channelizer -> 1024 demod lanes",
         "value": n * nsteps / el / 1e6, "unit": "complex MS/s (wideband input)", "n_gpus": 1, "steps": nsteps,
@@ -446,8 +489,13 @@ def bench_wideband(args, torch, device, as_dict=False, steps=None):
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": "1 x %d wideband samples/step at 25 MS/s -> 1024 lanes x %d items (decim 512, 60227-tap "
                                "prototype) -> corr_est(N=1024)->msk" % (n, nfr)},
-        "pfb_ms": ev[0].elapsed_time(ev[1]), "demod_ms": ev[1].elapsed_time(ev[2]),
         "realtime_factor": n * nsteps / el / 25e6}
+    if args.full:
+        # one more step with the channelizer and the demod lanes timed apart
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record(); lanes = pfb.work(x); ev[1].record(); dem.work(lanes); ev[2].record()
+        torch.cuda.synchronize()
+        line.update(pfb_ms=ev[0].elapsed_time(ev[1]), demod_ms=ev[1].elapsed_time(ev[2]))
     del pfb, dem, x
     torch.cuda.empty_cache()
     if as_dict:
@@ -471,10 +519,16 @@ def parse_args(argv=None):
                     help="stock = the whole ais_demod.py flowgraph (freq_sync with freqest, agc, corr_est, msk timing "
                          "recovery, NRZI tail); core = corr_est -> msk only; corr = corr_est only; wideband = BASELINE "
                          "config 5: one 25 MS/s stream -> 1024-lane polyphase channelizer -> core chain")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the side measurements, the correlator alone on the chip, the parity gates "
+                         "against the oracle and the CPU baseline (a plain run times the steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (a fixed sample of the channels)")
     ap.add_argument("--single-chain", action="store_true",
-                    help="only the chain asked for: no corr_est->msk-only and correlator-only side measurements")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--parity-channels", type=int, default=8, help="channels of the last step compared with the oracle (0: off)")
+                    help="with --full: only the chain asked for: no corr_est->msk-only and correlator-only side measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--parity-channels", type=int, default=8,
+                    help="with --full: channels of the last step compared with the oracle (0: off)")
     ap.add_argument("--dry", action="store_true",
                     help="launcher check without a GPU: the ranks rendezvous over gloo, shard the channels and rank 0 "
                          "prints the line with value 0 (tests/test_multiproc.py)")
@@ -654,10 +708,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(chain, want_parity, lookahead=True, msk_tp=False, msk_Q=0, nch=None, corr_claim=0):
+    def measure(chain, want_parity, lookahead=True, msk_tp=False, msk_Q=0, nch=None, corr_claim=0, full=True, dump=None):
         """K timed steps of `chain` on this rank's channel shard; returns the wall time (max over
         ranks), the correlator kernel's per-launch times inside the timed region and (rank 0) the
-        parity gates of the last step.  The step is the product's pipelined chain
+        parity gates of the last step; with `full` also the package power over the timed steps and the
+        correlator's launch time with the chip to itself.  `dump`: the directory the last step's outputs
+        go to (dump_outputs).  The step is the product's pipelined chain
         (ais_demod.work_pipelined = aisx_chain_step, include/aisx.h): the sample passes of step k + 1
         on one stream beside the timing recovery of step k on another, its bit tail and the NCO
         phase walk of step k + 2 on two more.  This benchmark feeds the same samples every step, so
@@ -668,7 +724,7 @@ def main():
         # (the buffers of the alone-on-the-chip measurement at the end are allocated now: a 2 GB buffer
         # allocated late comes out of what the allocator has left over, and the same kernel reads
         # ~20 % longer on it -- placement, not the kernel)
-        early = os.environ.get("AISX_BENCH_EARLY_ISO") == "1"
+        early = full and os.environ.get("AISX_BENCH_EARLY_ISO") == "1"
         yout = torch.empty((nchan, T), dtype=torch.complex64, device=device) if early else None
         yin_buf = torch.empty((nchan, T + 1024), dtype=torch.complex64, device=device) if (stock and early) else None
         dem = ais_amd.ais_demod(opts, nchan=nchan, max_items=T, stages="stock" if stock else "core",
@@ -699,13 +755,13 @@ def main():
         corr.set_profiling(True)  # restart the event ring: the timed steps only
         if chain != "corr" and not msk_tp:
             dem.clockrec.set_profiling(True)
-        ps = PowerSampler(local_rank).start()
+        ps = PowerSampler(local_rank).start() if full else None
         t0 = time.perf_counter()
         for _ in range(args.steps):
             step()
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
-        power = ps.stop()
+        power = ps.stop() if full else None
         barrier()
         # per-launch duration of the dominant kernel over the timed region: hipEvents
         # recorded around it on its launch stream in every step, read back only now
@@ -721,6 +777,11 @@ def main():
                 res["tag_overflow"] = True
                 tags = corr.tags(allow_overflow=True)
             res["ndet"] = int((tags["key"] == 2).sum())
+            if dump:
+                if chain == "corr":
+                    dump_outputs(dump, nchan, tags, y=y_corr[(state["k"] - 1) & 1])
+                else:
+                    dump_outputs(dump, nchan, tags, bits=state["last"]["bits"], produced=state["last"]["produced"])
             K = min(args.parity_channels, nchan) if want_parity else 0
             if K > 0:
                 last = state["last"]
@@ -731,36 +792,38 @@ def main():
             if msk_tp:
                 res["restart_stats"] = dem.clockrec.restart_stats()
         barrier()
-        # the same kernel with the chip to itself (no timing-recovery kernel alongside), on the
-        # data it sees in the chain: behind the front end for the stock chain
-        yin = x
-        if stock:
-            fs2 = ais_amd.square_and_fft_sync_cc(sps * 9600.0, 9600.0, 1024, nchan=nchan, max_items=T)
-            agc2 = ais_amd.feedforward_agc_cc(512, 2.0, nchan=nchan, max_items=T + 1024)
-            yin = ais_amd.freq_sync_agc(fs2, agc2, x, out=yin_buf)[0]
-            del fs2, agc2
-        if yout is None:
-            yout = torch.empty((nchan, T), dtype=torch.complex64, device=device)
-        # (launches back to back for 0.15 s, then twenty timed ones: a launch that follows a host synchronisation
-        # starts on a clocked-down chip -- the shader clock takes tens of ms to come up -- and the kernel's time follows the clock)
-        t1 = time.perf_counter()
-        while time.perf_counter() - t1 < 0.15:
-            for _ in range(10):
+        res["iso"] = res["power_alone"] = None
+        if full:
+            # the same kernel with the chip to itself (no timing-recovery kernel alongside), on the
+            # data it sees in the chain: behind the front end for the stock chain
+            yin = x
+            if stock:
+                fs2 = ais_amd.square_and_fft_sync_cc(sps * 9600.0, 9600.0, 1024, nchan=nchan, max_items=T)
+                agc2 = ais_amd.feedforward_agc_cc(512, 2.0, nchan=nchan, max_items=T + 1024)
+                yin = ais_amd.freq_sync_agc(fs2, agc2, x, out=yin_buf)[0]
+                del fs2, agc2
+            if yout is None:
+                yout = torch.empty((nchan, T), dtype=torch.complex64, device=device)
+            # (launches back to back for 0.15 s, then twenty timed ones: a launch that follows a host synchronisation
+            # starts on a clocked-down chip -- the shader clock takes tens of ms to come up -- and the kernel's time follows the clock)
+            t1 = time.perf_counter()
+            while time.perf_counter() - t1 < 0.15:
+                for _ in range(10):
+                    corr.work(yin, out=yout)
+                torch.cuda.synchronize()
+            for _ in range(5):
+                corr.work(yin, out=yout)
+            corr.set_profiling(True)
+            ps_iso = PowerSampler(local_rank).start()
+            for _ in range(20):
                 corr.work(yin, out=yout)
             torch.cuda.synchronize()
-        for _ in range(5):
-            corr.work(yin, out=yout)
-        corr.set_profiling(True)
-        ps_iso = PowerSampler(local_rank).start()
-        for _ in range(20):
-            corr.work(yin, out=yout)
-        torch.cuda.synchronize()
-        res["power_alone"] = ps_iso.stop()
-        iso = corr.kernel_ms_history()[-20:]
+            res["power_alone"] = ps_iso.stop()
+            res["iso"] = corr.kernel_ms_history()[-20:]
+            del yin
         res["el"] = max_over_ranks(el, device=device)
         res["el_min"] = -max_over_ranks(-el, device=device)
-        res["iso"] = iso
-        del dem, x, y_corr, yin, yout, yin_buf
+        del dem, x, y_corr, yout, yin_buf
         torch.cuda.empty_cache()
         return res
 
@@ -810,10 +873,10 @@ def main():
         torch.cuda.empty_cache()
         return r
 
-    r = measure(args.chain, True)
+    r = measure(args.chain, args.full, full=args.full, dump=args.dump_outputs)
     el, kern_ms, iso, st = r["el"], r["kern_ms"], r["iso"], r["st"]
-    side = not args.single_chain
-    # the default run also times the two-block chain the metric string names, and the correlator alone
+    side = args.full and not args.single_chain
+    # a --full run also times the two-block chain the metric string names, and the correlator alone
     extra = measure("core", False) if (args.chain == "stock" and side) else None
     # the caveats of the headline as numbers: the same steps without the one-buffer look-ahead (x_next = None: every
     # step estimates for itself), and with the time-parallel timing recovery (opt-in, include/aisx.h)
@@ -827,7 +890,7 @@ def main():
     if side and world == 1:
         corr_only = [measure_corr_only(c, f) for c in (256, 4096) for f in ("S", "P")]
 
-    # BASELINE config 4's per-GPU shape (8192 channels) as a side measurement of the default run: there the
+    # BASELINE config 4's per-GPU shape (8192 channels) as a side measurement of a --full run: there the
     # timing recovery hides behind the sample passes, and every millisecond taken off those shows one to one
     c4 = measure("stock", False, nch=8192) if (args.chain == "stock" and side and world == 1 and nchan != 8192) else None
     h2d = measure_h2d(torch, device) if (rank == 0 and side and world == 1) else None
@@ -880,31 +943,33 @@ def main():
                 "bound": "hbm",
                 "achieved": achieved,
                 "peak": HBM_PEAK_GBS,
-                "copy_ceiling_GBs": copy_gbs,
-                "frac_of_copy_ceiling": (achieved / copy_gbs) if copy_gbs else None,
                 "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBS,
                 "traffic": traffic,
                 "traffic_static": True,  # (read from the committed PMC summary of this workload, not collected in this run)
                 "traffic_source": traffic_src,
                 "kernel_ms": kms,
+                "note": "kernel_ms is measured over the timed region, where the timing-recovery kernel of the "
+                        "previous step shares the chip" + ("; *_alone = same launch with nothing else running; copy_ceiling_GBs = "
+                        "read + write rate of a plain float4 copy of 2 GiB on this box (hipEvents, no profiler)" if args.full else ""),
+                "algorithmic_bytes_per_launch": CORR_BYTES_PER_SAMPLE * float(nchan) * T,
+            },
+            "detections_last_step": r["ndet"],
+            "tag_overflow": r["tag_overflow"],
+            "msk_status": int(st),
+        }
+        if args.full:
+            line["roofline"].update({
+                "copy_ceiling_GBs": copy_gbs,
+                "frac_of_copy_ceiling": (achieved / copy_gbs) if copy_gbs else None,
                 "kernel_ms_alone": float(np.mean(iso)),
                 "power": {"timed_region": r.get("power"), "kernel_alone": r.get("power_alone"),
                           "note": "package power (W) and shader clock (MHz) from the GPU's hwmon files while the measurement ran; "
                                   "the package limit is 1400 W, the clock's ceiling 2400 MHz: the correlator alone sits at the "
                                   "limit and its time follows the clock (DESIGN.md 4.1)"},
                 "frac_alone": CORR_BYTES_PER_SAMPLE * float(nchan) * T / (float(np.mean(iso)) * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "energy_split_alone": energy_split() if tmpl.size > 512 else None,
-                "note": "kernel_ms is measured over the timed region, where the timing-recovery kernel of the "
-                        "previous step shares the chip; *_alone = same launch with nothing else running; copy_ceiling_GBs = "
-                        "read + write rate of a plain float4 copy of 2 GiB on this box (hipEvents, no profiler)",
-                "algorithmic_bytes_per_launch": CORR_BYTES_PER_SAMPLE * float(nchan) * T,
-            },
-            "parity": r["parity"],
-            "detections_last_step": r["ndet"],
-            "tag_overflow": r["tag_overflow"],
-            "msk_status": int(st),
-        }
+                "energy_split_alone": energy_split() if tmpl.size > 512 else None})
+            line["parity"] = r["parity"]
         if ceil is not None:
             # what this box's HBM sustains by access shape (tools/ubench/hbm_ceiling.hip, 2 GiB buffers, hipEvents): the
             # correlator moves 8 B in + 8 B out per sample, so the copy figure is its practical ceiling
@@ -982,7 +1047,7 @@ def main():
             }
         if corr_only is not None:
             line["corr_only"] = corr_only
-        if not args.no_cpu_baseline and world == 1:  # (the CPU path is timed beside the one-GPU run only)
+        if args.full and not args.no_cpu_baseline and world == 1:  # (the CPU path is timed beside the one-GPU run only)
             line["cpu_baseline"] = cpu_baseline(args.chain if args.chain != "corr" else "core", args.template, sps, T)
         # the side measurements once more under keys the driver's record keeps whole (it stores `config`, `roofline` and
         # `cpu_baseline` in full and only the NAMES of other top-level keys)
@@ -997,9 +1062,10 @@ def main():
             line["roofline"]["msk"] = line["roofline_msk"]
         if "corr_only" in line:
             line["roofline"]["corr_only"] = line["corr_only"]
-        line["roofline"]["parity_of_this_run"] = {k: line["parity"][k] for k in ("detections", "detections_matched_within_1", "mag_rtol_max",
-                                                                                  "time_est_abs_max", "bursts_compared", "bursts_in_place",
-                                                                                  "bursts_within_4") if line.get("parity") and k in line["parity"]}
+        if args.full:
+            line["roofline"]["parity_of_this_run"] = {k: line["parity"][k] for k in (
+                "detections", "detections_matched_within_1", "mag_rtol_max", "time_est_abs_max", "bursts_compared", "bursts_in_place",
+                "bursts_within_4") if line.get("parity") and k in line["parity"]}
         print(json.dumps(line))
     if use_dist:
         dist.barrier()

@@ -467,12 +467,20 @@ def test_chain_front_end_claim_is_near_the_best_of_a_sweep(ais, nchan):
     # tools/claim_sweep.py).  The gate: a step with the chain's own choice takes at most 2 % longer than the best of
     # {no claim, 24, 48, 63 KB} set by hand on the same chain object, medians of three interleaved runs of 20 steps;
     # a claim never changes a result (test_config3 / test_config4 run with it, their twins without).
-    import importlib.util
+    # The sweep runs in a process of its own with the eight hardware queues the chain's streams are made for (DESIGN.md
+    # 4.8; the runtime reads GPU_MAX_HW_QUEUES once, at its first call, and this process has made that call): with
+    # fewer, two of the streams share a queue and run in turn, and the kernels the claim places beside each other no
+    # longer overlap.
+    import json
+    import subprocess
+    import sys
 
-    spec = importlib.util.spec_from_file_location("claim_sweep", os.path.join(ROOT, "tools", "claim_sweep.py"))
-    cs = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cs)
-    r = cs.sweep(nchan, [0, 24, 48, 63], steps=20, reps=3)
+    code = ("import json, sys; sys.path.insert(0, %r); import claim_sweep as cs; "
+            "print(json.dumps(cs.sweep(%d, [0, 24, 48, 63], steps=20, reps=3)))" % (os.path.join(ROOT, "tools"), nchan))
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, GPU_MAX_HW_QUEUES="8"), capture_output=True,
+                         text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    r = json.loads(out.stdout.strip().splitlines()[-1])
     print("claim sweep at %d channels: chosen %d B -> %.3f ms per step; by hand %s" % (
         nchan, r["chosen_claim_bytes"], r["ms_per_step"]["chosen"], {k: v for k, v in r["ms_per_step"].items() if k != "chosen"}))
     assert r["chosen_claim_bytes"] > 0

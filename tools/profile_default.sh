@@ -6,4 +6,4 @@ set -e
 out=${1:-gpurun_out/prof}
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python bench.py > $out/bench_default.log 2> $out/bench_default.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python bench.py --full > $out/bench_default.log 2> $out/bench_default.err

@@ -71,9 +71,9 @@ if __name__ == "__main__":
     with open("profiles/%s_default_bench_kernel_stats.csv" % tag, "w") as f:
         f.write(open(stats).read())
     json.dump(line, open("profiles/%s_default_bench_line.json" % tag, "w"), indent=1)
-    md = ["# rocprofv3 --kernel-trace --stats -- python bench.py   (MI355X, default run)", "",
-          "Command on the GPU box: `cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && rocprofv3 --kernel-trace --stats "
-          "--output-format csv -d gpurun_out/<dir>/stats -- python bench.py`; summarised by `tools/summarize_profile.py`.", "",
+    md = ["# rocprofv3 --kernel-trace --stats -- python bench.py --full   (MI355X, default run)", "",
+          "Command: `tools/profile_default.sh <outdir>` (`rocprofv3 --kernel-trace --stats --output-format csv -d <outdir>/stats -- "
+          "python bench.py --full`); summarised by `tools/summarize_profile.py`.", "",
           "bench.py's line of the same run (`%s_default_bench_line.json`): value %.0f complex MS/s, %.2f ms/step, "
           "`roofline.kernel_ms` %.3f (hipEvents over the timed region), `kernel_ms_alone` %.3f."
           % (tag, line["value"], line["ms_per_step"], line["roofline"]["kernel_ms"], line["roofline"]["kernel_ms_alone"]), "",

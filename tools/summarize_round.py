@@ -46,10 +46,9 @@ stats = trace.replace("kernel_trace.csv", "kernel_stats.csv")
 st = {k: v for k, v in sp.timed_stats(trace, prof["steps"], prof["warmup"]).items()
       if not k.startswith(("k_mskp", "k_msk_ff"))}  # (kernels of the time-parallel side run only)
 open("profiles/%s_default_bench_kernel_stats.csv" % tag, "w").write(open(stats).read())
-md = ["# rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline   (MI355X, default run)", "",
-      "Command on the GPU box: `bash tools/profile_round.sh %s` (`cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && rocprofv3 "
-      "--kernel-trace --stats --output-format csv -d gpurun_out/prof_%s/stats -- python bench.py --no-cpu-baseline`); summarised by "
-      "`tools/summarize_round.py`." % (tag, tag), "",
+md = ["# rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline   (MI355X, default run)", "",
+      "Command: `bash tools/profile_round.sh %s` (its `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py "
+      "--full --no-cpu-baseline` run); summarised by `tools/summarize_round.py`." % tag, "",
       "bench.py's line of the SAME (profiled) run: %.0f complex MS/s, %.2f ms/step, `roofline.kernel_ms` %.3f (hipEvents over the "
       "timed region), `kernel_ms_alone` %.3f.  The plain run right before it on the same box (`%s_default_bench_line.json`): "
       "%.0f complex MS/s, %.2f ms/step, `roofline.kernel_ms` %.3f."
@@ -261,7 +260,7 @@ try:
     cands = glob.glob(os.path.join(src, "c4stats", "*", "*kernel_trace.csv"))
     tr = max(cands, key=lambda f: open(f).read().count("k_msk<"))
     st4 = {k: v for k, v in sp.timed_stats(tr, c4["steps"], c4["warmup"]).items() if not k.startswith(("k_mskp", "k_msk_ff"))}
-    md = ["# rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --parity-channels 0 --single-chain --config4 --steps 30", "",
+    md = ["# rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --parity-channels 0 --single-chain --config4 --steps 30", "",
           "BASELINE config 4's per-GPU shape (8192 channels x 65536 samples per step) on one MI355X.  bench.py's line of this (profiled) "
           "run: %.0f complex MS/s, %.2f ms/step, correlator %.3f ms in the chain." % (c4["value"], c4["ms_per_step"], c4["roofline"]["kernel_ms"]), "",
           "| kernel | timed launches | avg ms | min ms | max ms |", "|---|---|---|---|---|"]
