@@ -73,6 +73,12 @@ class corr_est_cc:
         """placement knob of the F = 4096 build (include/aisx.h: aisx_corr_set_lds_claim); results do not depend on it"""
         check(_lib.lib().aisx_corr_set_lds_claim(self._h, int(nbytes)), "set_lds_claim")
 
+    def get_lds_claim(self):
+        """(claim, used): the claim in force and the LDS a workgroup of the F = 4096 build uses (0: the F = 2048 build)"""
+        b, u = C.c_int(0), C.c_int(0)
+        check(_lib.lib().aisx_corr_get_lds_claim(self._h, C.byref(b), C.byref(u)), "get_lds_claim")
+        return b.value, u.value
+
     def history(self):
         return _lib.lib().aisx_corr_history(self._h)
 

@@ -6,6 +6,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <map>
+#include <mutex>
+#include <utility>
+
 #include "../../include/aisx.h"
 #include "aisx_common.h"
 
@@ -53,6 +57,38 @@ inline int require_device()
     if (e != hipSuccess || n <= 0) {
         set_err("no HIP device available (libaisx has no CPU fallback)");
         return AISX_ERR_NO_DEVICE;
+    }
+    return AISX_OK;
+}
+
+// The dynamic-LDS limit hipFuncSetAttribute sets belongs to a kernel on a device, not to a handle: handles of one kernel
+// that ask for different sizes (template lengths, placement claims) share it, and one that set it lower than another
+// had raised it would make that one's next launch ask for more than the limit.  ensure_dyn_lds raises the current
+// device's limit for `kernel` to at least `bytes` and never lowers it: one record per (device, kernel), starting at
+// the runtime's 64 KB default, behind a mutex (handles are driven from several host threads).  A size above the
+// device's LDS per CU is refused (AISX_ERR_INVALID, `who` in the message) and nothing is set.
+inline int ensure_dyn_lds(const void* kernel, int bytes, const char* who)
+{
+    static std::mutex mu;
+    static std::map<std::pair<int, const void*>, int> raised; // (device, kernel) -> limit set so far
+    static std::map<int, int> lds_cu;                         // device -> hipDeviceProp_t::maxSharedMemoryPerMultiProcessor
+    int dev = 0;
+    AISX_HIPCHK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    auto d = lds_cu.find(dev);
+    if (d == lds_cu.end()) {
+        hipDeviceProp_t prop;
+        AISX_HIPCHK(hipGetDeviceProperties(&prop, dev));
+        d = lds_cu.emplace(dev, (int)prop.maxSharedMemoryPerMultiProcessor).first;
+    }
+    if (bytes > d->second) {
+        set_err("%s: a workgroup would need %d bytes of LDS, device %d has %d per CU", who, bytes, dev, d->second);
+        return AISX_ERR_INVALID;
+    }
+    int& limit = raised.emplace(std::make_pair(dev, kernel), 64 * 1024).first->second;
+    if (bytes > limit) {
+        AISX_HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        limit = bytes;
     }
     return AISX_OK;
 }

@@ -310,8 +310,6 @@ struct aisx_corr {
     // F = 4096 with dma: 0 = k_corr4d.h, 1 = the 512-thread build k_corr4e.h, 2 = k_corr4f.h (1 and 2: the template
     // spectrum in the order of the 8 x 8 x 8 x 8 plan)
     int wide = AISX_CORR_WIDE_DEFAULT;
-    const void* dma_attr_set = nullptr; // build whose dynamic-LDS limit has been raised ...
-    int dma_attr_bytes = 0;             // ... and to how many bytes
     int lds_claim = 0; // aisx_corr_set_lds_claim: LDS a workgroup of the F = 4096 build claims beyond what it uses
     float sps = 0, thresh = 0;
     unsigned mark_delay = 0;
@@ -358,7 +356,9 @@ static int corr_upload_taps(aisx_corr* h)
         hipLaunchKernelGGL(k_corr4_inith, dim3(1), dim3(CF4_T), CF4_LDS_BYTES, 0, ip);
 #endif
     else {
-        AISX_HIPCHK(hipFuncSetAttribute((const void*)k_corr4e_inith, hipFuncAttributeMaxDynamicSharedMemorySize, CE_LDS_BYTES));
+        int rc = ensure_dyn_lds((const void*)k_corr4e_inith, CE_LDS_BYTES, "corr_est_cc: the template's transform");
+        if (rc != AISX_OK)
+            return rc;
         hipLaunchKernelGGL(k_corr4e_inith, dim3(1), dim3(CE_T), CE_LDS_BYTES, 0, ip);
     }
     AISX_HIPCHK(hipGetLastError());
@@ -626,6 +626,32 @@ extern "C" int aisx_corr_process(aisx_corr* h, const aisx_cf32* d_in, long in_st
         nseg = (ntiles + tps - 1) / tps;
     }
 
+    // The builds whose dynamic LDS may exceed the runtime's default (the F = 4096 ones: what they use + the placement
+    // claim): the kernel and its size are settled, and its limit raised, before anything of the handle or the call's
+    // buffers changes -- a size the device cannot give refuses the call with nothing launched.
+    void (*kbig)(CorrParams) = nullptr;
+    int kbig_threads = 0, kbig_bytes = 0;
+#ifdef AISX_EXPERIMENTS
+    // (LDS a workgroup claims beyond what it uses decides how many of them fit beside the timing recovery's 92 160 bytes on a CU)
+    static const int lds_pad_env = exp_env("AISX_CORR_LDS_PAD") ? atoi(exp_env("AISX_CORR_LDS_PAD")) : 0;
+    const int lds_pad = lds_pad_env + h->lds_claim;
+    const bool f4dma = h->F == CF4_F && dma;
+    if (f4dma && h->wide == 0)
+        kbig = corr4d_pick(h->N), kbig_threads = CF4_T, kbig_bytes = CD_LDS_BYTES + lds_pad;
+    else if (f4dma && h->wide == 1)
+        kbig = corr4e_pick(h->N), kbig_threads = CE_T, kbig_bytes = CE_LDS_BYTES + lds_pad;
+    else if (f4dma)
+#else
+    const int lds_pad = h->lds_claim;
+    if (h->F == CF4_F)
+#endif
+        kbig = corr4f_pick(h->N), kbig_threads = CE_T, kbig_bytes = cfz_lds_bytes(h->N) + lds_pad;
+    if (kbig) {
+        const int rc = ensure_dyn_lds((const void*)kbig, kbig_bytes, "aisx_corr_process");
+        if (rc != AISX_OK)
+            return rc;
+    }
+
     AISX_HIPCHK(hipMemsetAsync(h->d_abits, 0, sizeof(unsigned long long) * (size_t)h->nchan * h->abits_stride, st));
     CorrParams p;
     p.in = (const cf*)d_in;
@@ -651,38 +677,17 @@ extern "C" int aisx_corr_process(aisx_corr* h, const aisx_cf32* d_in, long in_st
     const int evi = (int)(h->ncalls_prof % aisx_corr::NEV);
     if (h->prof)
         AISX_HIPCHK(hipEventRecord(h->ev0[evi], st));
-    int rc_launch = AISX_OK;
-    auto launch_big_lds = [&](void (*kern)(CorrParams), int threads, int lds_bytes) -> int {
-        if (h->dma_attr_set != (const void*)kern || lds_bytes > h->dma_attr_bytes) { // (per handle: handles may live on different devices)
-            AISX_HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-            h->dma_attr_set = (const void*)kern;
-            h->dma_attr_bytes = lds_bytes;
-        }
-        hipLaunchKernelGGL(kern, dim3(nseg, h->nchan), dim3(threads), lds_bytes, st, p);
-        return AISX_OK;
-    };
 #ifdef AISX_EXPERIMENTS
-    // (LDS a workgroup claims beyond what it uses decides how many of them fit beside the timing recovery's 92 160 bytes on a CU)
-    static const int lds_pad_env = exp_env("AISX_CORR_LDS_PAD") ? atoi(exp_env("AISX_CORR_LDS_PAD")) : 0;
-    const int lds_pad = lds_pad_env + h->lds_claim;
     if (h->F == CF_F && !dma)
         hipLaunchKernelGGL(k_corr_main, dim3(nseg, h->nchan), dim3(CF_T), CF_LDS_BYTES, st, p);
     else if (h->F == CF4_F && !dma)
         hipLaunchKernelGGL(k_corr4_main, dim3(nseg, h->nchan), dim3(CF4_T), CF4_LDS_BYTES, st, p);
-    else if (h->F == CF4_F && h->wide == 0)
-        rc_launch = launch_big_lds(corr4d_pick(h->N), CF4_T, CD_LDS_BYTES + lds_pad);
-    else if (h->F == CF4_F && h->wide == 1)
-        rc_launch = launch_big_lds(corr4e_pick(h->N), CE_T, CE_LDS_BYTES + lds_pad);
     else
-#else
-    const int lds_pad = h->lds_claim;
 #endif
-    if (h->F == CF_F)
-        hipLaunchKernelGGL(corr2d_pick(h->N), dim3(nseg, h->nchan), dim3(CF_T), C2_LDS_BYTES, st, p);
+    if (kbig)
+        hipLaunchKernelGGL(kbig, dim3(nseg, h->nchan), dim3(kbig_threads), kbig_bytes, st, p);
     else
-        rc_launch = launch_big_lds(corr4f_pick(h->N), CE_T, cfz_lds_bytes(h->N) + lds_pad);
-    if (rc_launch != AISX_OK)
-        return rc_launch;
+        hipLaunchKernelGGL(corr2d_pick(h->N), dim3(nseg, h->nchan), dim3(CF_T), C2_LDS_BYTES, st, p);
     AISX_HIPCHK(hipGetLastError());
     if (h->prof) {
         AISX_HIPCHK(hipEventRecord(h->ev1[evi], st));
@@ -774,6 +779,17 @@ extern "C" int aisx_corr_set_lds_claim(aisx_corr* h, int bytes)
         return AISX_ERR_INVALID;
     }
     h->lds_claim = bytes;
+    return AISX_OK;
+}
+
+extern "C" int aisx_corr_get_lds_claim(const aisx_corr* h, int* bytes, int* used_bytes)
+{
+    if (!h)
+        return AISX_ERR_INVALID;
+    if (bytes)
+        *bytes = h->lds_claim;
+    if (used_bytes) // (the F = 2048 build takes no claim)
+        *used_bytes = h->F == CF4_F ? cfz_lds_bytes(h->N) : 0;
     return AISX_OK;
 }
 

@@ -101,7 +101,6 @@ static int msk_launch(const MskParams& p, int nwg, hipStream_t st)
         k_msk<false, false, 8>,  k_msk<false, true, 8>,  k_msk<true, false, 8>,  k_msk<true, true, 8>,
         k_msk<false, false, 4>,  k_msk<false, true, 4>,  k_msk<true, false, 4>,  k_msk<true, true, 4>,
     };
-    static bool big_lds[20] = { false };
     const int li = p.lpw == 16 ? 0 : (p.lpw == 32 ? 1 : (p.lpw == 64 ? 2 : (p.lpw == 8 ? 3 : 4)));
     const int v = li * 4 + (((p.err || p.mu_out) ? 2 : 0) | (p.osps == 2 ? 1 : 0));
     // LDS beyond what the kernel uses keeps other streams' workgroups off this CU: a knob for how
@@ -112,21 +111,17 @@ static int msk_launch(const MskParams& p, int nwg, hipStream_t st)
     }();
     const int lds = std::min(msk_lds_bytes(p.lpw) + pad, 160 * 1024);
     kfn fn = fns[v];
-    bool* big = &big_lds[v];
     if (p.ff) { // the join of the time-parallel recovery: a build of its own (stream mode, osps 1, no err / mu)
         static const kfn ffs[5] = { k_msk_ff<16>, k_msk_ff<32>, k_msk_ff<64>, k_msk_ff<8>, k_msk_ff<4> };
-        static bool big_ff[5] = { false };
         if (p.err || p.mu_out || p.osps == 2) {
             set_err("msk_launch: the join build has no err / mu ports and osps == 1");
             return AISX_ERR_INVALID;
         }
         fn = ffs[li];
-        big = &big_ff[li];
     }
-    if (!*big) {
-        AISX_HIPCHK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        *big = true;
-    }
+    int rc = ensure_dyn_lds((const void*)fn, lds, "msk_timing_recovery_cc");
+    if (rc != AISX_OK)
+        return rc;
     // a workgroup = msk_waves(lpw) waves with lpw channels each
     hipLaunchKernelGGL(fn, dim3(nwg), dim3(64 * msk_waves(p.lpw)), lds, st, p);
     AISX_HIPCHK(hipGetLastError());
@@ -902,12 +897,9 @@ static int msk_process_stream(aisx_msk* h, const aisx_cf32* d_in, long in_stride
         p.ucap = (long)h->nchan * MSKP_SMAX;
         p.tail = mskp_tail(h->d_sps);
         p.max_noutput = h->max_noutput;
-        static bool attr_set = false;
-        if (!attr_set) {
-            AISX_HIPCHK(hipFuncSetAttribute((const void*)k_mskp_units, hipFuncAttributeMaxDynamicSharedMemorySize, MSKP_LDS_BYTES));
-            AISX_HIPCHK(hipFuncSetAttribute((const void*)k_mskp_join, hipFuncAttributeMaxDynamicSharedMemorySize, MSKP_LDS_BYTES));
-            attr_set = true;
-        }
+        if ((rc = ensure_dyn_lds((const void*)k_mskp_units, MSKP_LDS_BYTES, "msk_timing_recovery_cc: the restart units")) != AISX_OK ||
+            (rc = ensure_dyn_lds((const void*)k_mskp_join, MSKP_LDS_BYTES, "msk_timing_recovery_cc: the join")) != AISX_OK)
+            return rc;
         if (t_smax > 0) {
             const long units = (long)h->nchan * h->tp_smax;
             hipLaunchKernelGGL(k_mskp_units, dim3((unsigned)((units + 63) / 64 + (tp_sorted ? MSKP_NCLS : 0))), dim3(64), MSKP_LDS_BYTES, su, p);

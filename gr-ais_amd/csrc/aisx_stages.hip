@@ -152,9 +152,7 @@ struct aisx_freqsync {
     // made by aisx_freqest_create with a vector length the freq_sync kernels do not implement: the handle serves
     // aisx_freqest_work / aisx_freqest_work_host only (the search over bins needs no transform of ours)
     bool est_only = false;
-    // aisx_freqsync_set_walk_lds_claim: LDS a workgroup of the phase walk claims beyond the 3 KB it uses, and what this
-    // handle has raised the kernel's dynamic-LDS limit to
-    int walk_claim = 0, walk_attr = 64 * 1024;
+    int walk_claim = 0; // aisx_freqsync_set_walk_lds_claim: LDS a workgroup of the phase walk claims beyond the 3 KB it uses
     float binsize = 0, sensitivity = 0;
     cf* d_pend[2] = { nullptr, nullptr };
     int cur = 0, npend = 0;
@@ -560,8 +558,6 @@ struct aisx_agc {
     int cur = 0;
     bool tiles_only = false; // aisx_agc_set_streaming(h, 0): the tile kernels for every call
     int lds_claim = 0; // aisx_agc_set_lds_claim: LDS a streaming workgroup claims beyond the 8 KB it uses
-    int lds_attr = 64 * 1024; // dynamic LDS a k_agcw<true> launch of THIS handle may ask for (raised per handle: handles
-                              // may live on different devices, and the attribute is a per-device one)
     cf *d_hst_in = nullptr, *d_hst_out = nullptr; // aisx_agc_work_host's staging (grown, never shrunk)
     size_t hst_in_cap = 0, hst_out_cap = 0;
 };
@@ -830,10 +826,9 @@ static int fs_estimate_into_slot(aisx_freqsync* h, const aisx_cf32* d_in, long i
     // AISX_WALK_LDS_PAD, bytes, overrides it)
     static const int walk_pad_env = exp_env("AISX_WALK_LDS_PAD") ? atoi(exp_env("AISX_WALK_LDS_PAD")) : -1;
     const int walk_pad = walk_pad_env >= 0 ? walk_pad_env : h->walk_claim;
-    if (FSW_LDS_BYTES + walk_pad > h->walk_attr) {
-        AISX_HIPCHK(hipFuncSetAttribute((const void*)k_fs_walk, hipFuncAttributeMaxDynamicSharedMemorySize, FSW_LDS_BYTES + walk_pad));
-        h->walk_attr = FSW_LDS_BYTES + walk_pad;
-    }
+    int rc = ensure_dyn_lds((const void*)k_fs_walk, FSW_LDS_BYTES + walk_pad, "square_and_fft_sync_cc: the phase walk");
+    if (rc != AISX_OK)
+        return rc;
     hipLaunchKernelGGL(k_fs_walk, dim3((h->nchan + FSW_T - 1) / FSW_T), dim3(FSW_T), FSW_LDS_BYTES + walk_pad, st_walk, w);
     AISX_HIPCHK(hipGetLastError());
     AISX_HIPCHK(hipEventRecord(h->ev_walk, st_walk));
@@ -907,7 +902,13 @@ extern "C" int aisx_freqsync_agc_process(aisx_freqsync* h, aisx_agc* a, const ai
         set_err("aisx_freqsync_agc_process: %d output items exceed the AGC's max_items %d or the output stride", total, a->max_items);
         return AISX_ERR_INVALID;
     }
+    // the streaming AGC's LDS (what it uses + the placement claim), its limit raised before either handle changes
+    static const int agcw_pad = exp_env("AISX_AGCW_LDS_PAD") ? atoi(exp_env("AISX_AGCW_LDS_PAD")) : -1; // (experiments: overrides the handle's claim)
+    const bool agcw = agcw_applies(a->W, total) && !a->tiles_only;
+    const int agcw_lds = AGW_LDS_BYTES + (agcw_pad >= 0 ? agcw_pad : a->lds_claim);
     int rc;
+    if (agcw && (rc = ensure_dyn_lds((const void*)k_agcw<true>, agcw_lds, "aisx_freqsync_agc_process")) != AISX_OK)
+        return rc;
     if ((rc = fs_fused_prepare(h)) != AISX_OK)
         return rc;
     if (h->ahead_cnt > 0 && (h->ahead_q[0].in != (const void*)d_in || h->ahead_q[0].stride != in_stride || h->ahead_q[0].n != n)) {
@@ -954,15 +955,8 @@ extern "C" int aisx_freqsync_agc_process(aisx_freqsync* h, aisx_agc* a, const ai
     p.pend_out = h->d_pend[h->cur ^ 1];
     p.npend = h->npend;
     p.n_raw = n;
-    static const int agcw_pad = exp_env("AISX_AGCW_LDS_PAD") ? atoi(exp_env("AISX_AGCW_LDS_PAD")) : -1; // (experiments: overrides the handle's claim)
-    if (agcw_applies(p.W, total) && !a->tiles_only) {
-        const int lds = AGW_LDS_BYTES + (agcw_pad >= 0 ? agcw_pad : a->lds_claim);
-        if (lds > a->lds_attr) { // (what a launch may ask for before the kernel's limit is raised)
-            AISX_HIPCHK(hipFuncSetAttribute((const void*)k_agcw<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            a->lds_attr = lds;
-        }
-        hipLaunchKernelGGL(k_agcw<true>, dim3(agcw_grid(total), h->nchan), dim3(AGW_T), lds, st, p);
-    }
+    if (agcw)
+        hipLaunchKernelGGL(k_agcw<true>, dim3(agcw_grid(total), h->nchan), dim3(AGW_T), agcw_lds, st, p);
     else
         hipLaunchKernelGGL(k_agc8, dim3(p.ntiles, h->nchan), dim3(AGC8_T), AGC8_LDS_BYTES_MIXED, st, p);
     AISX_HIPCHK(hipGetLastError());

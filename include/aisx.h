@@ -114,13 +114,19 @@ int aisx_corr_reset(aisx_corr* h); /* zero history, nitems_written = 0 */
 int aisx_corr_process(aisx_corr* h, const aisx_cf32* d_in, long in_stride, aisx_cf32* d_out, long out_stride,
                       aisx_cf32* d_corr, long corr_stride, int n, void* stream);
 /* Placement knob (as aisx_agc_set_lds_claim): LDS a workgroup of the F = 4096 build (templates of 513 .. 2048 items) claims
- * beyond the ~55 KB it uses.  17 408 bytes keep its workgroups off the CUs that hold a timing-recovery workgroup (55 + 17 KB
- * does not fit beside 90) while two still fit a free CU: in the 4096-channel chain the recovery then runs up to 0.25 ms shorter
- * and the step up to 3 % (5.31 against 5.49 ms on one box, nothing on another), the correlator itself a third longer (1.98
- * against 1.50 ms) -- a caller's choice
- * between the step and this kernel's own rate; aisx_chain_create leaves it alone (bench.py: config.side.corr_off_recovery_cus).
- * Results do not depend on it; default 0.  Not part of the GNU Radio API. */
+ * beyond what it uses (aisx_corr_get_lds_claim: 49 KB at 513 items to 74 KB at 2048).  The rule: a claim with used + claim
+ * greater than what a timing-recovery workgroup leaves on a CU (LDS per CU - aisx_msk_placement's bytes) keeps the
+ * correlator's workgroups off the CUs that hold one; two still fit a free CU while 2 x (used + claim) <= LDS per CU.  At 896
+ * items (55 KB used) 17 408 bytes do that: in the 4096-channel chain the recovery then runs up to 0.25 ms shorter and the step
+ * up to 3 % (5.31 against 5.49 ms on one box, nothing on another), the correlator itself a third longer (1.98 against
+ * 1.50 ms) -- a caller's choice between the step and this kernel's own rate; aisx_chain_create leaves it alone (bench.py:
+ * config.side.corr_off_recovery_cus).  Results do not depend on it; default 0.  A call whose used + claim exceeds the
+ * device's LDS per CU is refused by aisx_corr_process (AISX_ERR_INVALID, nothing launched, the handle unchanged).  Not part
+ * of the GNU Radio API. */
 int aisx_corr_set_lds_claim(aisx_corr* h, int bytes);
+/* the claim in force, and the LDS a workgroup of the F = 4096 build uses itself for this template length (0: the F = 2048
+ * build serves it, and takes no claim); either pointer may be NULL */
+int aisx_corr_get_lds_claim(const aisx_corr* h, int* bytes, int* used_bytes);
 /* measurement hook: when on, aisx_corr_process brackets the main correlator
  * kernel with hipEvents on the launch stream; aisx_corr_last_kernel_ms waits for
  * the last bracket and returns its duration. */
