@@ -33,4 +33,8 @@ def __getattr__(name):
         from . import blocks
 
         return getattr(blocks, name)
+    if name in ("hdlc_deframer_batch", "PDU_DTYPE"):
+        from . import batch_framing
+
+        return getattr(batch_framing, name)
     raise AttributeError(name)

@@ -175,6 +175,12 @@ def lib(device=True):
     sig("aisx_hdlc_destroy", i32, [vp])
     sig("aisx_hdlc_work", i32, [vp, vp, i32, vp, i32, vp, i32, pi32])
     sig("aisx_pdu_to_nmea", i32, [C.c_char_p, vp, i32, C.c_char_p, i32])
+    sig("aisx_hdlc_batch_create", i32, [pvp, i32, i32, i32, i32, i32])
+    sig("aisx_hdlc_batch_destroy", i32, [vp])
+    sig("aisx_hdlc_batch_reset", i32, [vp])
+    sig("aisx_hdlc_batch_process", i32, [vp, vp, lng, vp, vp])
+    sig("aisx_hdlc_batch_results_device", i32, [vp, pvp, pvp, pvp])
+    sig("aisx_hdlc_batch_read", i32, [vp, vp, i32, vp, lng, pi32, vp])
     _lib = L
     return L
 

@@ -1,0 +1,268 @@
+// aisx_hdlc.hip -- C ABI of the batched HDLC deframer (include/aisx.h, aisx_hdlc_batch_*): per call, one wave per
+// channel deframes that channel's bits (k_hdlc.h: hdlc_deframe_body) into a staging area of its own, one workgroup
+// places the channels' records one behind the other (hdlc_scan_body) and one wave per channel copies them there
+// (hdlc_gather_body).  Everything is queued on the caller's stream; the per-channel bit counts are read on the device.
+#include <limits.h>
+
+#include "aisx_devctx.h"
+#include "aisx_host.h"
+#include "k_hdlc.h"
+
+using namespace aisx;
+
+static_assert(sizeof(HdlcRec) == sizeof(aisx_pdu), "pdu record layout");
+static_assert(HD_LDS_BYTES + 2 * HD_SCAN_T * 8 <= 64 * 1024, "static LDS");
+
+__global__ __launch_bounds__(HD_T) void k_hdlc_deframe(HdlcParams p)
+{
+    __shared__ __attribute__((aligned(16))) char smem[HD_LDS_BYTES];
+    DevCtx cx{ smem };
+    hdlc_deframe_body(cx, p);
+}
+
+__global__ __launch_bounds__(HD_SCAN_T) void k_hdlc_scan(HdlcScanParams p)
+{
+    __shared__ __attribute__((aligned(16))) char smem[2 * HD_SCAN_T * 8];
+    DevCtx cx{ smem };
+    hdlc_scan_body(cx, p);
+}
+
+__global__ __launch_bounds__(HD_T) void k_hdlc_gather(HdlcGatherParams p)
+{
+    DevCtx cx{ nullptr };
+    hdlc_gather_body(cx, p);
+}
+
+struct aisx_hdlc_batch {
+    int dev = 0;
+    int lmin = 0, lmax = 0, nchan = 0, max_bits = 0, max_pdus = 0;
+    int carry_words = 0, rec_cap = 0, byte_cap = 0;
+    long long out_bytes_cap = 0;
+    HdlcState* d_st = nullptr;
+    unsigned long long* d_carry = nullptr;
+    HdlcRec* d_srec = nullptr;
+    unsigned char* d_sbytes = nullptr;
+    int* d_cnt = nullptr;   // [nchan] records, [nchan] bytes
+    long long* d_base = nullptr; // [nchan] record bases, [nchan] byte bases
+    int* d_count = nullptr; // [0] found, [1] kept, [2] bad-count flag
+    hipEvent_t done = nullptr; // behind the last call's work (reset waits for it)
+    HdlcRec* d_out = nullptr;
+    unsigned char* d_out_bytes = nullptr;
+};
+
+namespace {
+
+// the calls run on the device that was current when the handle was created, and leave the caller's current
+struct OnDevice {
+    int prev = -1;
+    hipError_t err = hipSuccess;
+    explicit OnDevice(int dev)
+    {
+        if ((err = hipGetDevice(&prev)) == hipSuccess && prev != dev)
+            err = hipSetDevice(dev);
+    }
+    ~OnDevice()
+    {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev)
+            (void)hipSetDevice(prev);
+    }
+};
+
+} // namespace
+
+extern "C" int aisx_hdlc_batch_destroy(aisx_hdlc_batch* h)
+{
+    if (!h)
+        return AISX_OK;
+    OnDevice on(h->dev);
+    dev_free(h->d_st);
+    dev_free(h->d_carry);
+    dev_free(h->d_srec);
+    dev_free(h->d_sbytes);
+    dev_free(h->d_cnt);
+    dev_free(h->d_base);
+    dev_free(h->d_count);
+    dev_free(h->d_out);
+    dev_free(h->d_out_bytes);
+    if (h->done)
+        (void)hipEventDestroy(h->done);
+    delete h;
+    return AISX_OK;
+}
+
+extern "C" int aisx_hdlc_batch_create(aisx_hdlc_batch** out, int length_min, int length_max, int nchan, int max_bits,
+                                      int max_pdus)
+{
+    if (!out)
+        return AISX_ERR_INVALID;
+    *out = nullptr;
+    if (length_min < 2 || length_max < length_min || length_max > HD_MAX_OCTETS || nchan < 1 || max_bits < 1 ||
+        max_bits > (1 << 28) || max_pdus < 1) {
+        set_err("aisx_hdlc_batch_create: need 2 <= length_min <= length_max <= %d, nchan >= 1, 1 <= max_bits <= 2^28, "
+                "max_pdus >= 1", HD_MAX_OCTETS);
+        return AISX_ERR_INVALID;
+    }
+    int rc = require_device();
+    if (rc != AISX_OK)
+        return rc;
+    aisx_hdlc_batch* h = new aisx_hdlc_batch();
+    if (hipGetDevice(&h->dev) != hipSuccess) {
+        delete h;
+        set_err("aisx_hdlc_batch_create: hipGetDevice failed");
+        return AISX_ERR_HIP;
+    }
+    h->lmin = length_min;
+    h->lmax = length_max;
+    h->nchan = nchan;
+    h->max_bits = max_bits;
+    h->max_pdus = max_pdus;
+    // a call's good frames per channel: disjoint runs of >= 8 length_min data bits, each closed by a bit of its
+    // own, all but the first inside the call's bits; their payload comes from the open frame and the call's bits
+    const long long span = 8LL * (length_max + 1) + max_bits;
+    h->carry_words = (8 * (length_max + 1) + 63) / 64;
+    h->rec_cap = (int)(span / (8LL * length_min + 1) + 2);
+    h->byte_cap = (int)(span / 8 + 8);
+    h->out_bytes_cap = (long long)max_pdus * (length_max - 1); // (a payload is at most length_max - 1 octets)
+    if ((rc = dev_alloc(&h->d_st, (size_t)nchan)) != AISX_OK ||
+        (rc = dev_alloc(&h->d_carry, (size_t)nchan * h->carry_words)) != AISX_OK ||
+        (rc = dev_alloc(&h->d_srec, (size_t)nchan * h->rec_cap, false)) != AISX_OK ||
+        (rc = dev_alloc(&h->d_sbytes, (size_t)nchan * h->byte_cap, false)) != AISX_OK ||
+        (rc = dev_alloc(&h->d_cnt, 2 * (size_t)nchan)) != AISX_OK ||
+        (rc = dev_alloc(&h->d_base, 2 * (size_t)nchan)) != AISX_OK || (rc = dev_alloc(&h->d_count, 4)) != AISX_OK ||
+        (rc = dev_alloc(&h->d_out, (size_t)max_pdus)) != AISX_OK ||
+        (rc = dev_alloc(&h->d_out_bytes, (size_t)h->out_bytes_cap)) != AISX_OK) {
+        aisx_hdlc_batch_destroy(h);
+        return rc;
+    }
+    if (hipEventCreateWithFlags(&h->done, hipEventDisableTiming) != hipSuccess) {
+        set_err("aisx_hdlc_batch_create: hipEventCreateWithFlags failed");
+        aisx_hdlc_batch_destroy(h);
+        return AISX_ERR_HIP;
+    }
+    *out = h;
+    return AISX_OK;
+}
+
+extern "C" int aisx_hdlc_batch_reset(aisx_hdlc_batch* h)
+{
+    if (!h)
+        return AISX_ERR_INVALID;
+    OnDevice on(h->dev);
+    AISX_HIPCHK(on.err);
+    AISX_HIPCHK(hipEventSynchronize(h->done)); // (the last call's kernels; nothing else on the device)
+    AISX_HIPCHK(hipMemsetAsync(h->d_st, 0, sizeof(HdlcState) * h->nchan, nullptr));
+    AISX_HIPCHK(hipMemsetAsync(h->d_carry, 0, sizeof(unsigned long long) * h->nchan * h->carry_words, nullptr));
+    AISX_HIPCHK(hipMemsetAsync(h->d_cnt, 0, sizeof(int) * 2 * h->nchan, nullptr));
+    AISX_HIPCHK(hipMemsetAsync(h->d_count, 0, sizeof(int) * 4, nullptr));
+    AISX_HIPCHK(hipStreamSynchronize(nullptr)); // (done before the next call, whatever stream that is queued on)
+    return AISX_OK;
+}
+
+extern "C" int aisx_hdlc_batch_process(aisx_hdlc_batch* h, const uint8_t* d_bits, long bits_stride, const int* d_nbits,
+                                       void* stream)
+{
+    if (!h || !d_bits || !d_nbits || bits_stride < h->max_bits) {
+        set_err("aisx_hdlc_batch_process: bits, counts and a row stride of at least max_bits (%d) are needed",
+                h ? h->max_bits : 0);
+        return AISX_ERR_INVALID;
+    }
+    OnDevice on(h->dev);
+    AISX_HIPCHK(on.err);
+    const hipStream_t st = (hipStream_t)stream;
+    HdlcParams p;
+    p.bits = d_bits;
+    p.stride = bits_stride;
+    p.nbits = d_nbits;
+    p.max_bits = h->max_bits;
+    p.lmin = h->lmin;
+    p.lmax = h->lmax;
+    p.st = h->d_st;
+    p.carry = h->d_carry;
+    p.carry_words = h->carry_words;
+    p.srec = h->d_srec;
+    p.rec_cap = h->rec_cap;
+    p.sbytes = h->d_sbytes;
+    p.byte_cap = h->byte_cap;
+    p.cnt = h->d_cnt;
+    p.nbytes = h->d_cnt + h->nchan;
+    p.flags = h->d_count + 2;
+    hipLaunchKernelGGL(k_hdlc_deframe, dim3(h->nchan), dim3(HD_T), 0, st, p);
+    AISX_HIPCHK(hipGetLastError());
+    HdlcScanParams s;
+    s.cnt = p.cnt;
+    s.nbytes = p.nbytes;
+    s.rec_base = h->d_base;
+    s.byte_base = h->d_base + h->nchan;
+    s.nchan = h->nchan;
+    s.max_pdus = h->max_pdus;
+    s.count = h->d_count;
+    hipLaunchKernelGGL(k_hdlc_scan, dim3(1), dim3(HD_SCAN_T), 0, st, s);
+    AISX_HIPCHK(hipGetLastError());
+    HdlcGatherParams g;
+    g.srec = h->d_srec;
+    g.rec_cap = h->rec_cap;
+    g.sbytes = h->d_sbytes;
+    g.byte_cap = h->byte_cap;
+    g.cnt = p.cnt;
+    g.nbytes = p.nbytes;
+    g.rec_base = s.rec_base;
+    g.byte_base = s.byte_base;
+    g.max_pdus = h->max_pdus;
+    g.out = h->d_out;
+    g.out_bytes = h->d_out_bytes;
+    hipLaunchKernelGGL(k_hdlc_gather, dim3(h->nchan), dim3(HD_T), 0, st, g);
+    AISX_HIPCHK(hipGetLastError());
+    AISX_HIPCHK(hipEventRecord(h->done, st));
+    return AISX_OK;
+}
+
+extern "C" int aisx_hdlc_batch_results_device(const aisx_hdlc_batch* h, const aisx_pdu** d_pdus, const uint8_t** d_bytes,
+                                              const int** d_count)
+{
+    if (!h)
+        return AISX_ERR_INVALID;
+    if (d_pdus)
+        *d_pdus = (const aisx_pdu*)h->d_out;
+    if (d_bytes)
+        *d_bytes = h->d_out_bytes;
+    if (d_count)
+        *d_count = h->d_count;
+    return AISX_OK;
+}
+
+extern "C" int aisx_hdlc_batch_read(aisx_hdlc_batch* h, aisx_pdu* pdus, int pdu_cap, uint8_t* bytes, long bytes_cap,
+                                    int* npdus, void* stream)
+{
+    if (!h || !npdus || pdu_cap < 0 || bytes_cap < 0 || (pdu_cap > 0 && !pdus) || (bytes_cap > 0 && !bytes))
+        return AISX_ERR_INVALID;
+    OnDevice on(h->dev);
+    AISX_HIPCHK(on.err);
+    const hipStream_t st = (hipStream_t)stream;
+    int cnt[3] = { 0, 0, 0 };
+    AISX_HIPCHK(hipMemcpyAsync(cnt, h->d_count, sizeof cnt, hipMemcpyDeviceToHost, st));
+    AISX_HIPCHK(hipStreamSynchronize(st));
+    int k = cnt[1] < pdu_cap ? cnt[1] : pdu_cap;
+    if (k > 0)
+        AISX_HIPCHK(hipMemcpyAsync(pdus, h->d_out, sizeof(aisx_pdu) * k, hipMemcpyDeviceToHost, st));
+    AISX_HIPCHK(hipStreamSynchronize(st));
+    while (k > 0 && pdus[k - 1].offset + pdus[k - 1].len > bytes_cap) // (records are in byte order: a prefix again)
+        k--;
+    const long long nb = k > 0 ? pdus[k - 1].offset + pdus[k - 1].len : 0;
+    if (nb > 0)
+        AISX_HIPCHK(hipMemcpyAsync(bytes, h->d_out_bytes, (size_t)nb, hipMemcpyDeviceToHost, st));
+    if (cnt[2])
+        AISX_HIPCHK(hipMemsetAsync(h->d_count + 2, 0, sizeof(int), st));
+    AISX_HIPCHK(hipStreamSynchronize(st));
+    *npdus = cnt[0];
+    if (cnt[2]) {
+        set_err("aisx_hdlc_batch_read: a channel's bit count was outside [0, %d]: that channel was not advanced",
+                h->max_bits);
+        return AISX_ERR_INVALID;
+    }
+    if (k < cnt[0]) {
+        set_err("aisx_hdlc_batch_read: %d PDUs found, %d kept", cnt[0], k);
+        return AISX_ERR_OVERFLOW;
+    }
+    return AISX_OK;
+}

@@ -510,6 +510,40 @@ int aisx_hdlc_work(aisx_hdlc* h, const uint8_t* bits, int nbits, uint8_t* pdu_by
  * returns the string length. */
 int aisx_pdu_to_nmea(const char* designator, const uint8_t* pdu, int len, char* out, int cap);
 
+/* ------------------------------------------------------------------------ */
+/* batched HDLC deframer on the device: for every channel of a chain step,   */
+/* exactly what one aisx_hdlc handle per channel returns when fed that       */
+/* channel's bits in call order (the stream state carries across calls)      */
+/* ------------------------------------------------------------------------ */
+typedef struct aisx_pdu {
+    uint64_t end_bit; /* index, in this channel's bit stream counted from create / reset, of the bit that closed the frame */
+    int64_t offset;   /* first payload octet in the byte buffer */
+    int32_t chan;
+    int32_t len;      /* payload octets, FCS excluded */
+} aisx_pdu;
+typedef struct aisx_hdlc_batch aisx_hdlc_batch;
+/* 2 <= length_min <= length_max <= 1024 octets (as aisx_hdlc_create's, frame = payload + FCS); nchan channels of at
+ * most max_bits (<= 2^28) bits per call; max_pdus records (and max_pdus * (length_max - 1) payload bytes) per call.
+ * The handle belongs to the device that was current here. */
+int aisx_hdlc_batch_create(aisx_hdlc_batch** h, int length_min, int length_max, int nchan, int max_bits, int max_pdus);
+int aisx_hdlc_batch_destroy(aisx_hdlc_batch* h);
+int aisx_hdlc_batch_reset(aisx_hdlc_batch* h); /* back to the state after create; waits for the last process call's work */
+/* d_bits [nchan][bits_stride] one bit per byte (nonzero = 1), d_nbits [nchan] on the DEVICE (the chain's
+ * d_produced), bits_stride >= max_bits.  Queued on `stream`, no host synchronisation: the counts are read when the
+ * work runs.  The PDUs whose CRC checks replace the previous call's results, ordered by channel, then end_bit.  A
+ * channel whose count is outside [0, max_bits] is not advanced and the next aisx_hdlc_batch_read says so. */
+int aisx_hdlc_batch_process(aisx_hdlc_batch* h, const uint8_t* d_bits, long bits_stride, const int* d_nbits, void* stream);
+/* the last call's results in device memory: d_pdus [max_pdus] (offsets into d_bytes), d_count[0] = PDUs found,
+ * d_count[1] = records kept = min(found, max_pdus) (a prefix of the ordered list), d_count[2] != 0 after a bad count */
+int aisx_hdlc_batch_results_device(const aisx_hdlc_batch* h, const aisx_pdu** d_pdus, const uint8_t** d_bytes,
+                                   const int** d_count);
+/* copies the last call's results to the host (synchronises `stream`): *npdus = PDUs found; the records written are
+ * the first min(*npdus, max_pdus, pdu_cap) of them (fewer only where their bytes would pass bytes_cap), their bytes
+ * at the same offsets.  AISX_ERR_OVERFLOW when not all were written, AISX_ERR_INVALID when a call since the
+ * previous read met a bad count (the flag is then cleared). */
+int aisx_hdlc_batch_read(aisx_hdlc_batch* h, aisx_pdu* pdus, int pdu_cap, uint8_t* bytes, long bytes_cap, int* npdus,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
