@@ -101,14 +101,20 @@ class corr_est_cc:
         check(_lib.lib().aisx_corr_reset(self._h), "reset")
 
     # -- batched device path ---------------------------------------------
-    def work(self, x, want_corr=False, out=None, stream=None):
+    def work(self, x, want_corr=False, out=None, stream=None, corr=None):
         """One work() call on x[nchan][n] new items (device tensor).  Returns
-        (out, corr|None); the tags of the call are read with tags()."""
+        (out, corr|None); the tags of the call are read with tags().  out / corr: [nchan][n]
+        device views to write into (rows may be strided); a given corr implies want_corr."""
         x = _dev_c64(x, self.nchan)
         n = x.shape[1]
         if out is None:
             out = torch.empty_like(x)
-        corr = torch.empty_like(x) if want_corr else None
+        if corr is not None:
+            want_corr = True
+            if corr.dtype != torch.complex64 or tuple(corr.shape) != tuple(x.shape) or corr.stride(1) != 1:
+                raise ValueError("corr must be a complex64 [nchan][n] view with unit item stride")
+        elif want_corr:
+            corr = torch.empty_like(x)
         check(_lib.lib().aisx_corr_process(self._h, x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0),
                                            corr.data_ptr() if want_corr else None, corr.stride(0) if want_corr else 0,
                                            n, _stream_ptr(stream)), "corr_est_cc.work")

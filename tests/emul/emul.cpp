@@ -413,6 +413,11 @@ void* emu_corr_create(const cf* symbols, int nsym, float sps, unsigned mark_dela
     return h;
 }
 void emu_corr_destroy(void* hv) { delete (EmuCorr*)hv; }
+// the main kernel's grid (aisx_plan.h: corr_grid) as the product computes it
+void emu_corr_grid(int nchan, int n, int L, int F, int wg_per_cu, int* nseg, int* tps)
+{
+    corr_grid(nchan, n, L, F, nseg, tps, wg_per_cu);
+}
 float emu_corr_threshold(void* hv) { return ((EmuCorr*)hv)->cs.thresh; }
 int emu_corr_output_multiple(void* hv) { return ((EmuCorr*)hv)->cs.out_multiple; }
 void emu_corr_symbols(void* hv, cf* out) { EmuCorr* h = (EmuCorr*)hv; memcpy(out, h->cs.symbols.data(), sizeof(cf) * h->N); }
@@ -422,7 +427,8 @@ int emu_corr_process(void* hv, const cf* in, long in_stride, cf* out, long out_s
 {
     EmuCorr* h = (EmuCorr*)hv;
     int nseg, tps;
-    corr_grid(h->nchan, n, h->L, h->F, &nseg, &tps, (h->F == CF4_F && g_corr_dma) ? 2 : 0);
+    // (the product's resident workgroups per CU for the DMA builds, aisx_corr_process: 2 at F = 4096, 4 at F = 2048)
+    corr_grid(h->nchan, n, h->L, h->F, &nseg, &tps, g_corr_dma ? (h->F == CF4_F ? 2 : 4) : 0);
     if (force_nseg > 0) {
         const int ntiles = (n + h->L - 1) / h->L;
         tps = (ntiles + force_nseg - 1) / force_nseg;

@@ -34,6 +34,7 @@ def lib():
         L.emu_corr_output_multiple.restype = i32
         L.emu_corr_output_multiple.argtypes = [vp]
         L.emu_corr_symbols.argtypes = [vp, vp]
+        L.emu_corr_grid.argtypes = [i32, i32, i32, i32, i32, vp, vp]
         L.emu_corr_process.restype = i32
         L.emu_corr_process.argtypes = [vp, vp, lng, vp, lng, vp, lng, i32, vp, i32, vp, i32]
         L.emu_msk_create.restype = vp
@@ -104,6 +105,13 @@ class CorrEst:
         cnt = np.zeros(self.nchan, dtype=np.int32)
         lib().emu_corr_process(self.h, _p(x), n, _p(out), n, _p(corr), n, n, _p(tags), tag_cap, _p(cnt), force_nseg)
         return out, corr, [tags[c, : min(cnt[c], tag_cap)].copy() for c in range(self.nchan)], cnt, tags
+
+
+def corr_grid(nchan, n, L, F, wg_per_cu):
+    """(nseg, tiles_per_seg) of the correlator's main-kernel grid (aisx_plan.h: corr_grid)"""
+    a, b = C.c_int(0), C.c_int(0)
+    lib().emu_corr_grid(nchan, n, L, F, wg_per_cu, C.byref(a), C.byref(b))
+    return a.value, b.value
 
 
 class MskStream:

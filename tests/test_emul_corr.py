@@ -2,9 +2,12 @@
 model and compared with the oracle.  Exercises the index arithmetic of the
 2048-point register/LDS FFT, overlap-save tiling, history carry, threshold
 bitmask and the tag resolver without a GPU."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
+import corr_cases
 import emul_py as emu
 import oracle_py as orc
 from parity import assert_tags_match, planted, unit_template
@@ -225,3 +228,90 @@ def test_emul_corr_resolver_flood_falls_back_to_one_wave(monkeypatch):
         _, _, ot = o.work(x[c], want_corr=False)
         assert_tags_match(tags[c], ot)
     assert len(tags[0]) > 4 * 100 and 4 <= len(tags[1])
+
+
+# ---- the build matrix of tests/test_gpu_corr_builds.py: its grid, and its call sequence under the lane model ----
+
+def _lane_model_grid(nchan, n, N):
+    F = corr_cases.fft_size(N)
+    return emu.corr_grid(nchan, n, F - N, F, corr_cases.WG_PER_CU[F])
+
+
+@pytest.mark.parametrize("N", corr_cases.ALL_LENGTHS)
+def test_corr_matrix_grid_pin(N):
+    # What the device matrix claims to cover, from the product's grid arithmetic (aisx_plan.h: corr_grid) at the
+    # product's resident workgroups per CU (4 at F = 2048, 2 at F = 4096).  At 1 and 3 channels the long first
+    # call (12 L + 517 items, 13 tiles) is two segments of 7 and 6 tiles, the second one ending in the ragged
+    # tile; every later call of the sequence is one segment.  If the plan changes, this fails rather than the
+    # device matrix quietly losing its multi-segment calls.
+    F = corr_cases.fft_size(N)
+    L = F - N
+    for nchan in (1, 3):
+        assert _lane_model_grid(nchan, corr_cases.long_call(N), N) == (2, corr_cases.LONG_TPS)
+        for n in corr_cases.call_lengths(N)[1:]:
+            assert _lane_model_grid(nchan, n, N)[0] == 1
+    assert corr_cases.long_call(N) % L == 517 and 517 < L
+
+
+@pytest.mark.parametrize("N,nchan", corr_cases.MANY)
+def test_corr_matrix_grid_pin_many_channels(N, nchan):
+    # the many-channel cases: more workgroups than one round of resident slots (256 CUs x wg_per_cu), with
+    # several segments per channel on the long call -- 517 channels at N = 2047: 2 x 517 = 1034 workgroups over
+    # 512 slots; 1100 channels at N = 129: 2 x 1100 = 2200 over 1024
+    F = corr_cases.fft_size(N)
+    slots = 256 * corr_cases.WG_PER_CU[F]
+    assert nchan > slots
+    nseg, tps = _lane_model_grid(nchan, corr_cases.long_call(N), N)
+    assert (nseg, tps) == (2, corr_cases.LONG_TPS)
+    assert nseg * nchan > 2 * slots
+    for n in corr_cases.many_call_lengths(N)[1:]:
+        assert _lane_model_grid(nchan, n, N)[0] == 1
+
+
+# float64 gate floor of the lane-model run (tests/test_gpu_corr_builds.py sets the device's)
+FLOOR = 2e-6
+
+
+def _strided(nchan, n, fill):
+    # rows at an odd item offset (not 16-byte aligned), row stride n + 3
+    buf = np.full(1 + nchan * (n + 3), fill, np.complex64)
+    return buf[1:].reshape(nchan, n + 3)[:, :n]
+
+
+# F = 4096 lengths under k_corr4f.h (mode 5: folded where the lane model has the fold, else run-time)
+@pytest.mark.parametrize("N", [1, 99, 129, 140, 512, 513, 1139, 2048])
+def test_emul_corr_matrix_sequence(N):
+    # the device matrix's call sequence (tests/corr_cases.py) on one handle of three channels: a long two-segment
+    # call, calls of 1, N - 1, N, N + 1, N // 2 + 1, 2 L and 3 L + 1 items, a ragged last one; dense and sparse
+    # alternate; every call in strided, unaligned rows; dense output also against a float64 correlation
+    # (measured under the lane model: at most 1.15e-6 of the slice's maximum, at N = 2048 on a call whose
+    # slice holds no planted peak, below 4.9e-7 at the other lengths; the oracle's float32 FFT on the same
+    # samples up to 7.8e-7; the model up to 3.6 x the oracle)
+    F = corr_cases.fft_size(N)
+    emu.lib().emu_corr_set_dma(1 if F == 2048 else 5)
+    try:
+        rng = np.random.default_rng(4242 + N)
+        lens = corr_cases.call_lengths(N)
+        nchan = 3
+        tmpl, x = corr_cases.make_stream(rng, N, lens, nchan)
+        chk = corr_cases.Checker(tmpl, x)
+        e = emu.CorrEst(tmpl, 4.0, 1, 0.9, nchan=nchan)
+        k = 0
+        for i, n in enumerate(lens):
+            dense = i % 2 == 0
+            xin = _strided(nchan, n, 9e9)
+            xin[:] = x[:, k:k + n]
+            out = _strided(nchan, n, -7e9)
+            corr = _strided(nchan, n, -5e9) if dense else None
+            cap = 256
+            tags = np.zeros((nchan, cap), dtype=emu.TAG_DTYPE)
+            cnt = np.zeros(nchan, dtype=np.int32)
+            pc = C.c_void_p(corr.ctypes.data) if dense else None
+            emu.lib().emu_corr_process(e.h, C.c_void_p(xin.ctypes.data), n + 3, C.c_void_p(out.ctypes.data), n + 3,
+                                       pc, n + 3, n, emu._p(tags), cap, emu._p(cnt), 0)
+            assert np.all(cnt <= cap)
+            chk.check(out, corr, lambda r: tags[r, :cnt[r]], n, FLOOR)
+            k += n
+        assert chk.ndet >= 10
+    finally:
+        emu.lib().emu_corr_set_dma(1)
