@@ -33,7 +33,7 @@ def __getattr__(name):
         from . import blocks
 
         return getattr(blocks, name)
-    if name in ("hdlc_deframer_batch", "PDU_DTYPE"):
+    if name in ("hdlc_deframer_batch", "pdu_to_nmea_batch", "PDU_DTYPE"):
         from . import batch_framing
 
         return getattr(batch_framing, name)

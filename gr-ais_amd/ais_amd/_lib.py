@@ -181,6 +181,11 @@ def lib(device=True):
     sig("aisx_hdlc_batch_process", i32, [vp, vp, lng, vp, vp])
     sig("aisx_hdlc_batch_results_device", i32, [vp, pvp, pvp, pvp])
     sig("aisx_hdlc_batch_read", i32, [vp, vp, i32, vp, lng, pi32, vp])
+    sig("aisx_nmea_batch_create", i32, [pvp, C.POINTER(C.c_char_p), i32, i32, i32, lng])
+    sig("aisx_nmea_batch_destroy", i32, [vp])
+    sig("aisx_nmea_batch_process", i32, [vp, vp, vp, vp, vp, vp])
+    sig("aisx_nmea_batch_results_device", i32, [vp, pvp, pvp, pvp])
+    sig("aisx_nmea_batch_read", i32, [vp, vp, i32, vp, lng, pi32, pi32, vp])
     _lib = L
     return L
 

@@ -1,6 +1,7 @@
-"""Batched HDLC deframer on the device (aisx_hdlc_batch_*): the receive chain's `hdlc_deframer_bp(11, 64)`
-(python/radio.py:64) for every channel of a chain step at once, behind `ais_demod.work_pipelined`.  Only the PDUs
-whose CRC checks come back to the host; `pdu_to_nmea` stays there (it runs once per packet)."""
+"""The receive chain's tail on the device, for every channel of a chain step at once, behind
+`ais_demod.work_pipelined`: the batched HDLC deframer (aisx_hdlc_batch_*, `hdlc_deframer_bp(11, 64)`,
+python/radio.py:64) and, queued behind it on the same stream, the batched `pdu_to_nmea` (aisx_nmea_batch_*,
+python/radio.py:73).  One copy per step brings back either the PDUs or a newline-terminated NMEA stream."""
 import ctypes as C
 
 import numpy as np
@@ -92,3 +93,104 @@ class hdlc_deframer_batch:
         if as_list:
             return [(int(r["chan"]), int(r["end_bit"]), bytes(data[r["offset"]:r["offset"] + r["len"]])) for r in recs]
         return recs, data
+
+
+def nmea_text_len(length, dlen):
+    """what pdu_to_nmea's msg_to_sentence returns for a payload of `length` octets and a designator of dlen bytes,
+    in characters (fragments of 56 payload characters, separated by '\n'); 0 for an empty payload"""
+    if length <= 0:
+        return 0
+    P = (8 * length + 5) // 6
+    F = (P + 55) // 56
+    return F * (18 + (2 if F >= 10 else 1) + dlen) + max(F - 9, 0) + P - 1
+
+
+class pdu_to_nmea_batch:
+    """`pdu_to_nmea(designator)` for every PDU of a device list at once: per record, byte for byte what
+    ais_amd.pdu_to_nmea(designator of its channel).msg_to_sentence(payload) returns, followed by one '\n'; the
+    records' texts one behind the other (by channel, then end bit, as the deframer orders them), so the text up to
+    the last record's end is a ready-to-write NMEA stream.  designators: one str for every channel, or a sequence
+    of nchan str (0..16 bytes each); at most max_pdus records per call of at most length_max - 1 payload octets;
+    text_cap bytes of text (0: the worst case, nothing can overflow).
+
+    Queued behind the deframer on the caller's stream `s`, the pipelined chain's PDUs become text on the device:
+
+        hd = ais_amd.hdlc_deframer_batch(11, 64, nchan, cap, max_pdus)
+        nm = ais_amd.pdu_to_nmea_batch(["A", "B"] * (nchan // 2), nchan, max_pdus, 64)
+        r = dem.work_pipelined(x_k, x_next)              # step k
+        recs, text = nm.sentences(stream=s)              # step k - 1's text, read while step k runs
+        dem.wait(r["step"], stream=s)
+        hd.work(r["bits"], r["produced"], stream=s)      # deframe step k on s
+        nm.work(hd, stream=s)                            # and armour its PDUs, still on s: nothing waits
+        sys.stdout.buffer.write(text)                    # (records: chan, end_bit, offset / len of each text)
+
+    The read of step k - 1 comes before step k's work is queued: both handles' results are replaced by it."""
+
+    def __init__(self, designators, nchan, max_pdus, length_max, text_cap=0):
+        nchan = int(nchan)
+        if isinstance(designators, (str, bytes)):
+            designators = [designators] * nchan
+        designators = [d.encode() if isinstance(d, str) else bytes(d) for d in designators]
+        if len(designators) != nchan:
+            raise ValueError("pdu_to_nmea_batch: %d designators for %d channels" % (len(designators), nchan))
+        arr = (C.c_char_p * nchan)(*designators)
+        h = C.c_void_p()
+        check(_lib.lib().aisx_nmea_batch_create(C.byref(h), arr, nchan, int(max_pdus), int(length_max), int(text_cap)),
+              "pdu_to_nmea_batch")
+        self._h = h
+        self.nchan, self.max_pdus, self.length_max = nchan, int(max_pdus), int(length_max)
+        self.designators = [d.decode("latin-1") for d in designators]
+        self.found = 0  # PDUs the last call's producer found (armoured or not)
+        worst = self.max_pdus * (nmea_text_len(self.length_max - 1, max(len(d) for d in designators)) + 1)
+        self.text_cap = worst if int(text_cap) == 0 or int(text_cap) > worst else int(text_cap)  # (the handle's)
+        self._recs = np.zeros(self.max_pdus, dtype=PDU_DTYPE)  # read-back buffers, reused by every call
+        self._text = np.zeros(self.text_cap, dtype=np.uint8)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            _lib.lib().aisx_nmea_batch_destroy(h)
+            self._h = None
+
+    def work(self, deframer, stream=None):
+        """Armours the PDUs of the deframer's last call (queued on `stream`, default the current one; nothing
+        waits): records count + 1, PDUs found count + 0, so the deframer's overflow shows in sentences()."""
+        p, b, n = deframer.results_device()
+        self.work_device(p, b, n + 4, n, stream)
+
+    def work_device(self, pdus_ptr, bytes_ptr, npdus_ptr, nfound_ptr=None, stream=None):
+        """Device addresses: records in the aisx_pdu layout, their payload bytes, ONE int = records to armour and
+        optionally ONE int = PDUs the producer found.  Queued on `stream`; the counts are read on the device."""
+        check(_lib.lib().aisx_nmea_batch_process(self._h, C.c_void_p(pdus_ptr), C.c_void_p(bytes_ptr),
+                                                 C.c_void_p(npdus_ptr), C.c_void_p(nfound_ptr) if nfound_ptr else None,
+                                                 _stream_ptr(stream)), "pdu_to_nmea_batch.work")
+
+    def results_device(self):
+        """device addresses of the last call's records (aisx_pdu [max_pdus]: offset / len of each text), text and
+        counts (int [3]: found, records written, bad-input flag)"""
+        p, t, n = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(_lib.lib().aisx_nmea_batch_results_device(self._h, C.byref(p), C.byref(t), C.byref(n)),
+              "pdu_to_nmea_batch.results_device")
+        return p.value, t.value, n.value
+
+    def sentences(self, stream=None, as_list=False, overflow_ok=False):
+        """The last call's text (synchronises `stream`): (records, text bytes) with records a PDU_DTYPE array
+        (chan, end_bit, offset / len of the text in text bytes), or with as_list=True a list of (chan, end_bit,
+        str).  When fewer records were armoured than PDUs found (the deframer's or this handle's overflow),
+        OverflowError -- or with overflow_ok=True the ones armoured (self.found tells how many there were).
+        ValueError when a call since the last read met a bad count, channel or length (those gave no text)."""
+        recs, text = self._recs, self._text
+        n, f = C.c_int(0), C.c_int(0)
+        rc = _lib.lib().aisx_nmea_batch_read(self._h, recs.ctypes.data_as(C.c_void_p), self.max_pdus,
+                                             text.ctypes.data_as(C.c_void_p), text.size, C.byref(n), C.byref(f),
+                                             _stream_ptr(stream))
+        self.found = f.value
+        if not (rc == _lib.AISX_ERR_OVERFLOW and overflow_ok):
+            check(rc, "pdu_to_nmea_batch.sentences")
+        recs = recs[: n.value].copy()
+        nt = int(recs["offset"][-1] + recs["len"][-1] + (recs["len"][-1] > 0)) if len(recs) else 0
+        text = text[:nt].tobytes()
+        if as_list:
+            return [(int(r["chan"]), int(r["end_bit"]), text[r["offset"]:r["offset"] + r["len"]].decode("latin-1"))
+                    for r in recs]
+        return recs, text

@@ -50,27 +50,6 @@ struct aisx_hdlc_batch {
     unsigned char* d_out_bytes = nullptr;
 };
 
-namespace {
-
-// the calls run on the device that was current when the handle was created, and leave the caller's current
-struct OnDevice {
-    int prev = -1;
-    hipError_t err = hipSuccess;
-    explicit OnDevice(int dev)
-    {
-        if ((err = hipGetDevice(&prev)) == hipSuccess && prev != dev)
-            err = hipSetDevice(dev);
-    }
-    ~OnDevice()
-    {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev)
-            (void)hipSetDevice(prev);
-    }
-};
-
-} // namespace
-
 extern "C" int aisx_hdlc_batch_destroy(aisx_hdlc_batch* h)
 {
     if (!h)

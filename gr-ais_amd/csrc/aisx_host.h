@@ -112,4 +112,21 @@ inline void dev_free(T*& p)
     p = nullptr;
 }
 
+// a handle's calls run on the device that was current when it was created, and leave the caller's current
+struct OnDevice {
+    int prev = -1;
+    hipError_t err = hipSuccess;
+    explicit OnDevice(int dev)
+    {
+        if ((err = hipGetDevice(&prev)) == hipSuccess && prev != dev)
+            err = hipSetDevice(dev);
+    }
+    ~OnDevice()
+    {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev)
+            (void)hipSetDevice(prev);
+    }
+};
+
 } // namespace aisx

@@ -544,6 +544,39 @@ int aisx_hdlc_batch_results_device(const aisx_hdlc_batch* h, const aisx_pdu** d_
 int aisx_hdlc_batch_read(aisx_hdlc_batch* h, aisx_pdu* pdus, int pdu_cap, uint8_t* bytes, long bytes_cap, int* npdus,
                          void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* batched NMEA armouring on the device: for every record of a device PDU    */
+/* list (aisx_hdlc_batch_results_device's), the text aisx_pdu_to_nmea        */
+/* writes for it, byte for byte, queued behind the deframer                  */
+/* ------------------------------------------------------------------------ */
+typedef struct aisx_nmea_batch aisx_nmea_batch;
+/* nchan designators (each 0..16 bytes, NUL-terminated; one per channel, as radio.py gives "A" / "B"), at most
+ * max_pdus records per call of at most length_max - 1 payload octets (2 <= length_max <= 1024, as the deframer's),
+ * text_cap bytes of text (0 = the worst case for these arguments, so nothing can overflow).  The handle belongs to
+ * the device that was current here. */
+int aisx_nmea_batch_create(aisx_nmea_batch** h, const char* const* designators, int nchan, int max_pdus, int length_max,
+                           long text_cap);
+int aisx_nmea_batch_destroy(aisx_nmea_batch* h);
+/* d_pdus / d_bytes as aisx_hdlc_batch_results_device gives them; d_npdus: ONE int on the device = records to armour
+ * (for the deframer: d_count + 1); d_nfound: optional (NULL) int on the device = PDUs the producer found
+ * (d_count + 0), only used to report a producer's overflow.  Queued on `stream`; no host sync.  Output record i
+ * belongs to input record i (chan and end_bit copied); its offset / len give its text in the text buffer, followed
+ * by one '\n' that len does not count.  A record with an empty payload gets no text and no newline; a record whose
+ * chan is outside [0, nchan) or whose len is above length_max - 1, and a count outside [0, max_pdus], give no text
+ * and make the next read say so.  Records whose text does not fit text_cap are not written (a prefix is). */
+int aisx_nmea_batch_process(aisx_nmea_batch* h, const aisx_pdu* d_pdus, const uint8_t* d_bytes, const int* d_npdus,
+                            const int* d_nfound, void* stream);
+/* the last call's results in device memory: d_recs [max_pdus], d_text, d_count[0] = PDUs found (the producer's count,
+ * else the record count), d_count[1] = records written, d_count[2] != 0 after bad input */
+int aisx_nmea_batch_results_device(const aisx_nmea_batch* h, const aisx_pdu** d_recs, const char** d_text,
+                                   const int** d_count);
+/* copies the last call's results to the host (synchronises `stream`): *nrecs = records copied, the first of those
+ * written that fit rec_cap and (text and newline) text_cap, their text at the same offsets; *nfound (may be NULL) as
+ * d_count[0].  AISX_ERR_OVERFLOW when fewer records were copied than *nfound, AISX_ERR_INVALID when a call since the
+ * previous read met bad input (the flag is then cleared). */
+int aisx_nmea_batch_read(aisx_nmea_batch* h, aisx_pdu* recs, int rec_cap, char* text, long text_cap, int* nrecs,
+                         int* nfound, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
