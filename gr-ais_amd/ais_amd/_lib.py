@@ -171,6 +171,15 @@ def lib(device=True):
     sig("aisx_pfb_create", i32, [pvp, i32, i32, vp, i32, i32, i32])
     sig("aisx_pfb_destroy", i32, [vp])
     sig("aisx_pfb_process", i32, [vp, vp, lng, i32, vp, lng, pi32, vp])
+    pf64 = C.POINTER(C.c_double)
+    sig("aisx_xlate_create", i32, [pvp, i32, vp, i32, vp, i32, f64, i32, i32])
+    sig("aisx_xlate_destroy", i32, [vp])
+    sig("aisx_xlate_reset", i32, [vp])
+    sig("aisx_xlate_geometry", i32, [vp, pi32, pi32, pi32, pi32, pi32])
+    sig("aisx_xlate_set_center_freq", i32, [vp, i32, i32, f64])
+    sig("aisx_xlate_center_freq", i32, [vp, i32, i32, pf64])
+    sig("aisx_xlate_output_count", i32, [vp, i32])
+    sig("aisx_xlate_process", i32, [vp, vp, lng, i32, vp, lng, pi32, vp])
     sig("aisx_hdlc_create", i32, [pvp, i32, i32])
     sig("aisx_hdlc_destroy", i32, [vp])
     sig("aisx_hdlc_work", i32, [vp, vp, i32, vp, i32, vp, i32, pi32])

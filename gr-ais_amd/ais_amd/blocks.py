@@ -695,3 +695,75 @@ class pfb_channelizer_ccf:
         check(_lib.lib().aisx_pfb_process(self._h, x.data_ptr(), x.stride(0), n, out.data_ptr(), out.stride(0),
                                           C.byref(got), _stream_ptr(stream)), "pfb_channelizer_ccf.work")
         return out[:, : got.value]
+
+
+class freq_xlating_fir_filter_ccf:
+    """filter.freq_xlating_fir_filter_ccf(decimation, taps, center_freq, sampling_freq) (python/radio.py:49-54) for
+    any decimation, real prototype and centre frequency, batched: `nstreams` input streams, and per stream one output
+    channel per centre frequency.  `center_freq`: a float, a sequence of per-channel frequencies shared by all
+    streams, or an (nstreams, nchan) array.  Output row s * nchan + c is stream s at centre c (the rows
+    ais_demod.work_pipelined takes).  Streaming: any call length, any split of the input gives the same bits."""
+
+    def __init__(self, decimation, taps, center_freq, sampling_freq, nstreams=1, max_items=1 << 20):
+        t = np.ascontiguousarray(taps, dtype=np.float32).ravel()
+        self.nstreams = int(nstreams)
+        f = np.asarray(center_freq, dtype=np.float64)
+        if f.ndim == 0:
+            f = f.reshape(1, 1)
+        if f.ndim == 1:
+            f = f.reshape(1, -1)
+        if f.ndim != 2 or f.shape[0] not in (1, self.nstreams) or f.shape[1] < 1:
+            raise ValueError("freq_xlating_fir_filter_ccf: center_freq must be a float, a sequence of per-channel "
+                             "frequencies or an (nstreams, nchan) array")
+        f = np.ascontiguousarray(np.broadcast_to(f, (self.nstreams, f.shape[1])))
+        self.decimation, self.nchan, self.sampling_freq = int(decimation), int(f.shape[1]), float(sampling_freq)
+        self.max_items = int(max_items)
+        h = C.c_void_p()
+        check(_lib.lib().aisx_xlate_create(C.byref(h), self.decimation, t.ctypes.data_as(C.c_void_p), t.size,
+                                           f.ctypes.data_as(C.c_void_p), self.nchan, self.sampling_freq, self.nstreams,
+                                           self.max_items), "freq_xlating_fir_filter_ccf")
+        self._h = h
+        self.ntaps = t.size
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            _lib.lib().aisx_xlate_destroy(h)
+            self._h = None
+
+    def output_count(self, n):
+        r = _lib.lib().aisx_xlate_output_count(self._h, int(n))
+        check(min(r, 0), "freq_xlating_fir_filter_ccf.output_count")
+        return r
+
+    def center_freq(self, stream=0, chan=0):
+        f = C.c_double(0.0)
+        check(_lib.lib().aisx_xlate_center_freq(self._h, stream, chan, C.byref(f)), "freq_xlating_fir_filter_ccf.center_freq")
+        return f.value
+
+    def set_center_freq(self, f, stream=None, chan=None):
+        """from the next call on (GNU Radio 3.8: the rotator goes on from its phase); stream / chan None = all"""
+        for s in range(self.nstreams) if stream is None else [stream]:
+            for c in range(self.nchan) if chan is None else [chan]:
+                check(_lib.lib().aisx_xlate_set_center_freq(self._h, s, c, float(f)),
+                      "freq_xlating_fir_filter_ccf.set_center_freq")
+
+    def reset(self):
+        check(_lib.lib().aisx_xlate_reset(self._h), "freq_xlating_fir_filter_ccf.reset")
+
+    def work(self, x, out=None, stream=None):
+        """x [nstreams][n] complex64 (a device tensor, any row stride); returns the [nstreams*nchan][nout] device
+        tensor, or a view of `out` ([nstreams*nchan][>= nout], any row stride) holding the outputs"""
+        x = _dev_c64(x, self.nstreams)
+        n = x.shape[1]
+        nout = self.output_count(n)
+        rows = self.nstreams * self.nchan
+        if out is None:
+            out = torch.empty((rows, max(nout, 1)), dtype=torch.complex64, device=x.device)
+        elif out.dtype != torch.complex64 or out.dim() != 2 or out.shape[0] != rows or out.shape[1] < nout or out.stride(1) != 1:
+            raise ValueError("freq_xlating_fir_filter_ccf.work: out must be complex64 [%d][>= %d] with unit column stride"
+                             % (rows, nout))
+        got = C.c_int(0)
+        check(_lib.lib().aisx_xlate_process(self._h, x.data_ptr(), x.stride(0), n, out.data_ptr(), out.stride(0),
+                                            C.byref(got), _stream_ptr(stream)), "freq_xlating_fir_filter_ccf.work")
+        return out[:, : got.value]

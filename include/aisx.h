@@ -492,6 +492,36 @@ int aisx_pfb_process(aisx_pfb* h, const aisx_cf32* d_in, long in_stride, int n, 
                      int* nframes, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* freq_xlating_fir_filter_ccf(decim, taps, center_freq, samp_rate) for any  */
+/* decimation, real prototype and centre frequency (python/radio.py:49-54),  */
+/* batched: nstreams input streams, nchan_per_stream output channels each    */
+/* ------------------------------------------------------------------------ */
+typedef struct aisx_xlate aisx_xlate;
+/* 1 <= decim <= 4096, 1 <= ntaps <= 131072, 1 <= nchan_per_stream <= 1024, 1 <= nstreams <= 65535,
+ * 1 <= max_items <= 2^30 inputs per call; center_freqs [nstreams][nchan_per_stream] in Hz, |f| <= samp_rate / 2.
+ * Output row s * nchan_per_stream + c is stream s filtered at centre c, as the float64 filter
+ *   y[k] = e^{-j w D k} sum_n h[n] e^{+j w n} x[kD - n],  w = 2 pi f_c / samp_rate,  x[m] = 0 for m < 0
+ * (GNU Radio 3.8's block; the first output uses input 0).  The handle belongs to the device current here. */
+int aisx_xlate_create(aisx_xlate** h, int decim, const float* taps, int ntaps, const double* center_freqs,
+                      int nchan_per_stream, double samp_rate, int nstreams, int max_items);
+int aisx_xlate_destroy(aisx_xlate* h);
+/* zero history, input index 0, rotators back to 1 (the centre frequencies stay); waits for the handle's own work */
+int aisx_xlate_reset(aisx_xlate* h);
+int aisx_xlate_geometry(const aisx_xlate* h, int* nstreams, int* nchan_per_stream, int* decim, int* ntaps, int* max_items);
+/* from the next call on; the output rotator goes on from its phase with the new increment (GNU Radio 3.8
+ * build_composite_fir): outputs after a retune at output k_r are the filter at the new frequency times
+ * e^{-j (w_old - w_new) D k_r} */
+int aisx_xlate_set_center_freq(aisx_xlate* h, int stream, int chan, double center_freq);
+int aisx_xlate_center_freq(const aisx_xlate* h, int stream, int chan, double* center_freq);
+/* outputs the next call with n inputs produces (the same for every row) */
+int aisx_xlate_output_count(const aisx_xlate* h, int n);
+/* d_in [nstreams][in_stride]: n new inputs per stream (1 <= n <= max_items); writes *nout outputs to columns
+ * 0 .. *nout - 1 of every row of d_out[..][out_stride].  Queued on `stream`; calls of one handle must be ordered.
+ * Any split of an input into calls gives the same outputs, bit for bit. */
+int aisx_xlate_process(aisx_xlate* h, const aisx_cf32* d_in, long in_stride, int n, aisx_cf32* d_out, long out_stride,
+                       int* nout, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* host-side tail of the receive chain (python/radio.py:64-73): per-packet,   */
 /* bytes-per-second work, plain CPU code, HOST pointers                      */
 /* ------------------------------------------------------------------------ */
