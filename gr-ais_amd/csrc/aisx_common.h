@@ -109,6 +109,37 @@ AISX_HD float branchless_clip(float x, float clip)
 
 AISX_HD int aisx_popc64(unsigned long long v) { return __builtin_popcountll(v); }
 
+// Interpolator tap row of a phase mu in [0, 1]: rintf(mu * 128) (mmse_fir_interpolator_cc::interpolate, 128 steps),
+// as a byte offset row * pitch + base.  mu * 128 is exact (a power of two), so fmaf(mu, 128, 1.5 * 2^23) rounds once,
+// to nearest even, to 1.5 * 2^23 + rintf(mu * 128) (ulp 1 there, and 1.5 * 2^23 is even: ties go the same way): its bits
+// are 0x4B400000 + row and their low 24 bits 0x400000 + row.  The caller biases the base by -0x400000 * pitch once
+// (mmse_row_base); the rest is one v_fma_f32 and one v_mad_u32_u24 (mod 2^32) instead of v_mul, v_rndne, v_cvt_i32 and
+// a 64-bit multiply-add.  mmse_row is the row itself (for tests).
+AISX_HD unsigned mmse_row_bits(float mu) { return __builtin_bit_cast(unsigned, fmaf(mu, 128.0f, 12582912.0f)); }
+AISX_HD unsigned mmse_row(float mu) { return mmse_row_bits(mu) - 0x4B400000u; }
+AISX_HD unsigned mmse_row_base(unsigned base, unsigned pitch) { return base - 0x400000u * pitch; }
+AISX_HD unsigned mmse_row_off(float mu, unsigned pitch, unsigned row_base)
+{
+    return (mmse_row_bits(mu) & 0xFFFFFFu) * pitch + row_base;
+}
+
+// Ring byte offset of the first sample an interpolation reads, for a lane at ring byte position sb (unmasked) that reads
+// adv (>= 0, < 2^24) items further on when it is the odd lane of a pair, step = the slot row bytes for that lane and 0
+// for the even lane: (sb + adv * step) & mask, equal to (odd ? sb + adv * slot : sb) & mask.  One v_mad_u32_u24 and
+// one v_and_b32, no select (the caller adds its lane's column to the base it reads from).  On the device the multiply-add
+// is written out: the compiler drops the 24-bit masks (only the bits under mask are demanded) and then picks a 64-bit
+// v_mad_u64_u32.
+AISX_HD unsigned ring_read_off(int sb, int adv, unsigned step, unsigned mask)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    unsigned r;
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(adv), "v"(step), "v"(sb));
+    return r & mask;
+#else
+    return ((unsigned)sb + ((unsigned)adv & 0xFFFFFFu) * (step & 0xFFFFFFu)) & mask;
+#endif
+}
+
 // gr::fast_atan2f (gnuradio-runtime fast_atan2f.cc); `tab` = 257-entry table.
 // Written with selects instead of the upstream if/else ladder (a divergent
 // ladder costs a wave every arm); every arithmetic operation and operand is the

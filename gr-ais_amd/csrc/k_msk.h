@@ -763,6 +763,25 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
             tv[k] = tp[7 - k];
         }
     };
+    // fir_load as the pair loops address it: the tap row of a phase mu in [0, 1] by mmse_row_off (aisx_common.h: two
+    // instructions instead of six), the samples at ring byte offset soff (masked) of this lane's column
+    const unsigned mm_rbase = mmse_row_base((unsigned)p.lds_tab_off, (unsigned)(MSK_TAPS_PITCH * 4));
+    const char* const lds_l = lds + l * 8;
+    constexpr unsigned RING_M = (unsigned)((MSK_RING - 1) * SLOT_B);
+    auto fir_load_pair = [&](float mu, unsigned soff, cf* sv, float* tv) {
+        typedef float tap4 __attribute__((vector_size(16)));
+        const tap4* tp4 = (const tap4*)(lds0 + mmse_row_off(mu, (unsigned)(MSK_TAPS_PITCH * 4), mm_rbase));
+        const tap4 tlo = tp4[0], thi = tp4[1];
+        const float tp[8] = { tlo[0], tlo[1], tlo[2], tlo[3], thi[0], thi[1], thi[2], thi[3] };
+        struct alignas(8) cf8 { float re, im; };
+        const cf8* sp = (const cf8*)(lds_l + soff);
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const cf8 t = sp[k * LPW];
+            sv[k] = mk(t.re, t.im);
+            tv[k] = tp[7 - k];
+        }
+    };
     auto fir_sum = [&](const cf* sv, const float* tv) -> cf {
         cf acc = mk(0.f, 0.f);
 #pragma unroll
@@ -981,6 +1000,7 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
                 }
                 if (ntrips > 0) {
                     const bool roleO = (cx.tid() & ROW) != 0;
+                    const unsigned rstep = (unsigned)(cx.tid() & ROW) * (unsigned)(SLOT_B / ROW); // roleO ? SLOT_B : 0
                     const unsigned pmask = roleO ? 0u : STG_MASK, pbase = roleO ? stg_spare : stg_real;
                     cf sqO = prev_sq, sqE = mk(0.f, 0.f), acc = last_interp;
                     float nl_prev = d_dly_diff_1.re;
@@ -1029,7 +1049,7 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
                         const bool skipO = winO && !nanO;
                         cf sv[8];
                         float tv[8];
-                        fir_load((unsigned)(int)rintf((roleO ? muO : d_mu) * 128.0f), roleO ? sb1 : sb, sv, tv);
+                        fir_load_pair(roleO ? muO : d_mu, ring_read_off(sb, adv1, rstep, RING_M), sv, tv);
                         acc = fir_sum(sv, tv);
                         const cf sq = cmul_exact(acc, acc);                            // :171
                         cf sE, s1;
@@ -1090,6 +1110,7 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
                 // computed by both lanes alike.  (With LPW <= 16 the other copies of a channel do the same once more.)
                 constexpr int ROW = LPW <= 16 ? 16 : 32; // lane i and lane i ^ ROW carry the same channel
                 const bool roleO = (cx.tid() & ROW) != 0;
+                const unsigned rstep = (unsigned)(cx.tid() & ROW) * (unsigned)(SLOT_B / ROW); // roleO ? SLOT_B : 0
                 // (the lanes running odd iterations stage theirs in the spare row: no exec masking)
                 const unsigned pmask = roleO ? 0u : STG_MASK, pbase = roleO ? stg_spare : stg_real;
                 cf sqO = prev_sq, sqE = mk(0.f, 0.f), acc = last_interp;
@@ -1101,10 +1122,11 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
 #endif
                     const float m1 = d_mu + d_omega;                               // :199-201, m1 > 0:
                     const float muO = cx.fract(m1);                                // m1 - floorf(m1)
-                    const int sb1 = sb + (int)m1 * SLOT_B;                         // (int)floorf(m1)
+                    const int adv1 = (int)m1;                                      // floorf(m1)
+                    const int sb1 = sb + adv1 * SLOT_B;
                     cf sv[8];
                     float tv[8];
-                    fir_load((unsigned)(int)rintf((roleO ? muO : d_mu) * 128.0f), roleO ? sb1 : sb, sv, tv);
+                    fir_load_pair(roleO ? muO : d_mu, ring_read_off(sb, adv1, rstep, RING_M), sv, tv);
                     acc = fir_sum(sv, tv);
                     const cf sq = cmul_exact(acc, acc);                            // :171
                     cf sE, s1;
@@ -1172,11 +1194,11 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
                     // loads go out together, the odd one's latency hides behind the even sum.
                     cf svE[8], svO[8];
                     float tvE[8], tvO[8];
-                    fir_load((unsigned)(int)rintf(d_mu * 128.0f), sb, svE, tvE);
+                    fir_load_pair(d_mu, (unsigned)sb & RING_M, svE, tvE);
                     const float m1 = d_mu + d_omega;                               // :199-201, m1 > 0:
                     const float muO = cx.fract(m1);                                // m1 - floorf(m1)
                     const int sb1 = sb + (int)m1 * SLOT_B;                            // (int)floorf(m1)
-                    fir_load((unsigned)(int)rintf(muO * 128.0f), sb1, svO, tvO);
+                    fir_load_pair(muO, (unsigned)sb1 & RING_M, svO, tvO);
                     const cf accE = fir_sum(svE, tvE);
                     const cf sE = cmul_exact(accE, accE);                          // :171
                     const float nlE = sE.re * sqO.re + sE.im * sqO.im;             // :173-174, real part
