@@ -30,7 +30,7 @@ def __getattr__(name):
     # helpers (modulate, framing) stay importable anywhere
     if name in ("corr_est_cc", "msk_timing_recovery_cc", "square_and_fft_sync_cc", "freqest", "feedforward_agc_cc",
                 "ais_demod", "TAG_DTYPE", "pfb_channelizer_ccf", "freq_xlating_fir_filter_ccf", "firdes_low_pass",
-                "freq_sync_agc"):
+                "freq_sync_agc", "ais_rx", "SAMPLE_FORMATS"):
         from . import blocks
 
         return getattr(blocks, name)

@@ -21,6 +21,9 @@ AISX_ERR_NO_DEVICE = -4
 AISX_ERR_OVERFLOW = -5
 AISX_ERR_RUNTIME = -6
 
+AISX_FMT_CF32, AISX_FMT_CS16, AISX_FMT_CS8, AISX_FMT_CU8 = 0, 1, 2, 3
+AISX_RX_ST_HDLC_OVERFLOW, AISX_RX_ST_NMEA_OVERFLOW, AISX_RX_ST_BAD_COUNT = 0x100, 0x200, 0x400
+
 KEY_CORR_START, KEY_PHASE_EST, KEY_TIME_EST, KEY_CORR_EST, KEY_PORT1 = 0, 1, 2, 3, 0x100
 KEY_NAMES = {0: "corr_start", 1: "phase_est", 2: "time_est", 3: "corr_est"}
 
@@ -180,6 +183,18 @@ def lib(device=True):
     sig("aisx_xlate_center_freq", i32, [vp, i32, i32, pf64])
     sig("aisx_xlate_output_count", i32, [vp, i32])
     sig("aisx_xlate_process", i32, [vp, vp, lng, i32, vp, lng, pi32, vp])
+    sig("aisx_xlate_process_fmt", i32, [vp, vp, i32, f32, f32, lng, i32, vp, lng, pi32, vp])
+    sig("aisx_msk_status_device", i32, [vp, pvp])
+    pll, plng = C.POINTER(C.c_longlong), C.POINTER(C.c_long)
+    sig("aisx_rx_create", i32, [pvp, f64, i32, i32, vp, C.POINTER(C.c_char_p), i32, f32, f32, i32, vp, i32, vp, i32, i32])
+    sig("aisx_rx_destroy", i32, [vp])
+    sig("aisx_rx_geometry", i32, [vp, pi32, pi32, pi32, pi32, pi32, plng])
+    sig("aisx_rx_acquire", i32, [vp, pvp, plng])
+    sig("aisx_rx_submit", i32, [vp, pll])
+    sig("aisx_rx_push", i32, [vp, vp, lng, pll])
+    sig("aisx_rx_flush", i32, [vp])
+    sig("aisx_rx_pop", i32, [vp, i32, pll, vp, lng, plng, vp, i32, pi32, pi32])
+    sig("aisx_rx_set_center_freq", i32, [vp, i32, i32, f64])
     sig("aisx_hdlc_create", i32, [pvp, i32, i32])
     sig("aisx_hdlc_destroy", i32, [vp])
     sig("aisx_hdlc_work", i32, [vp, vp, i32, vp, i32, vp, i32, pi32])

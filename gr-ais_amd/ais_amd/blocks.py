@@ -751,10 +751,23 @@ class freq_xlating_fir_filter_ccf:
     def reset(self):
         check(_lib.lib().aisx_xlate_reset(self._h), "freq_xlating_fir_filter_ccf.reset")
 
-    def work(self, x, out=None, stream=None):
+    def work(self, x, out=None, stream=None, fmt=None, scale=1.0, bias=0.0):
         """x [nstreams][n] complex64 (a device tensor, any row stride); returns the [nstreams*nchan][nout] device
-        tensor, or a view of `out` ([nstreams*nchan][>= nout], any row stride) holding the outputs"""
-        x = _dev_c64(x, self.nstreams)
+        tensor, or a view of `out` ([nstreams*nchan][>= nout], any row stride) holding the outputs.
+        fmt "cs16" / "cs8" / "cu8": x is a device tensor [nstreams][n][2] of int16 / int8 / uint8 (re, im), taken as
+        ((float)raw - bias) * scale where the filter stages its window (aisx_xlate_process_fmt): the same bits as
+        work() on the converted values"""
+        code = _fmt_code(fmt)
+        if code == _lib.AISX_FMT_CF32:
+            x = _dev_c64(x, self.nstreams)
+        else:
+            want = SAMPLE_FORMATS[code][2]
+            if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != want or x.dim() != 3 or x.shape[0] != self.nstreams \
+                    or x.shape[2] != 2:
+                raise TypeError("freq_xlating_fir_filter_ccf.work: fmt %s takes a device tensor [%d][n][2] of %s"
+                                % (SAMPLE_FORMATS[code][0], self.nstreams, want))
+            if x.stride(2) != 1 or x.stride(1) != 2 or x.stride(0) % 2:
+                x = x.contiguous()
         n = x.shape[1]
         nout = self.output_count(n)
         rows = self.nstreams * self.nchan
@@ -764,6 +777,159 @@ class freq_xlating_fir_filter_ccf:
             raise ValueError("freq_xlating_fir_filter_ccf.work: out must be complex64 [%d][>= %d] with unit column stride"
                              % (rows, nout))
         got = C.c_int(0)
-        check(_lib.lib().aisx_xlate_process(self._h, x.data_ptr(), x.stride(0), n, out.data_ptr(), out.stride(0),
-                                            C.byref(got), _stream_ptr(stream)), "freq_xlating_fir_filter_ccf.work")
+        if code == _lib.AISX_FMT_CF32:
+            check(_lib.lib().aisx_xlate_process(self._h, x.data_ptr(), x.stride(0), n, out.data_ptr(), out.stride(0),
+                                                C.byref(got), _stream_ptr(stream)), "freq_xlating_fir_filter_ccf.work")
+        else:
+            check(_lib.lib().aisx_xlate_process_fmt(self._h, x.data_ptr(), code, float(scale), float(bias), x.stride(0) // 2, n,
+                                                    out.data_ptr(), out.stride(0), C.byref(got), _stream_ptr(stream)),
+                  "freq_xlating_fir_filter_ccf.work")
         return out[:, : got.value]
+
+
+# AISX_FMT_* -> (name, numpy dtype of re / im, torch dtype)
+SAMPLE_FORMATS = {
+    _lib.AISX_FMT_CF32: ("cf32", np.float32, torch.float32),
+    _lib.AISX_FMT_CS16: ("cs16", np.int16, torch.int16),
+    _lib.AISX_FMT_CS8: ("cs8", np.int8, torch.int8),
+    _lib.AISX_FMT_CU8: ("cu8", np.uint8, torch.uint8),
+}
+
+
+def _fmt_code(fmt):
+    if fmt is None:
+        return _lib.AISX_FMT_CF32
+    for code, (name, _, _) in SAMPLE_FORMATS.items():
+        if fmt == name or fmt == code:
+            return code
+    raise ValueError("unknown sample format %r: one of %s" % (fmt, [v[0] for v in SAMPLE_FORMATS.values()]))
+
+
+class ais_rx:
+    """ais_rx(freq, rate, designator) (python/radio.py:40-73): freq_xlating_fir_filter_ccf -> ais_demod ->
+    hdlc_deframer_bp -> pdu_to_nmea, as one handle (aisx_rx_*) for `nstreams` sources at `rate`, fed from host memory
+    in the source's own sample format.  `freq` / `designator`: a scalar, or one per centre of every stream
+    (radio.py:88-89: (-25e3, 25e3) and ("A", "B")); `freq` may also be an (nstreams, ncentres) array.  Decimation
+    int(rate / 48000), taps low_pass(1, rate, 11e3, 1e3), samples_per_symbol rate / decimation / 9600, gain 0.04, limit
+    0.01, fftlen 1024, deframer (11, 64), as the reference sets them.
+
+    fmt "cf32" (complex64 blocks) or "cs16" / "cs8" / "cu8" (blocks [nstreams][block_items][2] of int16 / int8 /
+    uint8, value ((float)raw - bias) * scale).  Every block is block_items items per stream, a multiple of the
+    decimation.  Output row s * ncentres + c (a record's chan) is stream s at centre c.
+
+        rx = ais_amd.ais_rx((-25e3, 25e3), 250e3, ("A", "B"), nstreams=8, fmt="cu8", scale=1 / 128, bias=127.5)
+        while True:
+            source.read_into(rx.slot())          # the pinned slot: the copy to the device reads it in place
+            rx.submit()                          # returns at once; block k is issued when block k + 1 arrives
+            while (r := rx.pop()) is not None:   # (block, records, text) of every block that has finished
+                sys.stdout.buffer.write(r[2])
+    """
+
+    def __init__(self, freq, rate, designator, nstreams=1, fmt="cf32", scale=1.0, bias=0.0, block_items=None,
+                 preamble_symbols=None, taps=None, max_pdus_per_block=1 << 16):
+        from .batch_framing import PDU_DTYPE
+        from .modulate import gmsk_mod, modulate_vector_bc
+
+        self.nstreams, self.rate = int(nstreams), float(rate)
+        f = np.asarray(freq, dtype=np.float64)
+        if f.ndim == 0:
+            f = f.reshape(1, 1)
+        if f.ndim == 1:
+            f = f.reshape(1, -1)
+        if f.ndim != 2 or f.shape[0] not in (1, self.nstreams) or f.shape[1] < 1:
+            raise ValueError("ais_rx: freq must be a float, a sequence of per-centre frequencies or an (nstreams, "
+                             "ncentres) array")
+        f = np.ascontiguousarray(np.broadcast_to(f, (max(self.nstreams, 1), f.shape[1])))
+        self.ncentres = int(f.shape[1])
+        des = [designator] if isinstance(designator, (str, bytes)) else list(designator)
+        des = [d.encode() if isinstance(d, str) else bytes(d) for d in des]
+        if len(des) != self.ncentres:
+            raise ValueError("ais_rx: %d designators for %d centres" % (len(des), self.ncentres))
+        self.fmt = _fmt_code(fmt)
+        self._item = np.dtype(np.complex64) if self.fmt == _lib.AISX_FMT_CF32 else np.dtype(SAMPLE_FORMATS[self.fmt][1])
+        self.decimation = int(self.rate / 48000) if np.isfinite(self.rate) else 0
+        if block_items is None:
+            block_items = 65536 * max(self.decimation, 1)
+        self.block_items = int(block_items)
+        if taps is None and self.decimation >= 1:
+            taps = firdes_low_pass(1.0, self.rate, 11e3, 1e3)
+        t = np.ascontiguousarray(taps, dtype=np.float32).ravel() if taps is not None else None
+        if preamble_symbols is None and self.decimation >= 1:
+            sps = self.rate / self.decimation / 9600.0
+            preamble_symbols = modulate_vector_bc(gmsk_mod(int(sps), 0.4).to_basic_block(), [1, 1, 0, 0] * 7, [1])
+        sym = np.ascontiguousarray(preamble_symbols, dtype=np.complex64) if preamble_symbols is not None else np.zeros(1, np.complex64)
+        _warn_if_few_hw_queues()
+        h = C.c_void_p()
+        check(_lib.lib().aisx_rx_create(C.byref(h), self.rate, self.nstreams, self.ncentres, f.ctypes.data_as(C.c_void_p),
+                                        (C.c_char_p * len(des))(*des), self.fmt, float(scale), float(bias), self.block_items,
+                                        t.ctypes.data_as(C.c_void_p) if t is not None else None, t.size if t is not None else 0,
+                                        sym.ctypes.data_as(C.c_void_p), sym.size, int(max_pdus_per_block)), "ais_rx")
+        self._h = h
+        d, T, nch, nin, nres, tc = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_long()
+        check(_lib.lib().aisx_rx_geometry(h, C.byref(d), C.byref(T), C.byref(nch), C.byref(nin), C.byref(nres), C.byref(tc)),
+              "ais_rx")
+        self.items_per_block, self.nchan, self.input_slots, self.result_slots = T.value, nch.value, nin.value, nres.value
+        self._recs = np.zeros(int(max_pdus_per_block), dtype=PDU_DTYPE)
+        self._text = np.zeros(max(tc.value, 1), dtype=np.uint8)
+        self.status = 0  # of the block popped last (AISX_MSK_ST_* | AISX_RX_ST_*)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            _lib.lib().aisx_rx_destroy(h)
+            self._h = None
+
+    def _shape(self):
+        return (self.nstreams, self.block_items) if self.fmt == _lib.AISX_FMT_CF32 else (self.nstreams, self.block_items, 2)
+
+    def slot(self):
+        """the pinned host slot of the next block as a numpy view ([nstreams][block_items] complex64, or
+        [nstreams][block_items][2] of the format's integer type): fill it, then submit().  Blocks only while every slot
+        is still being copied from."""
+        p, stride = C.c_void_p(), C.c_long()
+        check(_lib.lib().aisx_rx_acquire(self._h, C.byref(p), C.byref(stride)), "ais_rx.slot")
+        shape = self._shape()
+        nbytes = int(np.prod(shape)) * self._item.itemsize
+        buf = (C.c_char * nbytes).from_address(p.value)
+        return np.frombuffer(buf, dtype=self._item).reshape(shape)
+
+    def submit(self):
+        """queues the slot filled last; returns the block's number.  OverflowError when every result slot waits to be
+        popped (nothing was queued: pop(), then submit() again)."""
+        b = C.c_longlong(-1)
+        check(_lib.lib().aisx_rx_submit(self._h, C.byref(b)), "ais_rx.submit")
+        return b.value
+
+    def push(self, iq):
+        """slot() + copy + submit() for a host array of the format's dtype, [nstreams][block_items] complex64 or
+        [nstreams][block_items][2] integers"""
+        a = np.asarray(iq)
+        if a.dtype != self._item or a.shape != self._shape():
+            raise TypeError("ais_rx.push: a block is %s of %s, got %s of %s" % (self._shape(), self._item, a.shape, a.dtype))
+        a = np.ascontiguousarray(a)
+        b = C.c_longlong(-1)
+        check(_lib.lib().aisx_rx_push(self._h, a.ctypes.data_as(C.c_void_p), self.block_items, C.byref(b)), "ais_rx.push")
+        return b.value
+
+    def flush(self):
+        """issues the block that waits for its successor (same results, no look-ahead for it)"""
+        check(_lib.lib().aisx_rx_flush(self._h), "ais_rx.flush")
+
+    def pop(self, wait=False):
+        """(block, records, text) of the oldest finished block not yet popped -- records a PDU_DTYPE array (chan,
+        end_bit, offset / len of each sentence in text), text the NMEA bytes, '\n' after every sentence -- or None when
+        none has finished (wait=True: blocks until the next issued block has; None when none is issued)"""
+        b, tl, nr, st = C.c_longlong(-1), C.c_long(0), C.c_int(0), C.c_int(0)
+        check(_lib.lib().aisx_rx_pop(self._h, 1 if wait else 0, C.byref(b), self._text.ctypes.data_as(C.c_void_p), self._text.size,
+                                     C.byref(tl), self._recs.ctypes.data_as(C.c_void_p), self._recs.size, C.byref(nr),
+                                     C.byref(st)), "ais_rx.pop")
+        if b.value < 0:
+            return None
+        self.status = st.value
+        return b.value, self._recs[: nr.value].copy(), self._text[: tl.value].tobytes()
+
+    def set_center_freq(self, f, stream=None, chan=None):
+        """from the next submitted block on; stream / chan None = all"""
+        for s in range(self.nstreams) if stream is None else [stream]:
+            for c in range(self.ncentres) if chan is None else [chan]:
+                check(_lib.lib().aisx_rx_set_center_freq(self._h, s, c, float(f)), "ais_rx.set_center_freq")

@@ -1264,6 +1264,14 @@ extern "C" int aisx_msk_last_status(aisx_msk* h, int* status, void* stream)
     return AISX_OK;
 }
 
+extern "C" int aisx_msk_status_device(const aisx_msk* h, const int** d_status)
+{
+    if (!h || !d_status)
+        return AISX_ERR_INVALID;
+    *d_status = h->d_status;
+    return AISX_OK;
+}
+
 // GNU Radio path: the call's control words set, and its three result words gathered behind the symbols' header,
 // by one-thread kernels -- a blocking hipMemcpy of four bytes costs as much as a launch, and a call had eight of them
 __global__ void k_msk_host_setup(int* tagn, int ntags, unsigned long long* nread, unsigned long long R, int* carry_len, int* ctag_n)

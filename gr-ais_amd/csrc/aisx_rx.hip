@@ -1,0 +1,558 @@
+// aisx_rx.hip -- C ABI of the host-fed receiver (include/aisx.h, aisx_rx_*): python/radio.py's ais_rx as one handle
+// for nstreams sources, fed from pinned host memory in the source's own sample format.  Nothing here computes: the
+// handle owns the filter (aisx_xlate), the four stage handles and their chain, the deframer and the NMEA stage, and
+// the rings, streams and events that order them (INTEGRATION.md states the rules; this file is their one home).
+//
+//   block b, submitted:   copy stream    pinned slot b % NPIN -> raw buffer b % NRAW      (after filter b - NRAW)
+//                         filter stream  raw buffer -> row buffer b % NROW                (after wait_input(b - NROW))
+//                         chain          step b - 1 with d_in_next = row buffer b % NROW  (after tail b - 1 - DEPTH)
+//                         tail stream    wait(step b - 1), deframer, NMEA, status, results -> pinned result slot
+//
+// so the copy of block b + 1 runs beside the compute of block b, and the host never waits for the device in submit.
+#include <string.h>
+
+#include <vector>
+
+#include "aisx_devctx.h"
+#include "aisx_host.h"
+#include "k_nmea.h"
+#include "k_xlate.h"
+
+using namespace aisx;
+
+namespace {
+
+constexpr int RX_NPIN = 3;                     // pinned host input slots
+constexpr int RX_NRAW = 2;                     // raw-input buffers on the device
+constexpr int RX_NROW = AISX_CHAIN_DEPTH + 1;  // row buffers (the filter's outputs, the chain's inputs)
+constexpr int RX_NOUT = AISX_CHAIN_DEPTH;      // sets of bits / produced (aisx_chain_step: one per step in flight)
+constexpr int RX_NRES = 8;                     // pinned result slots
+constexpr int RX_FFTLEN = 1024, RX_LMIN = 11, RX_LMAX = 64;
+constexpr int RX_META = 8;                     // ints: msk status, deframer count[3], NMEA count[3], spare
+
+// filter.firdes.low_pass(gain 1, fs, cutoff, transition) with the Hamming window (radio.py:51)
+std::vector<float> low_pass(double fs, double cutoff, double transition)
+{
+    int ntaps = (int)(53.0 * fs / (22.0 * transition));
+    if ((ntaps & 1) == 0)
+        ntaps++;
+    const int m = (ntaps - 1) / 2;
+    const double pi = 3.14159265358979323846, fwt0 = 2 * pi * cutoff / fs;
+    std::vector<float> t((size_t)ntaps);
+    for (int i = 0; i < ntaps; i++) {
+        const int n = i - m;
+        const double w = 0.54 - 0.46 * cos(2 * pi * i / (ntaps - 1));
+        t[i] = (float)((n == 0 ? fwt0 / pi : sin(n * fwt0) / (n * pi)) * w);
+    }
+    double fmax = t[m];
+    for (int i = m + 1; i < ntaps; i++)
+        fmax += 2 * (double)t[i];
+    for (float& v : t)
+        v = (float)((double)v * (1.0 / fmax));
+    return t;
+}
+
+} // namespace
+
+// one workgroup: the recovery's status words or-ed over the channels, and the deframer's and the NMEA stage's counts,
+// gathered into one record for the copy back
+__global__ __launch_bounds__(256) void k_rx_meta(const int* __restrict__ msk_status, int nchan, const int* __restrict__ hd_count,
+                                                 const int* __restrict__ nm_count, int* __restrict__ meta)
+{
+    __shared__ int acc;
+    if (threadIdx.x == 0)
+        acc = 0;
+    __syncthreads();
+    int v = 0;
+    for (int c = threadIdx.x; c < nchan; c += blockDim.x)
+        v |= msk_status[c];
+    if (v)
+        atomicOr(&acc, v);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        meta[0] = acc;
+        for (int i = 0; i < 3; i++) {
+            meta[1 + i] = hd_count[i];
+            meta[4 + i] = nm_count[i];
+        }
+        meta[7] = 0;
+    }
+}
+
+struct aisx_rx {
+    int dev = 0;
+    int fmt = 0, item_bytes = 0, ns = 0, nch = 0, D = 0, T = 0, block_items = 0, max_pdus = 0, cap = 0;
+    float scale = 1.f, bias = 0.f;
+    long long text_cap = 0;
+    size_t raw_bytes = 0, res_bytes = 0;
+    aisx_xlate* xl = nullptr;
+    aisx_freqsync* fs = nullptr;
+    aisx_agc* agc = nullptr;
+    aisx_corr* corr = nullptr;
+    aisx_msk* msk = nullptr;
+    aisx_chain* chain = nullptr;
+    aisx_hdlc_batch* hd = nullptr;
+    aisx_nmea_batch* nm = nullptr;
+    hipStream_t s_copy = nullptr, s_filt = nullptr, s_tail = nullptr;
+    char* h_in[RX_NPIN] = {};          // pinned [ns][block_items] items
+    char* d_raw[RX_NRAW] = {};
+    cf* d_row[RX_NROW] = {};           // [ns * nch][T]
+    uint8_t* d_bits[RX_NOUT] = {};     // [ns * nch][cap]
+    int* d_prod[RX_NOUT] = {};
+    int* d_meta = nullptr;
+    char* h_res[RX_NRES] = {};         // pinned: int meta[RX_META], aisx_pdu recs[max_pdus], char text[text_cap]
+    hipEvent_t ev_copy[RX_NPIN] = {};  // the slot's copy to the device has finished
+    hipEvent_t ev_filt[RX_NRAW] = {};  // the raw buffer's filter call has finished
+    hipEvent_t ev_tail[RX_NOUT] = {};  // the deframer has read this set of bits / produced
+    hipEvent_t ev_res[RX_NRES] = {};   // the result slot is complete
+    const int* d_msk_status = nullptr;
+    const aisx_pdu *d_hd_pdus = nullptr, *d_nm_recs = nullptr;
+    const uint8_t* d_hd_bytes = nullptr;
+    const char* d_nm_text = nullptr;
+    const int *d_hd_count = nullptr, *d_nm_count = nullptr;
+    long long submitted = 0, issued = 0, popped = 0; // blocks copied and filtered; steps issued; results taken
+    bool acquired = false;
+    int failed = AISX_OK;
+    char failed_msg[512] = {};
+};
+
+static int rx_fail(aisx_rx* h, int rc)
+{
+    h->failed = rc;
+    snprintf(h->failed_msg, sizeof h->failed_msg, "%s", aisx_last_error());
+    return rc;
+}
+
+static int rx_failed(const aisx_rx* h, const char* who)
+{
+    set_err("%s: an earlier block failed (%s): destroy the handle", who, h->failed_msg);
+    return h->failed;
+}
+
+extern "C" int aisx_rx_destroy(aisx_rx* h)
+{
+    if (!h)
+        return AISX_OK;
+    OnDevice on(h->dev);
+    for (hipStream_t s : { h->s_copy, h->s_filt, h->s_tail })
+        if (s)
+            (void)hipStreamSynchronize(s);
+    if (h->chain) {
+        (void)aisx_chain_synchronize(h->chain);
+        (void)aisx_chain_destroy(h->chain); // (before the stage handles it borrows)
+    }
+    if (h->s_tail)
+        (void)hipStreamSynchronize(h->s_tail);
+    (void)aisx_nmea_batch_destroy(h->nm);
+    (void)aisx_hdlc_batch_destroy(h->hd);
+    (void)aisx_msk_destroy(h->msk);
+    (void)aisx_corr_destroy(h->corr);
+    (void)aisx_agc_destroy(h->agc);
+    (void)aisx_freqsync_destroy(h->fs);
+    (void)aisx_xlate_destroy(h->xl);
+    for (char*& p : h->h_in)
+        if (p)
+            (void)hipHostFree(p);
+    for (char*& p : h->h_res)
+        if (p)
+            (void)hipHostFree(p);
+    for (char*& p : h->d_raw)
+        dev_free(p);
+    for (cf*& p : h->d_row)
+        dev_free(p);
+    for (uint8_t*& p : h->d_bits)
+        dev_free(p);
+    for (int*& p : h->d_prod)
+        dev_free(p);
+    dev_free(h->d_meta);
+    auto drop = [](hipEvent_t* e, int n) {
+        for (int i = 0; i < n; i++)
+            if (e[i])
+                (void)hipEventDestroy(e[i]);
+    };
+    drop(h->ev_copy, RX_NPIN);
+    drop(h->ev_filt, RX_NRAW);
+    drop(h->ev_tail, RX_NOUT);
+    drop(h->ev_res, RX_NRES);
+    for (hipStream_t s : { h->s_copy, h->s_filt, h->s_tail })
+        if (s)
+            (void)hipStreamDestroy(s);
+    delete h;
+    return AISX_OK;
+}
+
+static int rx_build(aisx_rx* h, double rate, const double* center_freqs, const char* const* designators, const float* taps,
+                    int ntaps, const aisx_cf32* tmpl, int ntmpl, int max_dlen)
+{
+    int rc;
+    const int rows = h->ns * h->nch, T = h->T;
+    const double sps = rate / h->D / 9600.0;
+    if ((rc = aisx_xlate_create(&h->xl, h->D, taps, ntaps, center_freqs, h->nch, rate, h->ns, h->block_items)) != AISX_OK ||
+        (rc = aisx_freqsync_create(&h->fs, sps * 9600.0, 9600.0, RX_FFTLEN, rows, T)) != AISX_OK ||
+        (rc = aisx_agc_create(&h->agc, 512, 2.f, rows, T + RX_FFTLEN)) != AISX_OK)
+        return rc;
+    const int tag_cap = 4 * ((T + RX_FFTLEN) / 256) > 64 ? 4 * ((T + RX_FFTLEN) / 256) : 64;
+    if ((rc = aisx_corr_create(&h->corr, tmpl, ntmpl, (float)sps, 1, 0.9f, rows, T + RX_FFTLEN, tag_cap)) != AISX_OK ||
+        (rc = aisx_msk_create(&h->msk, (float)sps, 0.04f, 0.01f, 1, rows, T + RX_FFTLEN)) != AISX_OK ||
+        (rc = aisx_chain_create(&h->chain, h->fs, h->agc, h->corr, h->msk, rows, T, RX_FFTLEN)) != AISX_OK)
+        return rc;
+    h->cap = aisx_msk_out_capacity(h->msk);
+    std::vector<const char*> des((size_t)rows);
+    for (int r = 0; r < rows; r++)
+        des[r] = designators[r % h->nch];
+    h->text_cap = (long long)h->max_pdus * (nm_text_len(RX_LMAX - 1, max_dlen) + 1);
+    if ((rc = aisx_hdlc_batch_create(&h->hd, RX_LMIN, RX_LMAX, rows, h->cap, h->max_pdus)) != AISX_OK ||
+        (rc = aisx_nmea_batch_create(&h->nm, des.data(), rows, h->max_pdus, RX_LMAX, (long)h->text_cap)) != AISX_OK ||
+        (rc = aisx_msk_status_device(h->msk, &h->d_msk_status)) != AISX_OK ||
+        (rc = aisx_hdlc_batch_results_device(h->hd, &h->d_hd_pdus, &h->d_hd_bytes, &h->d_hd_count)) != AISX_OK ||
+        (rc = aisx_nmea_batch_results_device(h->nm, &h->d_nm_recs, &h->d_nm_text, &h->d_nm_count)) != AISX_OK)
+        return rc;
+    h->raw_bytes = (size_t)h->ns * h->block_items * h->item_bytes;
+    h->res_bytes = sizeof(int) * RX_META + sizeof(aisx_pdu) * (size_t)h->max_pdus + (size_t)h->text_cap;
+    for (char*& p : h->d_raw)
+        if ((rc = dev_alloc(&p, h->raw_bytes, false)) != AISX_OK)
+            return rc;
+    for (cf*& p : h->d_row)
+        if ((rc = dev_alloc(&p, (size_t)rows * T, false)) != AISX_OK)
+            return rc;
+    for (uint8_t*& p : h->d_bits)
+        if ((rc = dev_alloc(&p, (size_t)rows * h->cap, false)) != AISX_OK)
+            return rc;
+    for (int*& p : h->d_prod)
+        if ((rc = dev_alloc(&p, (size_t)rows)) != AISX_OK)
+            return rc;
+    if ((rc = dev_alloc(&h->d_meta, RX_META)) != AISX_OK)
+        return rc;
+    for (char*& p : h->h_in)
+        AISX_HIPCHK(hipHostMalloc((void**)&p, h->raw_bytes));
+    for (char*& p : h->h_res)
+        AISX_HIPCHK(hipHostMalloc((void**)&p, h->res_bytes));
+    for (hipStream_t* s : { &h->s_copy, &h->s_filt, &h->s_tail })
+        AISX_HIPCHK(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+    auto make = [](hipEvent_t* e, int n) {
+        for (int i = 0; i < n; i++)
+            if (hipEventCreateWithFlags(&e[i], hipEventDisableTiming) != hipSuccess)
+                return false;
+        return true;
+    };
+    if (!make(h->ev_copy, RX_NPIN) || !make(h->ev_filt, RX_NRAW) || !make(h->ev_tail, RX_NOUT) || !make(h->ev_res, RX_NRES)) {
+        set_err("aisx_rx_create: hipEventCreateWithFlags failed");
+        return AISX_ERR_HIP;
+    }
+    AISX_HIPCHK(hipDeviceSynchronize()); // (the buffers were zeroed on the null stream, which the handle's streams do not follow)
+    return AISX_OK;
+}
+
+extern "C" int aisx_rx_create(aisx_rx** out, double rate, int nstreams, int nchan_per_stream, const double* center_freqs,
+                              const char* const* designators, int fmt, float scale, float bias, int block_items,
+                              const float* taps, int ntaps, const aisx_cf32* tmpl, int ntmpl, int max_pdus_per_block)
+{
+    if (!out)
+        return AISX_ERR_INVALID;
+    *out = nullptr;
+    if (!(rate >= 48000.0) || !isfinite(rate) || rate / 48000.0 > XL_MAX_DECIM) {
+        set_err("aisx_rx_create: the decimation is int(rate / 48000): need 48000 <= rate <= 48000 * %d", XL_MAX_DECIM);
+        return AISX_ERR_INVALID;
+    }
+    const int D = (int)(rate / 48000.0);
+    if (!xlate_fmt_ok(fmt, scale, bias)) {
+        set_err("aisx_rx_create: need a format 0 .. 3 (cf32, cs16, cs8, cu8) and a finite scale and bias");
+        return AISX_ERR_INVALID;
+    }
+    if (nstreams < 1 || nchan_per_stream < 1 || !center_freqs || !designators || !tmpl || ntmpl < 1 || max_pdus_per_block < 1 ||
+        (taps && ntaps < 1) || (long long)nstreams * nchan_per_stream > (1 << 20)) {
+        set_err("aisx_rx_create: need nstreams >= 1, nchan_per_stream >= 1 (at most 2^20 channels in all), centre "
+                "frequencies, designators, a template and max_pdus_per_block >= 1");
+        return AISX_ERR_INVALID;
+    }
+    if (block_items < D || block_items % D != 0) {
+        set_err("aisx_rx_create: block_items (%d) must be a positive multiple of the decimation (%d)", block_items, D);
+        return AISX_ERR_INVALID;
+    }
+    int max_dlen = 0;
+    for (int c = 0; c < nchan_per_stream; c++) {
+        const size_t n = designators[c] ? strnlen(designators[c], NM_DESIG + 1) : NM_DESIG + 1;
+        if (n > (size_t)NM_DESIG) {
+            set_err("aisx_rx_create: designator %d is missing or longer than %d bytes", c, NM_DESIG);
+            return AISX_ERR_INVALID;
+        }
+        max_dlen = (int)n > max_dlen ? (int)n : max_dlen;
+    }
+    std::vector<float> own;
+    if (!taps) {
+        own = low_pass(rate, 11e3, 1e3);
+        taps = own.data();
+        ntaps = (int)own.size();
+    }
+    if (const char* why = XlateHost::check(D, taps, ntaps, center_freqs, nchan_per_stream, rate, nstreams, block_items)) {
+        set_err("aisx_rx_create: the filter: %s", why);
+        return AISX_ERR_INVALID;
+    }
+    int rc = require_device();
+    if (rc != AISX_OK)
+        return rc;
+    aisx_rx* h = new aisx_rx();
+    if (hipGetDevice(&h->dev) != hipSuccess) {
+        delete h;
+        set_err("aisx_rx_create: hipGetDevice failed");
+        return AISX_ERR_HIP;
+    }
+    h->fmt = fmt;
+    h->item_bytes = xlate_item_bytes(fmt);
+    h->scale = scale;
+    h->bias = bias;
+    h->ns = nstreams;
+    h->nch = nchan_per_stream;
+    h->D = D;
+    h->block_items = block_items;
+    h->T = block_items / D;
+    h->max_pdus = max_pdus_per_block;
+    if ((rc = rx_build(h, rate, center_freqs, designators, taps, ntaps, tmpl, ntmpl, max_dlen)) != AISX_OK) {
+        const std::string msg = aisx_last_error();
+        aisx_rx_destroy(h);
+        set_err("%s", msg.c_str());
+        return rc;
+    }
+    *out = h;
+    return AISX_OK;
+}
+
+extern "C" int aisx_rx_geometry(const aisx_rx* h, int* decim, int* items_per_block, int* nchan, int* input_slots,
+                                int* result_slots, long* text_cap)
+{
+    if (!h)
+        return AISX_ERR_INVALID;
+    if (decim)
+        *decim = h->D;
+    if (items_per_block)
+        *items_per_block = h->T;
+    if (nchan)
+        *nchan = h->ns * h->nch;
+    if (input_slots)
+        *input_slots = RX_NPIN;
+    if (result_slots)
+        *result_slots = RX_NRES;
+    if (text_cap)
+        *text_cap = (long)h->text_cap;
+    return AISX_OK;
+}
+
+extern "C" int aisx_rx_acquire(aisx_rx* h, void** slot, long* stride_items)
+{
+    if (!h || !slot) {
+        set_err("aisx_rx_acquire: need a handle and somewhere to put the slot");
+        return AISX_ERR_INVALID;
+    }
+    if (h->failed != AISX_OK)
+        return rx_failed(h, "aisx_rx_acquire");
+    OnDevice on(h->dev);
+    AISX_HIPCHK(on.err);
+    const int pin = (int)(h->submitted % RX_NPIN);
+    if (!h->acquired && h->submitted >= RX_NPIN)
+        AISX_HIPCHK(hipEventSynchronize(h->ev_copy[pin])); // (block submitted - NPIN was copied from it)
+    h->acquired = true;
+    *slot = h->h_in[pin];
+    if (stride_items)
+        *stride_items = h->block_items;
+    return AISX_OK;
+}
+
+// chain step, deframer, NMEA stage and the copy back of block k; next = block k + 1's rows or nullptr
+static int rx_issue(aisx_rx* h, long long k, const cf* next)
+{
+    int rc;
+    const int set = (int)(k % RX_NOUT), res = (int)(k % RX_NRES), rows = h->ns * h->nch, T = h->T;
+    if (k >= RX_NOUT) // the deframer has read this set's bits of step k - NOUT
+        AISX_HIPCHK(hipStreamWaitEvent(h->s_filt, h->ev_tail[set], 0));
+    long long step = -1;
+    if ((rc = aisx_chain_step(h->chain, (const aisx_cf32*)h->d_row[k % RX_NROW], T, T, (const aisx_cf32*)next, T, next ? T : 0, nullptr,
+                              h->d_bits[set], h->cap, h->d_prod[set], h->s_filt, &step)) != AISX_OK)
+        return rc;
+    if (step != k) {
+        set_err("aisx_rx: the chain numbered block %lld as step %lld", k, step);
+        return AISX_ERR_RUNTIME;
+    }
+    hipStream_t st = h->s_tail;
+    if ((rc = aisx_chain_wait(h->chain, k, st, 0)) != AISX_OK ||
+        (rc = aisx_hdlc_batch_process(h->hd, h->d_bits[set], h->cap, h->d_prod[set], st)) != AISX_OK)
+        return rc;
+    AISX_HIPCHK(hipEventRecord(h->ev_tail[set], st));
+    if ((rc = aisx_nmea_batch_process(h->nm, h->d_hd_pdus, h->d_hd_bytes, h->d_hd_count + 1, h->d_hd_count, st)) != AISX_OK)
+        return rc;
+    hipLaunchKernelGGL(k_rx_meta, dim3(1), dim3(256), 0, st, h->d_msk_status, rows, h->d_hd_count, h->d_nm_count, h->d_meta);
+    AISX_HIPCHK(hipGetLastError());
+    // (the bad-input flags are this block's: cleared behind the record that took them)
+    AISX_HIPCHK(hipMemsetAsync((void*)(h->d_hd_count + 2), 0, sizeof(int), st));
+    AISX_HIPCHK(hipMemsetAsync((void*)(h->d_nm_count + 2), 0, sizeof(int), st));
+    char* r = h->h_res[res];
+    AISX_HIPCHK(hipMemcpyAsync(r, h->d_meta, sizeof(int) * RX_META, hipMemcpyDeviceToHost, st));
+    AISX_HIPCHK(hipMemcpyAsync(r + sizeof(int) * RX_META, h->d_nm_recs, sizeof(aisx_pdu) * (size_t)h->max_pdus, hipMemcpyDeviceToHost, st));
+    AISX_HIPCHK(hipMemcpyAsync(r + sizeof(int) * RX_META + sizeof(aisx_pdu) * (size_t)h->max_pdus, h->d_nm_text, (size_t)h->text_cap,
+                               hipMemcpyDeviceToHost, st));
+    AISX_HIPCHK(hipEventRecord(h->ev_res[res], st));
+    h->issued = k + 1;
+    return AISX_OK;
+}
+
+static bool rx_results_full(const aisx_rx* h) { return h->issued - h->popped >= RX_NRES; }
+
+extern "C" int aisx_rx_submit(aisx_rx* h, long long* block)
+{
+    if (!h) {
+        set_err("aisx_rx_submit: need a handle");
+        return AISX_ERR_INVALID;
+    }
+    if (h->failed != AISX_OK)
+        return rx_failed(h, "aisx_rx_submit");
+    if (!h->acquired) {
+        set_err("aisx_rx_submit: no slot has been acquired");
+        return AISX_ERR_INVALID;
+    }
+    const long long b = h->submitted;
+    const bool step_due = b >= 1 && h->issued < b; // block b - 1 waits for this one
+    if (step_due && rx_results_full(h)) {
+        set_err("aisx_rx_submit: all %d result slots wait to be popped; nothing was queued", RX_NRES);
+        return AISX_ERR_OVERFLOW;
+    }
+    OnDevice on(h->dev);
+    AISX_HIPCHK(on.err);
+    const int pin = (int)(b % RX_NPIN), raw = (int)(b % RX_NRAW), row = (int)(b % RX_NROW);
+    auto queue = [&]() -> int {
+        int rc;
+        if (b >= RX_NRAW) // the filter call of block b - NRAW has read the raw buffer
+            AISX_HIPCHK(hipStreamWaitEvent(h->s_copy, h->ev_filt[raw], 0));
+        AISX_HIPCHK(hipMemcpyAsync(h->d_raw[raw], h->h_in[pin], h->raw_bytes, hipMemcpyHostToDevice, h->s_copy));
+        AISX_HIPCHK(hipEventRecord(h->ev_copy[pin], h->s_copy));
+        AISX_HIPCHK(hipStreamWaitEvent(h->s_filt, h->ev_copy[pin], 0));
+        if (b >= RX_NROW && (rc = aisx_chain_wait_input(h->chain, b - RX_NROW, h->s_filt, 0)) != AISX_OK)
+            return rc; // (the row buffer was last read by step b - NROW)
+        int nout = 0;
+        if ((rc = aisx_xlate_process_fmt(h->xl, h->d_raw[raw], h->fmt, h->scale, h->bias, h->block_items, h->block_items,
+                                         (aisx_cf32*)h->d_row[row], h->T, &nout, h->s_filt)) != AISX_OK)
+            return rc;
+        AISX_HIPCHK(hipEventRecord(h->ev_filt[raw], h->s_filt));
+        if (nout != h->T) {
+            set_err("aisx_rx: the filter gave %d items for a block of %d", nout, h->T);
+            return AISX_ERR_RUNTIME;
+        }
+        h->submitted = b + 1;
+        h->acquired = false;
+        return step_due ? rx_issue(h, b - 1, h->d_row[row]) : AISX_OK;
+    };
+    const int rc = queue();
+    if (rc != AISX_OK)
+        return rx_fail(h, rc);
+    if (block)
+        *block = b;
+    return AISX_OK;
+}
+
+extern "C" int aisx_rx_push(aisx_rx* h, const void* host_iq, long stride_items, long long* block)
+{
+    if (!h || !host_iq || stride_items < h->block_items) {
+        set_err("aisx_rx_push: need a handle, the block and a row stride of at least block_items");
+        return AISX_ERR_INVALID;
+    }
+    if (h->failed != AISX_OK)
+        return rx_failed(h, "aisx_rx_push");
+    if (h->submitted >= 1 && h->issued < h->submitted && rx_results_full(h)) {
+        set_err("aisx_rx_push: all %d result slots wait to be popped; nothing was queued", RX_NRES);
+        return AISX_ERR_OVERFLOW;
+    }
+    void* slot = nullptr;
+    int rc = aisx_rx_acquire(h, &slot, nullptr);
+    if (rc != AISX_OK)
+        return rc;
+    const size_t row = (size_t)h->block_items * h->item_bytes;
+    for (int s = 0; s < h->ns; s++)
+        memcpy((char*)slot + s * row, (const char*)host_iq + (size_t)s * stride_items * h->item_bytes, row);
+    return aisx_rx_submit(h, block);
+}
+
+extern "C" int aisx_rx_flush(aisx_rx* h)
+{
+    if (!h) {
+        set_err("aisx_rx_flush: need a handle");
+        return AISX_ERR_INVALID;
+    }
+    if (h->failed != AISX_OK)
+        return rx_failed(h, "aisx_rx_flush");
+    if (h->issued >= h->submitted)
+        return AISX_OK;
+    if (rx_results_full(h)) {
+        set_err("aisx_rx_flush: all %d result slots wait to be popped; nothing was queued", RX_NRES);
+        return AISX_ERR_OVERFLOW;
+    }
+    OnDevice on(h->dev);
+    AISX_HIPCHK(on.err);
+    const int rc = rx_issue(h, h->submitted - 1, nullptr);
+    return rc != AISX_OK ? rx_fail(h, rc) : AISX_OK;
+}
+
+extern "C" int aisx_rx_pop(aisx_rx* h, int wait, long long* block, char* text, long text_cap, long* text_len, aisx_pdu* recs,
+                           int rec_cap, int* nrecs, int* status)
+{
+    if (!h || !block || !text_len || !nrecs || text_cap < 0 || rec_cap < 0 || (text_cap > 0 && !text) || (rec_cap > 0 && !recs)) {
+        set_err("aisx_rx_pop: need a handle, outputs for the block number and the counts, and buffers for their capacities");
+        return AISX_ERR_INVALID;
+    }
+    if (h->failed != AISX_OK)
+        return rx_failed(h, "aisx_rx_pop");
+    *block = -1;
+    *text_len = 0;
+    *nrecs = 0;
+    if (status)
+        *status = 0;
+    if (h->popped >= h->issued)
+        return AISX_OK;
+    OnDevice on(h->dev);
+    AISX_HIPCHK(on.err);
+    const int res = (int)(h->popped % RX_NRES);
+    if (!wait) {
+        const hipError_t e = hipEventQuery(h->ev_res[res]);
+        if (e == hipErrorNotReady)
+            return AISX_OK;
+        AISX_HIPCHK(e);
+    } else {
+        const hipError_t e = hipEventSynchronize(h->ev_res[res]);
+        if (e != hipSuccess) {
+            set_err("aisx_rx_pop: waiting for block %lld failed: %s", h->popped, hipGetErrorString(e));
+            return rx_fail(h, AISX_ERR_HIP);
+        }
+    }
+    const char* r = h->h_res[res];
+    const int* meta = (const int*)r;
+    const aisx_pdu* rr = (const aisx_pdu*)(r + sizeof(int) * RX_META);
+    const char* tt = r + sizeof(int) * RX_META + sizeof(aisx_pdu) * (size_t)h->max_pdus;
+    int k = meta[5]; // records the NMEA stage wrote
+    if (k < 0 || k > h->max_pdus)
+        k = 0;
+    const long long nt = k > 0 ? rr[k - 1].offset + rr[k - 1].len + (rr[k - 1].len > 0 ? 1 : 0) : 0;
+    *nrecs = k;
+    *text_len = (long)nt;
+    if (k > rec_cap || nt > text_cap) {
+        set_err("aisx_rx_pop: block %lld has %d records and %lld bytes of text; the buffers hold %d and %ld", h->popped, k, nt,
+                rec_cap, text_cap);
+        return AISX_ERR_OVERFLOW;
+    }
+    if (k > 0)
+        memcpy(recs, rr, sizeof(aisx_pdu) * (size_t)k);
+    if (nt > 0)
+        memcpy(text, tt, (size_t)nt);
+    if (status)
+        *status = meta[0] | (meta[1] > meta[2] ? AISX_RX_ST_HDLC_OVERFLOW : 0) | (meta[5] < meta[2] ? AISX_RX_ST_NMEA_OVERFLOW : 0) |
+                  ((meta[3] || meta[6]) ? AISX_RX_ST_BAD_COUNT : 0);
+    *block = h->popped++;
+    return AISX_OK;
+}
+
+extern "C" int aisx_rx_set_center_freq(aisx_rx* h, int stream, int chan, double center_freq)
+{
+    if (!h) {
+        set_err("aisx_rx_set_center_freq: need a handle");
+        return AISX_ERR_INVALID;
+    }
+    if (h->failed != AISX_OK)
+        return rx_failed(h, "aisx_rx_set_center_freq");
+    return aisx_xlate_set_center_freq(h->xl, stream, chan, center_freq);
+}

@@ -18,6 +18,15 @@ __global__ __launch_bounds__(XL_T) void k_xlate(XlateParams p, const float* __re
     xlate_body<R>(cx, p, taps);
 }
 
+// the same body reading the source's own sample format (AISX_FMT_CS16 / CS8 / CU8), converted where it is staged
+template <int R, class Ld>
+__global__ __launch_bounds__(XL_T) void k_xlate_fmt(XlateParams p, const float* __restrict__ taps)
+{
+    __shared__ __attribute__((aligned(16))) cf smem[XL_LDS_ITEMS];
+    DevCtx cx{ (char*)smem };
+    xlate_body<R, DevCtx, Ld>(cx, p, taps);
+}
+
 struct aisx_xlate {
     int dev = 0;
     XlateHost hs;                          // geometry, plan, phases, stream position (k_xlate.h)
@@ -167,22 +176,33 @@ extern "C" int aisx_xlate_reset(aisx_xlate* h)
 }
 
 template <int R>
-static void launch(const aisx_xlate* h, const XlateParams& p, int ntiles, hipStream_t st)
+static void launch(const aisx_xlate* h, const XlateParams& p, int fmt, int ntiles, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_xlate<R>, dim3(ntiles, h->hs.ns), dim3(XL_T), 0, st, p, (const float*)h->d_taps);
+    const dim3 grid(ntiles, h->hs.ns), block(XL_T);
+    const float* taps = h->d_taps;
+    switch (fmt) {
+    case XL_FMT_CS16: hipLaunchKernelGGL((k_xlate_fmt<R, XlLoadCS16>), grid, block, 0, st, p, taps); break;
+    case XL_FMT_CS8: hipLaunchKernelGGL((k_xlate_fmt<R, XlLoadCS8>), grid, block, 0, st, p, taps); break;
+    case XL_FMT_CU8: hipLaunchKernelGGL((k_xlate_fmt<R, XlLoadCU8>), grid, block, 0, st, p, taps); break;
+    default: hipLaunchKernelGGL(k_xlate<R>, grid, block, 0, st, p, taps); break;
+    }
 }
 
-extern "C" int aisx_xlate_process(aisx_xlate* h, const aisx_cf32* d_in, long in_stride, int n, aisx_cf32* d_out,
-                                  long out_stride, int* nout, void* stream)
+static int xlate_process(const char* who, aisx_xlate* h, const void* d_in, int fmt, float scale, float bias, long in_stride,
+                         int n, aisx_cf32* d_out, long out_stride, int* nout, void* stream)
 {
     if (!h || !d_in || !d_out || !nout || n < 1 || n > h->hs.max_items || (h->hs.ns > 1 && in_stride < n)) {
-        set_err("aisx_xlate_process: need a handle, input, output and count; 1 <= n <= max_items (%d), "
-                "in_stride >= n", h ? h->hs.max_items : 0);
+        set_err("%s: need a handle, input, output and count; 1 <= n <= max_items (%d), "
+                "in_stride >= n", who, h ? h->hs.max_items : 0);
+        return AISX_ERR_INVALID;
+    }
+    if (!xlate_fmt_ok(fmt, scale, bias)) {
+        set_err("%s: need a format 0 .. 3 (cf32, cs16, cs8, cu8) and a finite scale and bias", who);
         return AISX_ERR_INVALID;
     }
     const int cnt = h->hs.count(n);
     if (h->hs.nrows() > 1 && out_stride < cnt) {
-        set_err("aisx_xlate_process: out_stride %ld is below the %d outputs of this call", out_stride, cnt);
+        set_err("%s: out_stride %ld is below the %d outputs of this call", who, out_stride, cnt);
         return AISX_ERR_INVALID;
     }
     OnDevice on(h->dev);
@@ -200,7 +220,9 @@ extern "C" int aisx_xlate_process(aisx_xlate* h, const aisx_cf32* d_in, long in_
         h->dirty = false;
     }
     XlateParams p = hs.params(n, in_stride, out_stride);
-    p.in = (const cf*)d_in;
+    p.in = d_in;
+    p.scale = scale;
+    p.bias = bias;
     p.hist_in = h->d_hist[h->hsel];
     p.hist_out = h->d_hist[h->hsel ^ 1];
     p.tab = h->d_tab;
@@ -208,14 +230,26 @@ extern "C" int aisx_xlate_process(aisx_xlate* h, const aisx_cf32* d_in, long in_
     p.out = (cf*)d_out;
     const int ntiles = hs.tiles(cnt);
     switch (hs.plan.R) {
-    case 8: launch<8>(h, p, ntiles, st); break;
-    case 4: launch<4>(h, p, ntiles, st); break;
-    case 2: launch<2>(h, p, ntiles, st); break;
-    default: launch<1>(h, p, ntiles, st); break;
+    case 8: launch<8>(h, p, fmt, ntiles, st); break;
+    case 4: launch<4>(h, p, fmt, ntiles, st); break;
+    case 2: launch<2>(h, p, fmt, ntiles, st); break;
+    default: launch<1>(h, p, fmt, ntiles, st); break;
     }
     AISX_HIPCHK(hipGetLastError());
     AISX_HIPCHK(hipEventRecord(h->ev_done, st));
     h->hsel ^= 1;
     *nout = cnt;
     return AISX_OK;
+}
+
+extern "C" int aisx_xlate_process(aisx_xlate* h, const aisx_cf32* d_in, long in_stride, int n, aisx_cf32* d_out,
+                                  long out_stride, int* nout, void* stream)
+{
+    return xlate_process("aisx_xlate_process", h, d_in, XL_FMT_CF32, 1.f, 0.f, in_stride, n, d_out, out_stride, nout, stream);
+}
+
+extern "C" int aisx_xlate_process_fmt(aisx_xlate* h, const void* d_in, int fmt, float scale, float bias, long in_stride,
+                                      int n, aisx_cf32* d_out, long out_stride, int* nout, void* stream)
+{
+    return xlate_process("aisx_xlate_process_fmt", h, d_in, fmt, scale, bias, in_stride, n, d_out, out_stride, nout, stream);
 }

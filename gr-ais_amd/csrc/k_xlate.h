@@ -36,7 +36,7 @@ constexpr int XL_MAX_TAPS = 1 << 17;
 constexpr int XL_MAX_CHAN = 1024;
 
 struct XlateParams {
-    const cf* in;                       // [nstreams][in_stride]: n new inputs per stream
+    const void* in;                     // [nstreams][in_stride] items of the loader's format: n new inputs per stream
     long long in_stride;
     const cf* hist_in;                  // [nstreams][Lh]: inputs m_abs - Lh .. m_abs - 1
     cf* hist_out;                       // [nstreams][Lh]: the same after this call
@@ -49,7 +49,38 @@ struct XlateParams {
     int n, nout, Lh, nch, D, L;
     int P, S, G, U, Utot;               // the plan (XlatePlan)
     unsigned long long magic;           // j / P = (j * magic) >> 32 for the window's j
+    float scale = 1.f, bias = 0.f;      // integer formats: value = ((float)raw - bias) * scale (fc32 ignores them)
 };
+
+// The input's item in memory (include/aisx.h, AISX_FMT_*).  An integer item becomes ((float)raw - bias) * scale on re
+// and im alike: two float32 operations, each rounded once ((a - b) * c cannot contract into an fma), so numpy's
+// (raw.astype(float32) - float32(bias)) * float32(scale) gives the same bits.  The history stays converted values.
+enum { XL_FMT_CF32 = 0, XL_FMT_CS16 = 1, XL_FMT_CS8 = 2, XL_FMT_CU8 = 3, XL_NFMT = 4 };
+
+struct XlLoadCF32 {
+    typedef cf item;
+    static AISX_HD cf load(const item* x, long long i, float, float) { return x[i]; }
+};
+template <class I>
+struct XlLoadInt {
+    struct item {
+        I re, im;
+    };
+    static AISX_HD cf load(const item* x, long long i, float scale, float bias)
+    {
+        const item v = x[i];
+        return mk(((float)v.re - bias) * scale, ((float)v.im - bias) * scale);
+    }
+};
+typedef XlLoadInt<short> XlLoadCS16;
+typedef XlLoadInt<signed char> XlLoadCS8;
+typedef XlLoadInt<unsigned char> XlLoadCU8;
+
+inline bool xlate_fmt_ok(int fmt, float scale, float bias)
+{
+    return fmt >= 0 && fmt < XL_NFMT && isfinite(scale) && isfinite(bias);
+}
+inline int xlate_item_bytes(int fmt) { return fmt == XL_FMT_CF32 ? 8 : fmt == XL_FMT_CS16 ? 4 : 2; }
 
 // acc + h * z on re and im: one v_pk_fma_f32 on the device
 AISX_HD cf xl_fma(float h, cf z, cf acc)
@@ -85,7 +116,7 @@ AISX_HD cf xl_rot(unsigned long long inc, unsigned long long off, long long m)
     return mk((float)cs, (float)-sn);
 }
 
-template <int R, class Ctx>
+template <int R, class Ctx, class Ld = XlLoadCF32>
 AISX_DI void xlate_body(Ctx& cx, const XlateParams& p, const float* __restrict__ taps)
 {
     const int t = cx.tid(), nt = cx.nthreads();
@@ -97,7 +128,7 @@ AISX_DI void xlate_body(Ctx& cx, const XlateParams& p, const float* __restrict__
     const bool tile_on = col0 < p.nout;
     const long long mb = (p.k_first + col0) * (long long)p.D - (p.L - 1);
     const long long m_end = p.m_abs + p.n;
-    const cf* xin = p.in + (long long)s * p.in_stride;
+    const typename Ld::item* xin = (const typename Ld::item*)p.in + (long long)s * p.in_stride;
     const cf* hin = p.hist_in + (long long)s * p.Lh;
     const bool lane_on = t < p.G;
     const int P = p.P, S = p.S;
@@ -123,7 +154,7 @@ AISX_DI void xlate_body(Ctx& cx, const XlateParams& p, const float* __restrict__
                 const long long m = m0 + j;
                 cf z = mk(0.f, 0.f);
                 if (m >= 0 && m < m_end && m >= p.m_abs - p.Lh) {
-                    const cf x = m >= p.m_abs ? xin[m - p.m_abs] : hin[m - (p.m_abs - p.Lh)];
+                    const cf x = m >= p.m_abs ? Ld::load(xin, m - p.m_abs, p.scale, p.bias) : hin[m - (p.m_abs - p.Lh)];
                     const cf rot = cmul_fma(base[(m >> XL_LB) - b0], tab[m & (XL_B - 1)]);
                     z = cmul_fma(x, rot);
                 }
@@ -164,7 +195,7 @@ AISX_DI void xlate_body(Ctx& cx, const XlateParams& p, const float* __restrict__
             const long long m = m_end - p.Lh + j;
             cf v = mk(0.f, 0.f);
             if (m >= p.m_abs)
-                v = xin[m - p.m_abs];
+                v = Ld::load(xin, m - p.m_abs, p.scale, p.bias);
             else if (m >= p.m_abs - p.Lh)
                 v = hin[m - (p.m_abs - p.Lh)];
             ho[j] = v;

@@ -236,6 +236,8 @@ int aisx_msk_set_max_noutput_items(aisx_msk* h, int max_noutput_items);
 int aisx_msk_set_time_parallel(aisx_msk* h, int restart_points_per_channel, int join_kernel, int max_unit_items);
 int aisx_msk_get_max_noutput_items(const aisx_msk* h);
 int aisx_msk_last_status(aisx_msk* h, int* status, void* stream);
+/* the per-channel status words [nchan] in device memory (what aisx_msk_last_status copies and or-s) */
+int aisx_msk_status_device(const aisx_msk* h, const int** d_status);
 /* Diagnostics of the time-parallel recovery (k_mskp.h) for the last aisx_msk_process_stream call,
  * summed over the channels: out10 (ten entries) = { restart points chosen, units whose run was taken over,
  * symbols that came from units, units that ended at the next restart point, units that ended
@@ -520,6 +522,20 @@ int aisx_xlate_output_count(const aisx_xlate* h, int n);
  * Any split of an input into calls gives the same outputs, bit for bit. */
 int aisx_xlate_process(aisx_xlate* h, const aisx_cf32* d_in, long in_stride, int n, aisx_cf32* d_out, long out_stride,
                        int* nout, void* stream);
+/* The item formats SDR sources deliver.  An integer item's value is ((float)raw - bias) * scale on re and im alike:
+ * two float32 operations, each rounded once, so numpy's (raw.astype(float32) - float32(bias)) * float32(scale) gives
+ * the same bits (an RTL-SDR's unsigned bytes: bias 127.5 or the caller's choice).  CF32 ignores scale and bias. */
+enum {
+    AISX_FMT_CF32 = 0, /* float re, im */
+    AISX_FMT_CS16 = 1, /* int16 re, im */
+    AISX_FMT_CS8 = 2,  /* int8 re, im */
+    AISX_FMT_CU8 = 3   /* uint8 re, im */
+};
+/* aisx_xlate_process for d_in [nstreams][in_stride] ITEMS of `fmt`, converted where the filter stages its window: the
+ * same outputs, bit for bit, as aisx_xlate_process on the converted values.  The history the handle carries is the
+ * converted values, so a stream may change format between calls.  scale and bias must be finite. */
+int aisx_xlate_process_fmt(aisx_xlate* h, const void* d_in, int fmt, float scale, float bias, long in_stride, int n,
+                           aisx_cf32* d_out, long out_stride, int* nout, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* host-side tail of the receive chain (python/radio.py:64-73): per-packet,   */
@@ -606,6 +622,65 @@ int aisx_nmea_batch_results_device(const aisx_nmea_batch* h, const aisx_pdu** d_
  * previous read met bad input (the flag is then cleared). */
 int aisx_nmea_batch_read(aisx_nmea_batch* h, aisx_pdu* recs, int rec_cap, char* text, long text_cap, int* nrecs,
                          int* nfound, void* stream);
+
+/* ------------------------------------------------------------------------ */
+/* ais_rx (python/radio.py:40-73) as ONE handle, fed from host memory in the  */
+/* source's own sample format: freq_xlating_fir_filter_ccf -> ais_demod ->    */
+/* hdlc_deframer_bp -> pdu_to_nmea for nstreams sources at once               */
+/* ------------------------------------------------------------------------ */
+typedef struct aisx_rx aisx_rx;
+/* bits of aisx_rx_pop's *status above the msk status word (AISX_MSK_ST_*, or-ed over channels as the device holds it
+ * when the block's tail runs) */
+enum {
+    AISX_RX_ST_HDLC_OVERFLOW = 0x100, /* more PDUs found than max_pdus_per_block: a prefix was kept */
+    AISX_RX_ST_NMEA_OVERFLOW = 0x200, /* fewer records armoured than the deframer kept */
+    AISX_RX_ST_BAD_COUNT = 0x400      /* the deframer or the NMEA stage met a count, channel or length out of range */
+};
+/* nstreams sources at `rate` samples per second, nchan_per_stream centres each (center_freqs [nstreams][nchan], |f| <=
+ * rate / 2; designators [nchan_per_stream], 0..16 bytes each: radio.py:88-89 gives {-25e3, +25e3} and {"A", "B"}).
+ * Constants as radio.py:47-65: decimation int(rate / 48000) (so rate >= 48000), taps low_pass(1, rate, 11e3, 1e3)
+ * unless given (taps == NULL), samples_per_symbol = rate / decimation / 9600, clock recovery gain 0.04 and limit 0.01,
+ * fftlen 1024, deframer (11, 64).  Every block is block_items raw items per stream in `fmt` (AISX_FMT_*, with scale
+ * and bias as aisx_xlate_process_fmt), a multiple of the decimation, so that every block is block_items / decimation
+ * items per channel.  tmpl / ntmpl: the preamble at the demod rate (what ais_demod builds for corr_est).  At most
+ * max_pdus_per_block PDUs per block come out.  The handle owns the filter, the four stage handles and their chain,
+ * the deframer, the NMEA stage, AISX_CHAIN_DEPTH + 1 row buffers, two raw-input buffers on the device, three pinned
+ * host input slots, eight pinned result slots, and three streams of its own beside the chain's four (copy-in, filter,
+ * tail): GPU_MAX_HW_QUEUES >= 8 in the environment before the first HIP call lets all seven run side by side.
+ * Row s * nchan_per_stream + c of everything downstream (a record's chan) is stream s at centre c.
+ * One thread at a time per handle.  The handle belongs to the device that was current here. */
+int aisx_rx_create(aisx_rx** h, double rate, int nstreams, int nchan_per_stream, const double* center_freqs,
+                   const char* const* designators, int fmt, float scale, float bias, int block_items, const float* taps,
+                   int ntaps, const aisx_cf32* tmpl, int ntmpl, int max_pdus_per_block);
+int aisx_rx_destroy(aisx_rx* h); /* waits for what is in flight */
+/* any pointer may be NULL: the decimation, items per channel and block, channels (nstreams * nchan_per_stream), pinned
+ * input slots, result slots, bytes of text a block can give at most */
+int aisx_rx_geometry(const aisx_rx* h, int* decim, int* items_per_block, int* nchan, int* input_slots, int* result_slots,
+                     long* text_cap);
+/* a pinned host slot [nstreams][*stride_items] items for the source to write the next block into (the same slot until
+ * it is submitted); blocks the calling thread only while every slot is still being copied from */
+int aisx_rx_acquire(aisx_rx* h, void** slot, long* stride_items);
+/* The slot acquired last is full: queues its copy to the device (copy stream), its filter call (one block ahead of
+ * the chain, so that aisx_chain_step gets its d_in_next) and the chain step, deframer and NMEA stage of the block
+ * BEFORE it, whose results go to a pinned result slot on the tail stream.  Returns without waiting for the device.
+ * *block (optional) = this block's number, from 0.  When the block before it would need a result slot and all are
+ * waiting to be popped: AISX_ERR_OVERFLOW, nothing queued, the slot stays acquired -- pop, then submit again. */
+int aisx_rx_submit(aisx_rx* h, long long* block);
+/* acquire + memcpy of [nstreams][block_items] items from host_iq (row stride stride_items) + submit */
+int aisx_rx_push(aisx_rx* h, const void* host_iq, long stride_items, long long* block);
+/* issues the block that is waiting for its successor, without look-ahead (same results); AISX_ERR_OVERFLOW as submit */
+int aisx_rx_flush(aisx_rx* h);
+/* The oldest finished block not yet popped, in block order: *block its number; its NMEA text, one '\n' after every
+ * sentence (*text_len bytes); its records (chan, end_bit counted over the channel's whole bit stream, offset / len of
+ * the record's text in `text`); *status (optional) = 0 or the bits above.  wait == 0: *block = -1 when the next block
+ * has not finished (or none is issued); wait != 0 blocks the calling thread until it has (*block = -1 when none is
+ * issued).  A block stays available until it is popped, whatever has been submitted since.  When the caller's
+ * buffers are too small: AISX_ERR_OVERFLOW with *nrecs / *text_len = what is needed, and the block stays. */
+int aisx_rx_pop(aisx_rx* h, int wait, long long* block, char* text, long text_cap, long* text_len, aisx_pdu* recs,
+                int rec_cap, int* nrecs, int* status);
+/* from the next submitted block on (aisx_xlate_set_center_freq of the handle's filter) */
+int aisx_rx_set_center_freq(aisx_rx* h, int stream, int chan, double center_freq);
+/* A failed block (a HIP error, the chain refusing) makes every later call but destroy return that block's error. */
 
 #ifdef __cplusplus
 }
