@@ -642,7 +642,9 @@ enum {
  * unless given (taps == NULL), samples_per_symbol = rate / decimation / 9600, clock recovery gain 0.04 and limit 0.01,
  * fftlen 1024, deframer (11, 64).  Every block is block_items raw items per stream in `fmt` (AISX_FMT_*, with scale
  * and bias as aisx_xlate_process_fmt), a multiple of the decimation, so that every block is block_items / decimation
- * items per channel.  tmpl / ntmpl: the preamble at the demod rate (what ais_demod builds for corr_est).  At most
+ * items per channel.  That count need not be a multiple of fftlen: the chain holds the items short of a whole vector
+ * back for the next block (stream_to_vector), so a block's text is that of the vectors completed in it, the same with
+ * and without look-ahead.  tmpl / ntmpl: the preamble at the demod rate (what ais_demod builds for corr_est).  At most
  * max_pdus_per_block PDUs per block come out.  The handle owns the filter, the four stage handles and their chain,
  * the deframer, the NMEA stage, AISX_CHAIN_DEPTH + 1 row buffers, two raw-input buffers on the device, three pinned
  * host input slots, eight pinned result slots, and three streams of its own beside the chain's four (copy-in, filter,

@@ -83,18 +83,29 @@ def same(popped, got):
         assert recs.tobytes() == g[2].tobytes(), b
 
 
-def hand_wired(ais, x_blocks, nstreams, retunes=()):
+def hand_wired(ais, x_blocks, nstreams, retunes=(), fs=tx.FS_STOCK, freqs=(-25e3, 25e3), designators=("A", "B"), taps=None,
+               template=None, max_pdus=1 << 16, counts=None):
     """test_gpu_xlate._receiver's wiring, every step on its own, for any number of blocks; retunes: (block, stream,
-    chan, f) applied before that block is filtered.  Returns per block (recs, text)."""
+    chan, f) applied before that block is filtered.  Returns per block (recs, text).  The defaults are the stock
+    receiver's; fs sets the decimation int(fs / 48000) and the samples per symbol as ais_rx does, freqs / designators
+    are per centre of every stream, taps default to low_pass(1, fs, 11e3, 1e3), template to the stock one, the block
+    length is x_blocks' own.  max_pdus below a block's PDUs: the kept prefix comes back (overflow_ok); counts, a list,
+    receives per block (PDUs found, records kept)."""
     import torch
 
-    taps = ais.firdes_low_pass(1.0, tx.FS_STOCK, 11e3, 1e3)
-    nch = 2 * nstreams
-    xl = ais.freq_xlating_fir_filter_ccf(tx.DECIM, taps, (-25e3, 25e3), tx.FS_STOCK, nstreams=nstreams, max_items=tx.T * tx.DECIM)
-    opts = dict(samples_per_symbol=tx.SPS, bits_per_sec=9600.0, clockrec_gain=0.04, omega_relative_limit=0.01, fftlen=1024)
-    dem = ais.ais_demod(opts, nchan=nch, max_items=tx.T, stages="stock", preamble_symbols=tx._template(ais))
-    hd = ais.hdlc_deframer_batch(11, 64, nch, dem.clockrec.out_capacity, 1 << 16)
-    nm = ais.pdu_to_nmea_batch(["A", "B"] * nstreams, nch, 1 << 16, 64)
+    decim = int(fs / 48000)
+    sps = fs / decim / 9600.0
+    if taps is None:
+        taps = ais.firdes_low_pass(1.0, fs, 11e3, 1e3)
+    if template is None:
+        template = tx._template(ais)
+    nch = len(freqs) * nstreams
+    n = x_blocks[0].shape[1]
+    xl = ais.freq_xlating_fir_filter_ccf(decim, taps, freqs, fs, nstreams=nstreams, max_items=n)
+    opts = dict(samples_per_symbol=sps, bits_per_sec=9600.0, clockrec_gain=0.04, omega_relative_limit=0.01, fftlen=1024)
+    dem = ais.ais_demod(opts, nchan=nch, max_items=n // decim, stages="stock", preamble_symbols=template)
+    hd = ais.hdlc_deframer_batch(11, 64, nch, dem.clockrec.out_capacity, max_pdus)
+    nm = ais.pdu_to_nmea_batch(list(designators) * nstreams, nch, max_pdus, 64)
     out = []
     for k, x in enumerate(x_blocks):
         for (kb, s, c, f) in retunes:
@@ -105,7 +116,9 @@ def hand_wired(ais, x_blocks, nstreams, retunes=()):
         dem.wait(r["step"])
         hd.work(r["bits"], r["produced"])
         nm.work(hd)
-        out.append(nm.sentences())
+        out.append(nm.sentences(overflow_ok=counts is not None))
+        if counts is not None:
+            counts.append((nm.found, len(out[-1][0])))
         dem.synchronize()
     torch.cuda.synchronize()
     return out

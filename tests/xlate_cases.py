@@ -1,6 +1,8 @@
 """Cases of the batched freq_xlating_fir_filter_ccf shared by the lane-model tests (test_xlate_model.py) and the
 device tests (test_gpu_xlate.py): the matrix of decimations, tap counts, centres, channel counts and ragged call
-sequences, the float64 reference (oracle_py.freq_xlating_fir, the oracle's orc_freq_xlating_fir) and the gate."""
+sequences, the float64 reference (oracle_py.freq_xlating_fir, the oracle's orc_freq_xlating_fir) and the gate; and
+what the tests of the integer sample formats share (test_gpu_xlate_fmt.py on the device, test_xlate_fmt_cases.py on the
+lane model): the formats' conversions, the converted values in float64, the device's plan of every case."""
 import numpy as np
 
 import oracle_py as orc
@@ -98,3 +100,39 @@ def retune_reference(taps, D, x, f_list, k_list, nout):
         const *= np.exp(-1j * (w_old - w_new) * D * kr)
         y[kr:] = orc.freq_xlating_fir(taps, D, f_list[i + 1], FS, x, 0, nout)[kr:] * const
     return y
+
+
+# ---- the integer sample formats (AISX_FMT_CS16 / CS8 / CU8) ----------------------------------------------------------
+
+FMT_CODES = dict(cs16=1, cs8=2, cu8=3)
+THIRD, TENTH = float(np.float32(1.0 / 3.0)), float(np.float32(0.1))
+# (scale, bias): the stock receiver's (test_gpu_rx.quantise: 2^-13, and 2^-5 with the RTL-SDR's 127.5 for cu8), then a
+# scale that is no power of two with a bias that float32 rounds: (raw - bias) rounds for most raw values and the
+# product rounds again, so a conversion fused into one fma, or done in another order, changes bits
+FMT_CONVERSIONS = dict(cs16=[(2.0 ** -13, 0.0), (THIRD, TENTH)], cs8=[(2.0 ** -5, 0.0), (THIRD, TENTH)],
+                       cu8=[(2.0 ** -5, 127.5), (THIRD, TENTH)])
+
+
+def fmt_seed(i, fmt, j):
+    """the seed of case i's raw input in format fmt for conversion j: the device test and the lane-model test draw the
+    same integers"""
+    return 7000 + 10 * i + FMT_CODES[fmt] + 100000 * j
+
+
+def converted64(raw, scale, bias):
+    """[..., 2] integers -> the converted values formed in float64 (exact: at most 17 + 24 significant bits)"""
+    v = (raw.astype(np.float64) - np.float64(np.float32(bias))) * np.float64(np.float32(scale))
+    return v[..., 0] + 1j * v[..., 1]
+
+
+def device_plans():
+    """xlate_plan on the device's 256 lanes for every case of the matrix (R, P, S, G, U, Utot), through the lane
+    model's binding of the same host code"""
+    import test_xlate_model as tm
+
+    return [tm.EmuXlate(c["D"], lowpass(c["L"], c["D"]), c["freqs"], FS, c["max_items"], nt=256).plan() for c in matrix()]
+
+
+def one_case_per_build():
+    """of the matrix, the 603-tap case of every decimation: R = 8, 8, 4, 2, then R = 1 on 120 and on 12 lanes"""
+    return [c for c in matrix() if c["L"] == 603]
