@@ -23,6 +23,8 @@ AISX_ERR_RUNTIME = -6
 
 AISX_FMT_CF32, AISX_FMT_CS16, AISX_FMT_CS8, AISX_FMT_CU8 = 0, 1, 2, 3
 AISX_RX_ST_HDLC_OVERFLOW, AISX_RX_ST_NMEA_OVERFLOW, AISX_RX_ST_BAD_COUNT = 0x100, 0x200, 0x400
+AISX_MSG_NA, AISX_MSG_STR = -(1 << 31), 48
+AISX_MSG_FL_COMPLETE, AISX_MSG_FL_NO_LAYOUT, AISX_MSG_FL_BAD_RECORD = 1, 2, 4
 
 KEY_CORR_START, KEY_PHASE_EST, KEY_TIME_EST, KEY_CORR_EST, KEY_PORT1 = 0, 1, 2, 3, 0x100
 KEY_NAMES = {0: "corr_start", 1: "phase_est", 2: "time_est", 3: "corr_est"}
@@ -210,6 +212,14 @@ def lib(device=True):
     sig("aisx_nmea_batch_process", i32, [vp, vp, vp, vp, vp, vp])
     sig("aisx_nmea_batch_results_device", i32, [vp, pvp, pvp, pvp])
     sig("aisx_nmea_batch_read", i32, [vp, vp, i32, vp, lng, pi32, pi32, vp])
+    sig("aisx_msg_decode", i32, [vp, i32, vp, vp])
+    sig("aisx_msg_batch_create", i32, [pvp, i32, i32, i32])
+    sig("aisx_msg_batch_destroy", i32, [vp])
+    sig("aisx_msg_batch_process", i32, [vp, vp, vp, vp, vp, vp])
+    sig("aisx_msg_batch_results_device", i32, [vp, pvp, plng, pvp, pvp])
+    sig("aisx_msg_batch_read", i32, [vp, vp, lng, vp, i32, pi32, pi32, vp])
+    sig("aisx_rx_enable_messages", i32, [vp])
+    sig("aisx_rx_pop_messages", i32, [vp, i32, pll, vp, lng, plng, vp, i32, pi32, vp, lng, vp, pi32])
     _lib = L
     return L
 

@@ -1,7 +1,8 @@
 """The receive chain's tail on the device, for every channel of a chain step at once, behind
 `ais_demod.work_pipelined`: the batched HDLC deframer (aisx_hdlc_batch_*, `hdlc_deframer_bp(11, 64)`,
 python/radio.py:64) and, queued behind it on the same stream, the batched `pdu_to_nmea` (aisx_nmea_batch_*,
-python/radio.py:73).  One copy per step brings back either the PDUs or a newline-terminated NMEA stream."""
+python/radio.py:73) and the batched ITU-R M.1371 field decoder (aisx_msg_batch_*).  One copy per step brings back the
+PDUs, a newline-terminated NMEA stream or a table of decoded messages -- or the table stays on the device as tensors."""
 import ctypes as C
 
 import numpy as np
@@ -194,3 +195,107 @@ class pdu_to_nmea_batch:
             return [(int(r["chan"]), int(r["end_bit"]), text[r["offset"]:r["offset"] + r["len"]].decode("latin-1"))
                     for r in recs]
         return recs, text
+
+
+class pdu_decode_batch:
+    """The ITU-R M.1371 fields of every PDU of a device list at once (aisx_msg_batch_*): row i is exactly
+    ais_amd.msg_decode(payload of record i), as a struct-of-arrays table in device memory -- int32
+    cols[len(MSG_COLUMNS)][max_pdus] and uint8 strs[max_pdus][48] -- so that a column is a torch tensor.  At most
+    max_pdus records per call on nchan channels, of at most length_max - 1 payload octets.
+
+    Queued behind the deframer on the caller's stream `s` (beside or instead of pdu_to_nmea_batch):
+
+        md = ais_amd.pdu_decode_batch(nchan, max_pdus, 64)
+        hd.work(r["bits"], r["produced"], stream=s)      # deframe step k on s
+        md.work(hd, stream=s)                            # and decode its PDUs, still on s: nothing waits
+        c = md.columns(stream=s)                         # device views: c["MMSI"], c["LON"], ... c["strs"]
+        near = c["MMSI"][(c["LAT"] > lat0) & (c["LAT"] < lat1)]
+
+    Values are the transmitted integers; MSG_NA (-2**31) marks a column the message does not carry."""
+
+    def __init__(self, nchan, max_pdus, length_max):
+        h = C.c_void_p()
+        check(_lib.lib().aisx_msg_batch_create(C.byref(h), int(nchan), int(max_pdus), int(length_max)), "pdu_decode_batch")
+        self._h = h
+        self.nchan, self.max_pdus, self.length_max = int(nchan), int(max_pdus), int(length_max)
+        self.found = 0  # PDUs the last call's producer found (decoded or not)
+        self._cols = self._strs = None  # read-back buffers, made on first use
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            _lib.lib().aisx_msg_batch_destroy(h)
+            self._h = None
+
+    def work(self, deframer, stream=None):
+        """Decodes the PDUs of the deframer's last call (queued on `stream`, default the current one; nothing
+        waits): records count + 1, PDUs found count + 0, so the deframer's overflow shows in messages()."""
+        p, b, n = deframer.results_device()
+        self.work_device(p, b, n + 4, n, stream)
+
+    def work_device(self, pdus_ptr, bytes_ptr, npdus_ptr, nfound_ptr=None, stream=None):
+        """Device addresses: records in the aisx_pdu layout, their payload bytes, ONE int = records to decode and
+        optionally ONE int = PDUs the producer found.  Queued on `stream`; the counts are read on the device."""
+        check(_lib.lib().aisx_msg_batch_process(self._h, C.c_void_p(pdus_ptr), C.c_void_p(bytes_ptr), C.c_void_p(npdus_ptr),
+                                                C.c_void_p(nfound_ptr) if nfound_ptr else None, _stream_ptr(stream)),
+              "pdu_decode_batch.work")
+
+    def results_device(self):
+        """device addresses of the last call's columns (int32 [ncol][col_stride]), the column stride in items, the
+        strings (char [max_pdus][48]) and the counts (int [3]: found, rows written, bad-input flag)"""
+        c, s, n, stride = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_long()
+        check(_lib.lib().aisx_msg_batch_results_device(self._h, C.byref(c), C.byref(stride), C.byref(s), C.byref(n)),
+              "pdu_decode_batch.results_device")
+        return c.value, stride.value, s.value, n.value
+
+    def _views(self):
+        from .framing import MSG_COLUMNS
+
+        c, stride, s, n = self.results_device()
+        dev = torch.device("cuda", torch.cuda.current_device())
+
+        class _Mem:  # (the handle owns the memory: a view keeps the handle alive through `owner`)
+            def __init__(self, owner, ptr, shape, typestr):
+                self.owner = owner
+                self.__cuda_array_interface__ = dict(shape=shape, typestr=typestr, data=(ptr, False), version=3)
+
+        cols = torch.as_tensor(_Mem(self, c, (len(MSG_COLUMNS), stride), "<i4"), device=dev)
+        strs = torch.as_tensor(_Mem(self, s, (self.max_pdus, _lib.AISX_MSG_STR), "|u1"), device=dev)
+        cnt = torch.as_tensor(_Mem(self, n, (3,), "<i4"), device=dev)
+        return cols, strs, cnt
+
+    def columns(self, stream=None):
+        """The last call's table where it is: {column name: int32 device tensor [kept]} for every name of
+        MSG_COLUMNS, and "strs": uint8 device tensor [kept, 48] -- views of the handle's buffers, which the next
+        work() overwrites.  Waits on `stream` only to learn the row count; self.found = PDUs the producer found."""
+        from .framing import MSG_COLUMNS
+
+        cols, strs, cnt = self._views()
+        s = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(s):
+            found, kept, _ = cnt.cpu().tolist()
+        self.found = found
+        kept = max(0, min(kept, self.max_pdus))
+        out = {name: cols[k, :kept] for k, name in enumerate(MSG_COLUMNS)}
+        out["strs"] = strs[:kept]
+        return out
+
+    def messages(self, stream=None, overflow_ok=False):
+        """The last call's table on the host (synchronises `stream`): a MSG_DTYPE structured array, one int32 field
+        per column (lower-case names) and callsign / name / destination as S7 / S20 / S20.  When fewer rows were
+        written than PDUs found (the deframer's overflow), OverflowError -- or with overflow_ok=True the rows
+        written (self.found tells how many there were).  ValueError when a call since the last read met a bad
+        count, channel or length (such a record's row has FLAGS = 4 and no fields)."""
+        from .framing import MSG_COLUMNS, msg_table
+
+        if self._cols is None:
+            self._cols = np.zeros((len(MSG_COLUMNS), self.max_pdus), dtype=np.int32)
+            self._strs = np.zeros((self.max_pdus, _lib.AISX_MSG_STR), dtype=np.uint8)
+        n, f = C.c_int(0), C.c_int(0)
+        rc = _lib.lib().aisx_msg_batch_read(self._h, self._cols.ctypes.data_as(C.c_void_p), self.max_pdus,
+                                            self._strs.ctypes.data_as(C.c_void_p), self.max_pdus, C.byref(n), C.byref(f),
+                                            _stream_ptr(stream))
+        self.found = f.value
+        if not (rc == _lib.AISX_ERR_OVERFLOW and overflow_ok):
+            check(rc, "pdu_decode_batch.messages")
+        return msg_table(self._cols, self._strs, n.value)

@@ -823,10 +823,13 @@ class ais_rx:
             rx.submit()                          # returns at once; block k is issued when block k + 1 arrives
             while (r := rx.pop()) is not None:   # (block, records, text) of every block that has finished
                 sys.stdout.buffer.write(r[2])
+
+    decode=True queues the ITU-R M.1371 field decoder behind the NMEA stage; pop_messages() then returns (block,
+    records, text, messages) with one MSG_DTYPE row (mmsi, lon, lat, sog, cog, name ...) per record.
     """
 
     def __init__(self, freq, rate, designator, nstreams=1, fmt="cf32", scale=1.0, bias=0.0, block_items=None,
-                 preamble_symbols=None, taps=None, max_pdus_per_block=1 << 16):
+                 preamble_symbols=None, taps=None, max_pdus_per_block=1 << 16, decode=False):
         from .batch_framing import PDU_DTYPE
         from .modulate import gmsk_mod, modulate_vector_bc
 
@@ -872,6 +875,10 @@ class ais_rx:
         self._recs = np.zeros(int(max_pdus_per_block), dtype=PDU_DTYPE)
         self._text = np.zeros(max(tc.value, 1), dtype=np.uint8)
         self.status = 0  # of the block popped last (AISX_MSK_ST_* | AISX_RX_ST_*)
+        self.decode = False
+        self._cols = self._strs = None
+        if decode:
+            self.enable_messages()
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -927,6 +934,35 @@ class ais_rx:
             return None
         self.status = st.value
         return b.value, self._recs[: nr.value].copy(), self._text[: tl.value].tobytes()
+
+    def enable_messages(self):
+        """what decode=True does: from the first block on, the field decoder runs behind the NMEA stage and
+        pop_messages() hands out the table.  ValueError once a slot has been taken or a block pushed."""
+        from .framing import MSG_COLUMNS
+
+        check(_lib.lib().aisx_rx_enable_messages(self._h), "ais_rx.enable_messages")
+        if not self.decode:
+            self._cols = np.zeros((len(MSG_COLUMNS), self._recs.size), dtype=np.int32)
+            self._strs = np.zeros((self._recs.size, _lib.AISX_MSG_STR), dtype=np.uint8)
+        self.decode = True
+
+    def pop_messages(self, wait=False):
+        """pop() plus the block's decoded messages: (block, records, text, messages), messages a MSG_DTYPE array
+        with row i = ais_amd.msg_decode of record i's PDU.  Needs decode=True (ValueError otherwise)."""
+        from .framing import msg_table
+
+        b, tl, nr, st = C.c_longlong(-1), C.c_long(0), C.c_int(0), C.c_int(0)
+        cols = self._cols.ctypes.data_as(C.c_void_p) if self.decode else None
+        strs = self._strs.ctypes.data_as(C.c_void_p) if self.decode else None
+        check(_lib.lib().aisx_rx_pop_messages(self._h, 1 if wait else 0, C.byref(b), self._text.ctypes.data_as(C.c_void_p),
+                                              self._text.size, C.byref(tl), self._recs.ctypes.data_as(C.c_void_p), self._recs.size,
+                                              C.byref(nr), cols, self._cols.shape[1] if self.decode else 0, strs, C.byref(st)),
+              "ais_rx.pop_messages")
+        if b.value < 0:
+            return None
+        self.status = st.value
+        return (b.value, self._recs[: nr.value].copy(), self._text[: tl.value].tobytes(),
+                msg_table(self._cols, self._strs, nr.value))
 
     def set_center_freq(self, f, stream=None, chan=None):
         """from the next submitted block on; stream / chan None = all"""

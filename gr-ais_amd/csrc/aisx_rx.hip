@@ -1,7 +1,8 @@
 // aisx_rx.hip -- C ABI of the host-fed receiver (include/aisx.h, aisx_rx_*): python/radio.py's ais_rx as one handle
 // for nstreams sources, fed from pinned host memory in the source's own sample format.  Nothing here computes: the
-// handle owns the filter (aisx_xlate), the four stage handles and their chain, the deframer and the NMEA stage, and
-// the rings, streams and events that order them (INTEGRATION.md states the rules; this file is their one home).
+// handle owns the filter (aisx_xlate), the four stage handles and their chain, the deframer and the NMEA stage (and,
+// once aisx_rx_enable_messages asked for it, the field decoder behind that), and the rings, streams and events that
+// order them (INTEGRATION.md states the rules; this file is their one home).
 //
 //   block b, submitted:   copy stream    pinned slot b % NPIN -> raw buffer b % NRAW      (after filter b - NRAW)
 //                         filter stream  raw buffer -> row buffer b % NROW                (after wait_input(b - NROW))
@@ -93,6 +94,11 @@ struct aisx_rx {
     aisx_chain* chain = nullptr;
     aisx_hdlc_batch* hd = nullptr;
     aisx_nmea_batch* nm = nullptr;
+    aisx_msg_batch* mg = nullptr;      // only after aisx_rx_enable_messages
+    size_t msg_off = 0;                // of the table in a result slot: int32 cols[AISX_MSG_NCOL][max_pdus], char strs[max_pdus][AISX_MSG_STR]
+    const int32_t* d_mg_cols = nullptr;
+    const char* d_mg_strs = nullptr;
+    const int* d_mg_count = nullptr;
     hipStream_t s_copy = nullptr, s_filt = nullptr, s_tail = nullptr;
     char* h_in[RX_NPIN] = {};          // pinned [ns][block_items] items
     char* d_raw[RX_NRAW] = {};
@@ -143,6 +149,7 @@ extern "C" int aisx_rx_destroy(aisx_rx* h)
     }
     if (h->s_tail)
         (void)hipStreamSynchronize(h->s_tail);
+    (void)aisx_msg_batch_destroy(h->mg);
     (void)aisx_nmea_batch_destroy(h->nm);
     (void)aisx_hdlc_batch_destroy(h->hd);
     (void)aisx_msk_destroy(h->msk);
@@ -385,6 +392,15 @@ static int rx_issue(aisx_rx* h, long long k, const cf* next)
     AISX_HIPCHK(hipMemsetAsync((void*)(h->d_hd_count + 2), 0, sizeof(int), st));
     AISX_HIPCHK(hipMemsetAsync((void*)(h->d_nm_count + 2), 0, sizeof(int), st));
     char* r = h->h_res[res];
+    if (h->mg) { // the rows of the records the NMEA stage kept; its bad-input flag goes into the record's spare word
+        if ((rc = aisx_msg_batch_process(h->mg, h->d_hd_pdus, h->d_hd_bytes, h->d_nm_count + 1, h->d_hd_count, st)) != AISX_OK)
+            return rc;
+        AISX_HIPCHK(hipMemcpyAsync(h->d_meta + 7, h->d_mg_count + 2, sizeof(int), hipMemcpyDeviceToDevice, st));
+        AISX_HIPCHK(hipMemsetAsync((void*)(h->d_mg_count + 2), 0, sizeof(int), st));
+        const size_t cols_bytes = sizeof(int32_t) * AISX_MSG_NCOL * (size_t)h->max_pdus, strs_bytes = (size_t)AISX_MSG_STR * h->max_pdus;
+        AISX_HIPCHK(hipMemcpyAsync(r + h->msg_off, h->d_mg_cols, cols_bytes, hipMemcpyDeviceToHost, st));
+        AISX_HIPCHK(hipMemcpyAsync(r + h->msg_off + cols_bytes, h->d_mg_strs, strs_bytes, hipMemcpyDeviceToHost, st));
+    }
     AISX_HIPCHK(hipMemcpyAsync(r, h->d_meta, sizeof(int) * RX_META, hipMemcpyDeviceToHost, st));
     AISX_HIPCHK(hipMemcpyAsync(r + sizeof(int) * RX_META, h->d_nm_recs, sizeof(aisx_pdu) * (size_t)h->max_pdus, hipMemcpyDeviceToHost, st));
     AISX_HIPCHK(hipMemcpyAsync(r + sizeof(int) * RX_META + sizeof(aisx_pdu) * (size_t)h->max_pdus, h->d_nm_text, (size_t)h->text_cap,
@@ -489,15 +505,12 @@ extern "C" int aisx_rx_flush(aisx_rx* h)
     return rc != AISX_OK ? rx_fail(h, rc) : AISX_OK;
 }
 
-extern "C" int aisx_rx_pop(aisx_rx* h, int wait, long long* block, char* text, long text_cap, long* text_len, aisx_pdu* recs,
-                           int rec_cap, int* nrecs, int* status)
+// aisx_rx_pop, and with cols / strs aisx_rx_pop_messages (the arguments have been checked)
+static int rx_pop(aisx_rx* h, const char* who, int wait, long long* block, char* text, long text_cap, long* text_len, aisx_pdu* recs,
+                  int rec_cap, int* nrecs, int32_t* cols, long col_stride, char* strs, int* status)
 {
-    if (!h || !block || !text_len || !nrecs || text_cap < 0 || rec_cap < 0 || (text_cap > 0 && !text) || (rec_cap > 0 && !recs)) {
-        set_err("aisx_rx_pop: need a handle, outputs for the block number and the counts, and buffers for their capacities");
-        return AISX_ERR_INVALID;
-    }
     if (h->failed != AISX_OK)
-        return rx_failed(h, "aisx_rx_pop");
+        return rx_failed(h, who);
     *block = -1;
     *text_len = 0;
     *nrecs = 0;
@@ -516,7 +529,7 @@ extern "C" int aisx_rx_pop(aisx_rx* h, int wait, long long* block, char* text, l
     } else {
         const hipError_t e = hipEventSynchronize(h->ev_res[res]);
         if (e != hipSuccess) {
-            set_err("aisx_rx_pop: waiting for block %lld failed: %s", h->popped, hipGetErrorString(e));
+            set_err("%s: waiting for block %lld failed: %s", who, h->popped, hipGetErrorString(e));
             return rx_fail(h, AISX_ERR_HIP);
         }
     }
@@ -531,7 +544,7 @@ extern "C" int aisx_rx_pop(aisx_rx* h, int wait, long long* block, char* text, l
     *nrecs = k;
     *text_len = (long)nt;
     if (k > rec_cap || nt > text_cap) {
-        set_err("aisx_rx_pop: block %lld has %d records and %lld bytes of text; the buffers hold %d and %ld", h->popped, k, nt,
+        set_err("%s: block %lld has %d records and %lld bytes of text; the buffers hold %d and %ld", who, h->popped, k, nt,
                 rec_cap, text_cap);
         return AISX_ERR_OVERFLOW;
     }
@@ -539,11 +552,92 @@ extern "C" int aisx_rx_pop(aisx_rx* h, int wait, long long* block, char* text, l
         memcpy(recs, rr, sizeof(aisx_pdu) * (size_t)k);
     if (nt > 0)
         memcpy(text, tt, (size_t)nt);
+    if (cols && k > 0) {
+        const int32_t* cc = (const int32_t*)(r + h->msg_off);
+        for (int c = 0; c < AISX_MSG_NCOL; c++)
+            memcpy(cols + (size_t)c * col_stride, cc + (size_t)c * h->max_pdus, sizeof(int32_t) * (size_t)k);
+        memcpy(strs, r + h->msg_off + sizeof(int32_t) * AISX_MSG_NCOL * (size_t)h->max_pdus, (size_t)AISX_MSG_STR * k);
+    }
     if (status)
         *status = meta[0] | (meta[1] > meta[2] ? AISX_RX_ST_HDLC_OVERFLOW : 0) | (meta[5] < meta[2] ? AISX_RX_ST_NMEA_OVERFLOW : 0) |
-                  ((meta[3] || meta[6]) ? AISX_RX_ST_BAD_COUNT : 0);
+                  ((meta[3] || meta[6] || meta[7]) ? AISX_RX_ST_BAD_COUNT : 0);
     *block = h->popped++;
     return AISX_OK;
+}
+
+extern "C" int aisx_rx_pop(aisx_rx* h, int wait, long long* block, char* text, long text_cap, long* text_len, aisx_pdu* recs,
+                           int rec_cap, int* nrecs, int* status)
+{
+    if (!h || !block || !text_len || !nrecs || text_cap < 0 || rec_cap < 0 || (text_cap > 0 && !text) || (rec_cap > 0 && !recs)) {
+        set_err("aisx_rx_pop: need a handle, outputs for the block number and the counts, and buffers for their capacities");
+        return AISX_ERR_INVALID;
+    }
+    return rx_pop(h, "aisx_rx_pop", wait, block, text, text_cap, text_len, recs, rec_cap, nrecs, nullptr, 0, nullptr, status);
+}
+
+extern "C" int aisx_rx_enable_messages(aisx_rx* h)
+{
+    if (!h) {
+        set_err("aisx_rx_enable_messages: need a handle");
+        return AISX_ERR_INVALID;
+    }
+    if (h->failed != AISX_OK)
+        return rx_failed(h, "aisx_rx_enable_messages");
+    if (h->mg)
+        return AISX_OK;
+    if (h->acquired || h->submitted > 0) {
+        set_err("aisx_rx_enable_messages: only before the first acquire, submit or push");
+        return AISX_ERR_INVALID;
+    }
+    OnDevice on(h->dev);
+    AISX_HIPCHK(on.err);
+    // the result slots grow by the table: nothing is in flight yet, so they are simply made again
+    const size_t msg_off = (h->res_bytes + 15) & ~(size_t)15;
+    const size_t bytes = msg_off + (sizeof(int32_t) * AISX_MSG_NCOL + AISX_MSG_STR) * (size_t)h->max_pdus;
+    char* slots[RX_NRES] = {};
+    aisx_msg_batch* mg = nullptr;
+    int rc = aisx_msg_batch_create(&mg, h->ns * h->nch, h->max_pdus, RX_LMAX);
+    for (int i = 0; rc == AISX_OK && i < RX_NRES; i++)
+        if (hipHostMalloc((void**)&slots[i], bytes) != hipSuccess) {
+            set_err("aisx_rx_enable_messages: %zu bytes of pinned memory for result slot %d could not be had", bytes, i);
+            rc = AISX_ERR_HIP;
+        }
+    if (rc == AISX_OK)
+        rc = aisx_msg_batch_results_device(mg, &h->d_mg_cols, nullptr, &h->d_mg_strs, &h->d_mg_count);
+    if (rc != AISX_OK) { // (the handle stays as it was)
+        const std::string msg = aisx_last_error();
+        for (char* p : slots)
+            if (p)
+                (void)hipHostFree(p);
+        (void)aisx_msg_batch_destroy(mg);
+        set_err("%s", msg.c_str());
+        return rc;
+    }
+    for (int i = 0; i < RX_NRES; i++) {
+        (void)hipHostFree(h->h_res[i]);
+        h->h_res[i] = slots[i];
+    }
+    h->msg_off = msg_off;
+    h->res_bytes = bytes;
+    h->mg = mg;
+    return AISX_OK;
+}
+
+extern "C" int aisx_rx_pop_messages(aisx_rx* h, int wait, long long* block, char* text, long text_cap, long* text_len, aisx_pdu* recs,
+                                    int rec_cap, int* nrecs, int32_t* cols, long col_stride, char* strs, int* status)
+{
+    if (h && !h->mg) {
+        set_err("aisx_rx_pop_messages: aisx_rx_enable_messages was not called on this handle");
+        return AISX_ERR_INVALID;
+    }
+    if (!h || !block || !text_len || !nrecs || text_cap < 0 || rec_cap < 0 || (text_cap > 0 && !text) || (rec_cap > 0 && !recs) ||
+        (rec_cap > 0 && (!cols || !strs)) || col_stride < rec_cap) {
+        set_err("aisx_rx_pop_messages: need a handle, outputs for the block number and the counts, buffers for their "
+                "capacities and a table of rec_cap rows (col_stride >= rec_cap)");
+        return AISX_ERR_INVALID;
+    }
+    return rx_pop(h, "aisx_rx_pop_messages", wait, block, text, text_cap, text_len, recs, rec_cap, nrecs, rec_cap > 0 ? cols : nullptr,
+                  col_stride, strs, status);
 }
 
 extern "C" int aisx_rx_set_center_freq(aisx_rx* h, int stream, int chan, double center_freq)

@@ -624,6 +624,66 @@ int aisx_nmea_batch_read(aisx_nmea_batch* h, aisx_pdu* recs, int rec_cap, char* 
                          int* nfound, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* ITU-R M.1371 message fields: one PDU on the host (the specification), and  */
+/* every record of a device PDU list at once, queued behind the deframer      */
+/* ------------------------------------------------------------------------ */
+/* Columns of a decoded message.  Values are the transmitted integers (no scaling: longitude and latitude in 1/10000
+ * minute, speed in 1/10 knot, course in 1/10 degree ...; type 27's coarser position, speed and course are brought to
+ * these class-A units by exact integer multiplication).  A column the message's type does not carry, or whose bits
+ * the payload does not hold entirely, is AISX_MSG_NA. */
+enum {
+    AISX_MSG_COL_TYPE = 0, AISX_MSG_COL_REPEAT, AISX_MSG_COL_MMSI, AISX_MSG_COL_FLAGS, AISX_MSG_COL_NAV_STATUS,
+    AISX_MSG_COL_ROT, AISX_MSG_COL_SOG, AISX_MSG_COL_ACCURACY, AISX_MSG_COL_LON, AISX_MSG_COL_LAT, AISX_MSG_COL_COG,
+    AISX_MSG_COL_HEADING, AISX_MSG_COL_SECOND, AISX_MSG_COL_MANEUVER, AISX_MSG_COL_RAIM, AISX_MSG_COL_RADIO,
+    AISX_MSG_COL_IMO, AISX_MSG_COL_AIS_VERSION, AISX_MSG_COL_SHIPTYPE, AISX_MSG_COL_TO_BOW, AISX_MSG_COL_TO_STERN,
+    AISX_MSG_COL_TO_PORT, AISX_MSG_COL_TO_STARBOARD, AISX_MSG_COL_EPFD, AISX_MSG_COL_YEAR, AISX_MSG_COL_MONTH,
+    AISX_MSG_COL_DAY, AISX_MSG_COL_HOUR, AISX_MSG_COL_MINUTE, AISX_MSG_COL_DRAUGHT, AISX_MSG_COL_DTE, AISX_MSG_COL_PART,
+    AISX_MSG_COL_AID_TYPE, AISX_MSG_COL_OFF_POSITION, AISX_MSG_COL_VIRTUAL_AID, AISX_MSG_COL_ASSIGNED,
+    AISX_MSG_COL_CS_FLAGS, /* type 18's bits 141 .. 146 as one value: cs, display, dsc, band, msg22, assigned */
+    AISX_MSG_NCOL
+};
+#define AISX_MSG_NA (-2147483647 - 1)
+/* bits of the FLAGS column, which every row carries */
+enum {
+    AISX_MSG_FL_COMPLETE = 1,  /* the payload holds the type's whole minimum length (38 bits for a type without a layout) */
+    AISX_MSG_FL_NO_LAYOUT = 2, /* only TYPE, REPEAT and MMSI are decoded: types 6-10, 12-17, 20, 22, 23, 25, 26, 0, 28-63 */
+    AISX_MSG_FL_BAD_RECORD = 4 /* device lists only: chan or len out of range; nothing was read, every other column is NA */
+};
+/* a row's strings, six-bit characters as bytes ('@' for 0, nothing stripped); a slot the message does not carry, or
+ * does not hold entirely, is all NUL: [0, 7) call sign, [7] NUL, [8, 28) name, [28, 48) destination */
+#define AISX_MSG_STR 48
+/* Message bit i is bit 7 - i % 8 of pdu[i / 8] (the bits aisx_pdu_to_nmea's payload characters are made of).  Types
+ * 1-3, 4, 5, 11, 18, 19, 21 (without the name extension), 24 (parts A and B, without the vendor id) and 27 are decoded
+ * field by field (csrc/aisx_msgtab.h holds the layouts).  cols [AISX_MSG_NCOL], strs [AISX_MSG_STR].  Plain C++, no
+ * device.  AISX_ERR_INVALID for len < 0 or a missing pointer. */
+int aisx_msg_decode(const uint8_t* pdu, int len, int32_t* cols, char* strs);
+
+typedef struct aisx_msg_batch aisx_msg_batch;
+/* at most max_pdus records per call on nchan channels, of at most length_max - 1 payload octets (2 <= length_max <=
+ * 1024, as the deframer's).  The handle owns int32_t cols[AISX_MSG_NCOL][max_pdus] and char strs[max_pdus][AISX_MSG_STR]
+ * on the device that was current here. */
+int aisx_msg_batch_create(aisx_msg_batch** h, int nchan, int max_pdus, int length_max);
+int aisx_msg_batch_destroy(aisx_msg_batch* h);
+/* d_pdus / d_bytes / d_npdus / d_nfound as aisx_nmea_batch_process takes them (record offsets into d_bytes need be
+ * neither ordered nor contiguous).  Queued on `stream`; no host sync.  Row i of the table is aisx_msg_decode of
+ * record i's payload (its chan and end_bit stay in the input list); a record whose chan is outside [0, nchan) or whose
+ * len is outside [0, length_max - 1] gets FLAGS = AISX_MSG_FL_BAD_RECORD, NA columns and NUL strings without a payload
+ * byte being read, and makes the next read say so; a count outside [0, max_pdus] writes no rows and does the same. */
+int aisx_msg_batch_process(aisx_msg_batch* h, const aisx_pdu* d_pdus, const uint8_t* d_bytes, const int* d_npdus,
+                           const int* d_nfound, void* stream);
+/* the last call's table in device memory: column c is d_cols + c * *col_stride (*col_stride = max_pdus), row i's
+ * strings d_strs + i * AISX_MSG_STR; d_count[0] = PDUs found (the producer's count, else the record count),
+ * d_count[1] = rows written, d_count[2] != 0 after bad input */
+int aisx_msg_batch_results_device(const aisx_msg_batch* h, const int32_t** d_cols, long* col_stride, const char** d_strs,
+                                  const int** d_count);
+/* copies the first min(rows written, cap) rows to the host (synchronises `stream`): cols [AISX_MSG_NCOL][col_stride]
+ * with col_stride >= cap, strs [cap][AISX_MSG_STR]; *nrecs = rows copied, *nfound (may be NULL) as d_count[0].
+ * AISX_ERR_OVERFLOW when fewer rows were copied than *nfound, AISX_ERR_INVALID when a call since the previous read met
+ * bad input (the flag is then cleared). */
+int aisx_msg_batch_read(aisx_msg_batch* h, int32_t* cols, long col_stride, char* strs, int cap, int* nrecs, int* nfound,
+                        void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* ais_rx (python/radio.py:40-73) as ONE handle, fed from host memory in the  */
 /* source's own sample format: freq_xlating_fir_filter_ccf -> ais_demod ->    */
 /* hdlc_deframer_bp -> pdu_to_nmea for nstreams sources at once               */
@@ -680,6 +740,15 @@ int aisx_rx_flush(aisx_rx* h);
  * buffers are too small: AISX_ERR_OVERFLOW with *nrecs / *text_len = what is needed, and the block stays. */
 int aisx_rx_pop(aisx_rx* h, int wait, long long* block, char* text, long text_cap, long* text_len, aisx_pdu* recs,
                 int rec_cap, int* nrecs, int* status);
+/* Opt-in: from the first block on, the tail stream queues the field decoder (aisx_msg_batch_*) behind the NMEA stage
+ * and every result slot also carries the kept records' table.  Only before the first acquire, submit or push
+ * (AISX_ERR_INVALID afterwards); a handle on which this was never called allocates, queues and copies nothing more. */
+int aisx_rx_enable_messages(aisx_rx* h);
+/* aisx_rx_pop plus the block's table: cols [AISX_MSG_NCOL][col_stride] (col_stride >= rec_cap), strs
+ * [rec_cap][AISX_MSG_STR], row i for record i.  The same waiting and overflow rules (the table needs rec_cap rows).
+ * AISX_ERR_INVALID on a handle without messages enabled. */
+int aisx_rx_pop_messages(aisx_rx* h, int wait, long long* block, char* text, long text_cap, long* text_len, aisx_pdu* recs,
+                         int rec_cap, int* nrecs, int32_t* cols, long col_stride, char* strs, int* status);
 /* from the next submitted block on (aisx_xlate_set_center_freq of the handle's filter) */
 int aisx_rx_set_center_freq(aisx_rx* h, int stream, int chan, double center_freq);
 /* A failed block (a HIP error, the chain refusing) makes every later call but destroy return that block's error. */
