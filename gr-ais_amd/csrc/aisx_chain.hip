@@ -20,20 +20,21 @@ struct aisx_chain {
     int nchan = 0, max_items = 0, fftlen = 0;
     int serial = 0; // AISX_CHAIN_SERIAL: every stage on s_main (A/B runs)
     // streams: sample passes | timing recovery | its bit tail | NCO phase walk one step ahead
-    hipStream_t s_main = nullptr, s_msk = nullptr, s_tail = nullptr, s_walk = nullptr;
+    // (declared before the buffers and events used on them: destroyed after those)
+    Stream s_main, s_msk, s_tail, s_walk;
     long long corr_calls = 0;          // aisx_corr_process calls made so far
     long long corr_call_of[8] = { 0 }; // [step % NBUF]: corr_calls behind that step's call, 0 for a step without one
     bool failed = false;               // a step failed half way: see aisx_chain_step
     int msk_cus = 0; // compute units set aside for the timing recovery's stream (0: streams share the chip)
     static constexpr int NBUF = AISX_CHAIN_DEPTH;
-    cf* d_y = nullptr; // front-end output (stock chain): one buffer, written and read on s_main
+    DevBuf<cf> d_y; // front-end output (stock chain): one buffer, written and read on s_main
     long y_stride = 0;
-    cf* d_yc[NBUF] = {}; // corr_est's delayed output, read by the recovery of the same step on s_msk
+    DevBuf<cf> d_yc[NBUF]; // corr_est's delayed output, read by the recovery of the same step on s_msk
     long yc_stride = 0;
-    hipEvent_t ev_in = nullptr;
-    hipEvent_t ev_ready[NBUF] = {};    // s_main: the step's sample passes and tags are done (its input is free)
-    hipEvent_t ev_msk_done[NBUF] = {}; // s_msk: the step's recovery has read d_yc[par] and its tags
-    hipEvent_t ev_done[NBUF] = {};     // the step's outputs are complete (bit tail included)
+    Event ev_in;
+    Event ev_ready[NBUF];    // s_main: the step's sample passes and tags are done (its input is free)
+    Event ev_msk_done[NBUF]; // s_msk: the step's recovery has read d_yc[par] and its tags
+    Event ev_done[NBUF];     // the step's outputs are complete (bit tail included)
     long long nsteps = 0;
     int m_of[NBUF] = {}; // items the correlator wrote per row in the step that owns d_yc[k]
     int npend = 0; // items the front end holds back (n % fftlen arithmetic of stream_to_vector)
@@ -43,32 +44,22 @@ struct aisx_chain {
     int ahead_n = 0;
 };
 
-static void chain_free(aisx_chain* h)
+// the borrowed handles go back as they came, the streams come to rest; then everything the chain owns is released
+extern "C" int aisx_chain_destroy(aisx_chain* h)
 {
     if (!h)
-        return;
+        return AISX_OK;
     if (h->msk)
         (void)aisx_msk_set_tail_stream(h->msk, nullptr, 0);
-    if (h->agc && h->agc_claim_prev >= 0) // (the placement claims are the chain's: the handles go back as they came)
+    if (h->agc && h->agc_claim_prev >= 0) // (the placement claims are the chain's)
         (void)aisx_agc_set_lds_claim(h->agc, h->agc_claim_prev);
     if (h->fs && h->walk_claim_prev >= 0)
         (void)aisx_freqsync_set_walk_lds_claim(h->fs, h->walk_claim_prev);
-    for (hipStream_t s : { h->s_main, h->s_msk, h->s_tail, h->s_walk })
-        if (s)
-            (void)hipStreamSynchronize(s);
-    dev_free(h->d_y);
-    for (int k = 0; k < aisx_chain::NBUF; k++) {
-        dev_free(h->d_yc[k]);
-        for (hipEvent_t e : { h->ev_ready[k], h->ev_msk_done[k], h->ev_done[k] })
-            if (e)
-                (void)hipEventDestroy(e);
-    }
-    if (h->ev_in)
-        (void)hipEventDestroy(h->ev_in);
-    for (hipStream_t s : { h->s_main, h->s_msk, h->s_tail, h->s_walk })
-        if (s)
-            (void)hipStreamDestroy(s);
+    for (const Stream* s : { &h->s_main, &h->s_msk, &h->s_tail, &h->s_walk })
+        if (*s)
+            (void)hipStreamSynchronize(*s);
     delete h;
+    return AISX_OK;
 }
 
 // The LDS a front-end (k_agcw) workgroup claims beyond the `used` bytes it needs: how many of them the dispatcher can put
@@ -158,7 +149,7 @@ extern "C" int aisx_chain_create(aisx_chain** out, aisx_freqsync* fs, aisx_agc* 
             return AISX_ERR_INVALID;
         }
     }
-    aisx_chain* h = new aisx_chain();
+    HandlePtr<aisx_chain, aisx_chain_destroy> h(new aisx_chain());
     h->fs = fs;
     h->agc = agc;
     h->corr = corr;
@@ -168,23 +159,14 @@ extern "C" int aisx_chain_create(aisx_chain** out, aisx_freqsync* fs, aisx_agc* 
     h->fftlen = fs ? fftlen : 0;
     if (const char* e = exp_env("AISX_CHAIN_SERIAL"))
         h->serial = atoi(e) != 0;
-#define CKH(e)                                                                                     \
-    do {                                                                                           \
-        hipError_t e__ = (e);                                                                      \
-        if (e__ != hipSuccess) {                                                                   \
-            set_err("aisx_chain_create: %s failed: %s", #e, hipGetErrorString(e__));               \
-            chain_free(h);                                                                         \
-            return AISX_ERR_HIP;                                                                   \
-        }                                                                                          \
-    } while (0)
     {
         // AISX_CHAIN_MSK_CUS = N: the timing recovery's stream owns N compute units (CU-mask bits [0, N): the
         // driver deals mask bits round the XCDs, so N / 8 CUs in each), the other streams the remaining ones
         int ncu = 0, msk_cus = 0, walk_with_msk = 0, tail_with_msk = 0;
         hipDeviceProp_t prop;
         int dev = 0;
-        CKH(hipGetDevice(&dev));
-        CKH(hipGetDeviceProperties(&prop, dev));
+        AISX_HIPCHK(hipGetDevice(&dev));
+        AISX_HIPCHK(hipGetDeviceProperties(&prop, dev));
         ncu = prop.multiProcessorCount;
         if (const char* e = exp_env("AISX_CHAIN_MSK_CUS"))
             msk_cus = atoi(e);
@@ -194,39 +176,37 @@ extern "C" int aisx_chain_create(aisx_chain** out, aisx_freqsync* fs, aisx_agc* 
             tail_with_msk = atoi(e);
         if (h->serial || msk_cus < 0 || msk_cus >= ncu)
             msk_cus = 0;
-        auto make = [&](hipStream_t* s, int lo, int hi) -> hipError_t {
+        auto make = [&](Stream& s, int lo, int hi) -> int {
             if (msk_cus == 0)
-                return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+                return s.create_nonblocking();
             std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
             for (int b = lo; b < hi; b++)
                 mask[(size_t)b / 32] |= 1u << (b % 32);
-            return hipExtStreamCreateWithCUMask(s, (uint32_t)mask.size(), mask.data());
+            hipStream_t raw = nullptr;
+            AISX_HIPCHK(hipExtStreamCreateWithCUMask(&raw, (uint32_t)mask.size(), mask.data()));
+            s.adopt(raw);
+            return AISX_OK;
         };
-        CKH(make(&h->s_main, msk_cus, ncu));
-        CKH(make(&h->s_msk, 0, msk_cus));
-        CKH(tail_with_msk ? make(&h->s_tail, 0, msk_cus) : make(&h->s_tail, msk_cus, ncu));
-        CKH(walk_with_msk ? make(&h->s_walk, 0, msk_cus) : make(&h->s_walk, msk_cus, ncu));
+        if ((rc = make(h->s_main, msk_cus, ncu)) != AISX_OK || (rc = make(h->s_msk, 0, msk_cus)) != AISX_OK ||
+            (rc = tail_with_msk ? make(h->s_tail, 0, msk_cus) : make(h->s_tail, msk_cus, ncu)) != AISX_OK ||
+            (rc = walk_with_msk ? make(h->s_walk, 0, msk_cus) : make(h->s_walk, msk_cus, ncu)) != AISX_OK)
+            return rc;
         h->msk_cus = msk_cus;
     }
-    CKH(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
-    for (int k = 0; k < aisx_chain::NBUF; k++) {
-        CKH(hipEventCreateWithFlags(&h->ev_ready[k], hipEventDisableTiming));
-        CKH(hipEventCreateWithFlags(&h->ev_msk_done[k], hipEventDisableTiming));
-        CKH(hipEventCreateWithFlags(&h->ev_done[k], hipEventDisableTiming));
-    }
-#undef CKH
+    if ((rc = h->ev_in.create(hipEventDisableTiming)) != AISX_OK)
+        return rc;
+    for (int k = 0; k < aisx_chain::NBUF; k++)
+        if ((rc = h->ev_ready[k].create(hipEventDisableTiming)) != AISX_OK || (rc = h->ev_msk_done[k].create(hipEventDisableTiming)) != AISX_OK ||
+            (rc = h->ev_done[k].create(hipEventDisableTiming)) != AISX_OK)
+            return rc;
     // a step's front end emits every complete fftlen-vector of (pending + new) items
     const long cap = (long)max_items + h->fftlen;
     h->y_stride = h->yc_stride = (cap + 1) & ~1L; // rows 16-byte aligned
-    if (fs && (rc = dev_alloc(&h->d_y, (size_t)nchan * h->y_stride, false)) != AISX_OK) {
-        chain_free(h);
+    if (fs && (rc = h->d_y.alloc((size_t)nchan * h->y_stride, false)) != AISX_OK)
         return rc;
-    }
     for (int k = 0; k < aisx_chain::NBUF; k++)
-        if ((rc = dev_alloc(&h->d_yc[k], (size_t)nchan * h->yc_stride, false)) != AISX_OK) {
-            chain_free(h);
+        if ((rc = h->d_yc[k].alloc((size_t)nchan * h->yc_stride, false)) != AISX_OK)
             return rc;
-        }
     // What the part offers and what the recovery kernel's launch takes of it: the two placement decisions below follow.
     int ncu = 0, lds_cu = 0, msk_wgs = 0, msk_lds = 0;
     {
@@ -252,10 +232,8 @@ extern "C" int aisx_chain_create(aisx_chain** out, aisx_freqsync* fs, aisx_agc* 
             claim = v < 0 ? 0 : (v > 144 * 1024 ? 144 * 1024 : v);
         }
         h->agc_claim_prev = prev;
-        if ((rc = aisx_agc_set_lds_claim(agc, claim)) != AISX_OK) {
-            chain_free(h);
+        if ((rc = aisx_agc_set_lds_claim(agc, claim)) != AISX_OK)
             return rc;
-        }
         // The phase walk's one-wave workgroups (3 KB) likewise, while the recovery leaves half of the CUs free: one of them
         // beside a recovery workgroup delays its recurrence and takes the LDS the correlator's workgroup would have had
         // there (4096 channels: the step 5.43-5.47 against 5.47-5.53 ms, the correlator 1.45-1.47 against 1.52-1.54).
@@ -265,10 +243,8 @@ extern "C" int aisx_chain_create(aisx_chain** out, aisx_freqsync* fs, aisx_agc* 
             (void)aisx_freqsync_get_walk_lds_claim(fs, &wprev, &wused);
             const int wclaim = chain_front_claim(ncu, lds_cu, msk_wgs, msk_lds, wused);
             h->walk_claim_prev = wprev;
-            if ((rc = aisx_freqsync_set_walk_lds_claim(fs, wclaim)) != AISX_OK) {
-                chain_free(h);
+            if ((rc = aisx_freqsync_set_walk_lds_claim(fs, wclaim)) != AISX_OK)
                 return rc;
-            }
         }
     }
     if (!h->serial) {
@@ -278,18 +254,10 @@ extern "C" int aisx_chain_create(aisx_chain** out, aisx_freqsync* fs, aisx_agc* 
         if (const char* e = exp_env("AISX_MSK_HEADSTART_US"))
             us = atoi(e);
         if ((rc = aisx_msk_set_tail_stream(msk, h->s_tail, 1)) != AISX_OK || (rc = aisx_msk_set_head_start(msk, us < 0 ? 0 : us)) != AISX_OK ||
-            (rc = aisx_msk_wait_prepass(msk, h->s_main)) != AISX_OK) {
-            chain_free(h);
+            (rc = aisx_msk_wait_prepass(msk, h->s_main)) != AISX_OK)
             return rc;
-        }
     }
-    *out = h;
-    return AISX_OK;
-}
-
-extern "C" int aisx_chain_destroy(aisx_chain* h)
-{
-    chain_free(h);
+    *out = h.release();
     return AISX_OK;
 }
 
@@ -369,7 +337,7 @@ static int chain_step_issue(aisx_chain* h, const aisx_cf32* d_in, long in_stride
                 return rc;
         }
         int nout = 0;
-        if ((rc = aisx_freqsync_agc_process(h->fs, h->agc, d_in, in_stride, n, (aisx_cf32*)h->d_y, h->y_stride, nullptr, 0, &nout,
+        if ((rc = aisx_freqsync_agc_process(h->fs, h->agc, d_in, in_stride, n, (aisx_cf32*)h->d_y.get(), h->y_stride, nullptr, 0, &nout,
                                             sm)) != AISX_OK)
             return rc;
         h->npend = h->npend + n - nout;
@@ -397,7 +365,7 @@ static int chain_step_issue(aisx_chain* h, const aisx_cf32* d_in, long in_stride
         AISX_HIPCHK(hipEventRecord(h->ev_msk_done[par], sm));
         AISX_HIPCHK(hipEventRecord(h->ev_done[par], sm));
     } else {
-        if ((rc = aisx_corr_process(h->corr, (const aisx_cf32*)y, ys, (aisx_cf32*)h->d_yc[par], h->yc_stride, nullptr, 0, m, sm)) != AISX_OK)
+        if ((rc = aisx_corr_process(h->corr, (const aisx_cf32*)y, ys, (aisx_cf32*)h->d_yc[par].get(), h->yc_stride, nullptr, 0, m, sm)) != AISX_OK)
             return rc;
         h->corr_call_of[par] = ++h->corr_calls;
         const aisx_tag* tags = nullptr;
@@ -410,7 +378,7 @@ static int chain_step_issue(aisx_chain* h, const aisx_cf32* d_in, long in_stride
             AISX_HIPCHK(hipStreamWaitEvent(sk, h->ev_ready[par], 0));
         // (ev_ready: what the time-parallel recovery's units wait for on their own stream -- they need this
         // step's samples and tags, not the previous step's recovery, and run beside it)
-        if ((rc = aisx_msk_process_stream_after(h->msk, (const aisx_cf32*)h->d_yc[par], h->yc_stride, m, tags, counts, tcap, d_syms,
+        if ((rc = aisx_msk_process_stream_after(h->msk, (const aisx_cf32*)h->d_yc[par].get(), h->yc_stride, m, tags, counts, tcap, d_syms,
                                                 nullptr, nullptr, d_bits, out_stride, d_produced, sk,
                                                 h->serial ? nullptr : (void*)h->ev_ready[par])) != AISX_OK)
             return rc;
@@ -429,7 +397,7 @@ static int chain_step_issue(aisx_chain* h, const aisx_cf32* d_in, long in_stride
     return AISX_OK;
 }
 
-static int chain_wait_event(aisx_chain* h, long long step, void* stream, bool have_stream, hipEvent_t* evs, const char* what)
+static int chain_wait_event(aisx_chain* h, long long step, void* stream, bool have_stream, const Event* evs, const char* what)
 {
     if (!h || step < 0 || step >= h->nsteps) {
         set_err("%s: step %lld has not been issued", what, step);
@@ -498,8 +466,8 @@ extern "C" int aisx_chain_synchronize(aisx_chain* h)
 {
     if (!h)
         return AISX_ERR_INVALID;
-    for (hipStream_t s : { h->s_main, h->s_walk, h->s_msk, h->s_tail })
-        AISX_HIPCHK(hipStreamSynchronize(s));
+    for (const Stream* s : { &h->s_main, &h->s_walk, &h->s_msk, &h->s_tail })
+        AISX_HIPCHK(hipStreamSynchronize(*s));
     return AISX_OK;
 }
 

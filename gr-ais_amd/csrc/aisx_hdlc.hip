@@ -38,16 +38,16 @@ struct aisx_hdlc_batch {
     int lmin = 0, lmax = 0, nchan = 0, max_bits = 0, max_pdus = 0;
     int carry_words = 0, rec_cap = 0, byte_cap = 0;
     long long out_bytes_cap = 0;
-    HdlcState* d_st = nullptr;
-    unsigned long long* d_carry = nullptr;
-    HdlcRec* d_srec = nullptr;
-    unsigned char* d_sbytes = nullptr;
-    int* d_cnt = nullptr;   // [nchan] records, [nchan] bytes
-    long long* d_base = nullptr; // [nchan] record bases, [nchan] byte bases
-    int* d_count = nullptr; // [0] found, [1] kept, [2] bad-count flag
-    hipEvent_t done = nullptr; // behind the last call's work (reset waits for it)
-    HdlcRec* d_out = nullptr;
-    unsigned char* d_out_bytes = nullptr;
+    DevBuf<HdlcState> d_st;
+    DevBuf<unsigned long long> d_carry;
+    DevBuf<HdlcRec> d_srec;
+    DevBuf<unsigned char> d_sbytes;
+    DevBuf<int> d_cnt;         // [nchan] records, [nchan] bytes
+    DevBuf<long long> d_base;  // [nchan] record bases, [nchan] byte bases
+    DevBuf<int> d_count;       // [0] found, [1] kept, [2] bad-count flag
+    Event done;                // behind the last call's work (reset waits for it)
+    DevBuf<HdlcRec> d_out;
+    DevBuf<unsigned char> d_out_bytes;
 };
 
 extern "C" int aisx_hdlc_batch_destroy(aisx_hdlc_batch* h)
@@ -55,17 +55,6 @@ extern "C" int aisx_hdlc_batch_destroy(aisx_hdlc_batch* h)
     if (!h)
         return AISX_OK;
     OnDevice on(h->dev);
-    dev_free(h->d_st);
-    dev_free(h->d_carry);
-    dev_free(h->d_srec);
-    dev_free(h->d_sbytes);
-    dev_free(h->d_cnt);
-    dev_free(h->d_base);
-    dev_free(h->d_count);
-    dev_free(h->d_out);
-    dev_free(h->d_out_bytes);
-    if (h->done)
-        (void)hipEventDestroy(h->done);
     delete h;
     return AISX_OK;
 }
@@ -85,12 +74,8 @@ extern "C" int aisx_hdlc_batch_create(aisx_hdlc_batch** out, int length_min, int
     int rc = require_device();
     if (rc != AISX_OK)
         return rc;
-    aisx_hdlc_batch* h = new aisx_hdlc_batch();
-    if (hipGetDevice(&h->dev) != hipSuccess) {
-        delete h;
-        set_err("aisx_hdlc_batch_create: hipGetDevice failed");
-        return AISX_ERR_HIP;
-    }
+    HandlePtr<aisx_hdlc_batch, aisx_hdlc_batch_destroy> h(new aisx_hdlc_batch());
+    AISX_HIPCHK(hipGetDevice(&h->dev));
     h->lmin = length_min;
     h->lmax = length_max;
     h->nchan = nchan;
@@ -103,23 +88,14 @@ extern "C" int aisx_hdlc_batch_create(aisx_hdlc_batch** out, int length_min, int
     h->rec_cap = (int)(span / (8LL * length_min + 1) + 2);
     h->byte_cap = (int)(span / 8 + 8);
     h->out_bytes_cap = (long long)max_pdus * (length_max - 1); // (a payload is at most length_max - 1 octets)
-    if ((rc = dev_alloc(&h->d_st, (size_t)nchan)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_carry, (size_t)nchan * h->carry_words)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_srec, (size_t)nchan * h->rec_cap, false)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_sbytes, (size_t)nchan * h->byte_cap, false)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_cnt, 2 * (size_t)nchan)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_base, 2 * (size_t)nchan)) != AISX_OK || (rc = dev_alloc(&h->d_count, 4)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_out, (size_t)max_pdus)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_out_bytes, (size_t)h->out_bytes_cap)) != AISX_OK) {
-        aisx_hdlc_batch_destroy(h);
+    if ((rc = h->d_st.alloc((size_t)nchan)) != AISX_OK || (rc = h->d_carry.alloc((size_t)nchan * h->carry_words)) != AISX_OK ||
+        (rc = h->d_srec.alloc((size_t)nchan * h->rec_cap, false)) != AISX_OK ||
+        (rc = h->d_sbytes.alloc((size_t)nchan * h->byte_cap, false)) != AISX_OK || (rc = h->d_cnt.alloc(2 * (size_t)nchan)) != AISX_OK ||
+        (rc = h->d_base.alloc(2 * (size_t)nchan)) != AISX_OK || (rc = h->d_count.alloc(4)) != AISX_OK ||
+        (rc = h->d_out.alloc((size_t)max_pdus)) != AISX_OK || (rc = h->d_out_bytes.alloc((size_t)h->out_bytes_cap)) != AISX_OK ||
+        (rc = h->done.create(hipEventDisableTiming)) != AISX_OK)
         return rc;
-    }
-    if (hipEventCreateWithFlags(&h->done, hipEventDisableTiming) != hipSuccess) {
-        set_err("aisx_hdlc_batch_create: hipEventCreateWithFlags failed");
-        aisx_hdlc_batch_destroy(h);
-        return AISX_ERR_HIP;
-    }
-    *out = h;
+    *out = h.release();
     return AISX_OK;
 }
 
@@ -202,7 +178,7 @@ extern "C" int aisx_hdlc_batch_results_device(const aisx_hdlc_batch* h, const ai
     if (!h)
         return AISX_ERR_INVALID;
     if (d_pdus)
-        *d_pdus = (const aisx_pdu*)h->d_out;
+        *d_pdus = (const aisx_pdu*)h->d_out.get();
     if (d_bytes)
         *d_bytes = h->d_out_bytes;
     if (d_count)

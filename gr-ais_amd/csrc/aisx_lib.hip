@@ -12,7 +12,6 @@
 #include "aisx_plan.h"
 #include "aisx_tables.h"
 #include "k_corr.h"
-#include <cstdlib>
 
 using namespace aisx;
 
@@ -244,21 +243,12 @@ extern "C" int aisx_util_copy_GBs(size_t bytes, int iters, float* GBs)
     if (rc != AISX_OK)
         return rc;
     const size_t n = bytes / 16;
-    copy_v4 *a = nullptr, *b = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto done = [&](int r) {
-        dev_free(a);
-        dev_free(b);
-        if (e0)
-            (void)hipEventDestroy(e0);
-        if (e1)
-            (void)hipEventDestroy(e1);
-        return r;
-    };
-    if ((rc = dev_alloc(&a, n)) != AISX_OK || (rc = dev_alloc(&b, n, false)) != AISX_OK)
-        return done(rc);
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
-        return done(AISX_ERR_HIP);
+    DevBuf<copy_v4> abuf, bbuf;
+    Event e0, e1;
+    if ((rc = abuf.alloc(n)) != AISX_OK || (rc = bbuf.alloc(n, false)) != AISX_OK ||
+        (rc = e0.create(hipEventDefault)) != AISX_OK || (rc = e1.create(hipEventDefault)) != AISX_OK)
+        return rc;
+    copy_v4 *const a = abuf, *const b = bbuf;
     // several launch shapes; the best one is the figure (bytes read + bytes written per second)
     float best = 0.f;
     for (int mode = 0; mode < 3; mode++)
@@ -274,18 +264,18 @@ extern "C" int aisx_util_copy_GBs(size_t bytes, int iters, float* GBs)
             };
             launch();
             if (hipEventRecord(e0, 0) != hipSuccess)
-                return done(AISX_ERR_HIP);
+                return AISX_ERR_HIP;
             for (int k = 0; k < iters; k++)
                 launch();
             float ms = 0.f;
             if (hipEventRecord(e1, 0) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
                 hipEventElapsedTime(&ms, e0, e1) != hipSuccess || !(ms > 0.f))
-                return done(AISX_ERR_HIP);
+                return AISX_ERR_HIP;
             const float g = (float)(2.0 * (double)(n * 16) * iters / (ms * 1e-3) / 1e9);
             best = g > best ? g : best;
         }
     *GBs = best;
-    return done(AISX_OK);
+    return AISX_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -314,32 +304,28 @@ struct aisx_corr {
     float sps = 0, thresh = 0;
     unsigned mark_delay = 0;
     std::vector<cf> symbols; // d_symbols
-    cf *d_taps = nullptr, *d_tapspad = nullptr, *d_Hpos = nullptr, *d_wtab = nullptr;
-    cf* d_hist[2] = { nullptr, nullptr };
+    DevBuf<cf> d_taps, d_tapspad, d_Hpos, d_wtab;
+    DevBuf<cf> d_hist[2];
     int hist_cur = 0;
-    unsigned long long* d_abits = nullptr;
+    DevBuf<unsigned long long> d_abits;
     long abits_stride = 0;
-    cf* d_scratch = nullptr;
+    DevBuf<cf> d_scratch;
     long scratch_stride = 0;
     // tags rotate through three buffers so that a consumer on another stream (the
     // timing-recovery stage) can still read call k's tags while calls k+1 and k+2 run
     static constexpr int NTAGBUF = 3;
-    tag_rec* d_tags2[NTAGBUF] = { nullptr, nullptr, nullptr };
-    int* d_tag_count2[NTAGBUF] = { nullptr, nullptr, nullptr };
+    DevBuf<tag_rec> d_tags2[NTAGBUF];
+    DevBuf<int> d_tag_count2[NTAGBUF];
     int tag_cur = 0; // buffer the LAST call wrote
-    tag_rec* d_tags = nullptr;
+    tag_rec* d_tags = nullptr; // = d_tags2[tag_cur], d_tag_count2[tag_cur]
     int* d_tag_count = nullptr;
-    float* d_atan = nullptr;
+    DevBuf<float> d_atan;
     uint64_t written = 0;
     int last_emit_port1 = 0;
     int corr_hist_zero = 0; // set by set_symbols(), consumed by the next call
-    int prof = 0; // aisx_corr_set_profiling
-    static constexpr int NEV = 64; // ring of event pairs: one per call, read back after the timed region
-    hipEvent_t ev0[NEV] = {}, ev1[NEV] = {};
-    long ncalls_prof = 0;
+    EventRing prof; // aisx_corr_set_profiling: one pair per call around the correlator, read back after the timed region
     // GNU Radio path staging
-    cf *d_st_in = nullptr, *d_st_out = nullptr, *d_st_corr = nullptr;
-    int st_cap = 0;
+    DevBuf<cf> d_st_in, d_st_out, d_st_corr;
 };
 
 static int corr_upload_taps(aisx_corr* h)
@@ -384,7 +370,7 @@ extern "C" int aisx_corr_create(aisx_corr** out, const aisx_cf32* symbols, int n
     int rc = require_device();
     if (rc != AISX_OK)
         return rc;
-    aisx_corr* h = new aisx_corr();
+    HandlePtr<aisx_corr, aisx_corr_destroy> h(new aisx_corr());
     h->nchan = nchan;
     h->N = nsym;
     h->max_items = max_items;
@@ -406,38 +392,27 @@ extern "C" int aisx_corr_create(aisx_corr** out, const aisx_cf32* symbols, int n
     std::vector<cf> w = corr_wtab(h->F);
     h->abits_stride = (max_items + 63) / 64 + 1;
     h->scratch_stride = max_items;
-#define CK(e)               \
-    do {                    \
-        rc = (e);           \
-        if (rc != AISX_OK) { \
-            aisx_corr_destroy(h); \
-            return rc;      \
-        }                   \
-    } while (0)
-    CK(dev_alloc(&h->d_taps, nsym));
-    CK(dev_alloc(&h->d_tapspad, h->F));
-    CK(dev_alloc(&h->d_Hpos, h->F));
-    CK(dev_alloc(&h->d_wtab, h->F));
-    CK(dev_alloc(&h->d_hist[0], (size_t)nchan * nsym));
-    CK(dev_alloc(&h->d_hist[1], (size_t)nchan * nsym));
-    CK(dev_alloc(&h->d_abits, (size_t)nchan * h->abits_stride));
-    CK(dev_alloc(&h->d_scratch, (size_t)nchan * h->scratch_stride, false));
-    for (int k = 0; k < aisx_corr::NTAGBUF; k++) {
-        CK(dev_alloc(&h->d_tags2[k], (size_t)nchan * h->tag_cap));
-        CK(dev_alloc(&h->d_tag_count2[k], nchan));
-    }
+    if ((rc = h->d_taps.alloc(nsym)) != AISX_OK || (rc = h->d_tapspad.alloc(h->F)) != AISX_OK ||
+        (rc = h->d_Hpos.alloc(h->F)) != AISX_OK || (rc = h->d_wtab.alloc(h->F)) != AISX_OK ||
+        (rc = h->d_hist[0].alloc((size_t)nchan * nsym)) != AISX_OK || (rc = h->d_hist[1].alloc((size_t)nchan * nsym)) != AISX_OK ||
+        (rc = h->d_abits.alloc((size_t)nchan * h->abits_stride)) != AISX_OK ||
+        (rc = h->d_scratch.alloc((size_t)nchan * h->scratch_stride, false)) != AISX_OK)
+        return rc;
+    for (int k = 0; k < aisx_corr::NTAGBUF; k++)
+        if ((rc = h->d_tags2[k].alloc((size_t)nchan * h->tag_cap)) != AISX_OK || (rc = h->d_tag_count2[k].alloc(nchan)) != AISX_OK)
+            return rc;
     h->d_tags = h->d_tags2[0];
     h->d_tag_count = h->d_tag_count2[0];
-    CK(dev_alloc(&h->d_atan, 257));
+    if ((rc = h->d_atan.alloc(257)) != AISX_OK)
+        return rc;
     if (hipMemcpy(h->d_wtab, w.data(), sizeof(cf) * h->F, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(h->d_atan, aisx_atan_table, sizeof(float) * 257, hipMemcpyHostToDevice) != hipSuccess) {
         set_err("aisx_corr_create: table upload failed");
-        aisx_corr_destroy(h);
         return AISX_ERR_HIP;
     }
-    CK(corr_upload_taps(h));
-#undef CK
-    *out = h;
+    if ((rc = corr_upload_taps(h.get())) != AISX_OK)
+        return rc;
+    *out = h.release();
     return AISX_OK;
 }
 
@@ -445,28 +420,6 @@ extern "C" int aisx_corr_destroy(aisx_corr* h)
 {
     if (!h)
         return AISX_OK;
-    dev_free(h->d_taps);
-    dev_free(h->d_tapspad);
-    dev_free(h->d_Hpos);
-    dev_free(h->d_wtab);
-    dev_free(h->d_hist[0]);
-    dev_free(h->d_hist[1]);
-    dev_free(h->d_abits);
-    dev_free(h->d_scratch);
-    for (int k = 0; k < aisx_corr::NTAGBUF; k++) {
-        dev_free(h->d_tags2[k]);
-        dev_free(h->d_tag_count2[k]);
-    }
-    dev_free(h->d_atan);
-    dev_free(h->d_st_in);
-    dev_free(h->d_st_out);
-    dev_free(h->d_st_corr);
-    for (int k = 0; k < aisx_corr::NEV; k++) {
-        if (h->ev0[k])
-            (void)hipEventDestroy(h->ev0[k]);
-        if (h->ev1[k])
-            (void)hipEventDestroy(h->ev1[k]);
-    }
     delete h;
     return AISX_OK;
 }
@@ -499,48 +452,33 @@ extern "C" int aisx_corr_set_symbols(aisx_corr* h, const aisx_cf32* symbols, int
         // once nothing can fail any more.
         const int Nold = h->N, keep = std::min(Nold, nsym);
         const int F = corr_pick_fft_x(nsym);
-        cf *nh[2] = { nullptr, nullptr }, *ntaps = nullptr, *npad = nullptr, *nH = nullptr, *nw = nullptr;
-        auto undo = [&](int r) {
-            dev_free(nh[0]);
-            dev_free(nh[1]);
-            dev_free(ntaps);
-            dev_free(npad);
-            dev_free(nH);
-            dev_free(nw);
-            return r;
-        };
-        if ((rc = dev_alloc(&nh[0], (size_t)h->nchan * nsym)) != AISX_OK || (rc = dev_alloc(&nh[1], (size_t)h->nchan * nsym)) != AISX_OK ||
-            (rc = dev_alloc(&ntaps, nsym)) != AISX_OK)
-            return undo(rc);
+        DevBuf<cf> nh[2], ntaps, npad, nH, nw;
+        if ((rc = nh[0].alloc((size_t)h->nchan * nsym)) != AISX_OK || (rc = nh[1].alloc((size_t)h->nchan * nsym)) != AISX_OK ||
+            (rc = ntaps.alloc(nsym)) != AISX_OK)
+            return rc;
         if (F != h->F) {
-            if ((rc = dev_alloc(&npad, F)) != AISX_OK || (rc = dev_alloc(&nH, F)) != AISX_OK || (rc = dev_alloc(&nw, F)) != AISX_OK)
-                return undo(rc);
+            if ((rc = npad.alloc(F)) != AISX_OK || (rc = nH.alloc(F)) != AISX_OK || (rc = nw.alloc(F)) != AISX_OK)
+                return rc;
             std::vector<cf> w = corr_wtab(F);
             if (hipMemcpy(nw, w.data(), sizeof(cf) * F, hipMemcpyHostToDevice) != hipSuccess) {
                 set_err("aisx_corr_set_symbols: twiddle upload failed");
-                return undo(AISX_ERR_HIP);
+                return AISX_ERR_HIP;
             }
         }
         if (hipMemcpy2D(nh[0] + (nsym - keep), sizeof(cf) * nsym, h->d_hist[h->hist_cur] + (Nold - keep), sizeof(cf) * Nold,
                         sizeof(cf) * keep, h->nchan, hipMemcpyDeviceToDevice) != hipSuccess) {
             set_err("aisx_corr_set_symbols: history copy failed");
-            return undo(AISX_ERR_HIP);
+            return AISX_ERR_HIP;
         }
         // commit
-        dev_free(h->d_hist[0]);
-        dev_free(h->d_hist[1]);
-        dev_free(h->d_taps);
-        h->d_hist[0] = nh[0];
-        h->d_hist[1] = nh[1];
-        h->d_taps = ntaps;
+        h->d_hist[0] = std::move(nh[0]);
+        h->d_hist[1] = std::move(nh[1]);
+        h->d_taps = std::move(ntaps);
         h->hist_cur = 0;
         if (F != h->F) {
-            dev_free(h->d_tapspad);
-            dev_free(h->d_Hpos);
-            dev_free(h->d_wtab);
-            h->d_tapspad = npad;
-            h->d_Hpos = nH;
-            h->d_wtab = nw;
+            h->d_tapspad = std::move(npad);
+            h->d_Hpos = std::move(nH);
+            h->d_wtab = std::move(nw);
             h->F = F;
         }
         h->N = nsym;
@@ -674,9 +612,9 @@ extern "C" int aisx_corr_process(aisx_corr* h, const aisx_cf32* d_in, long in_st
     p.tiles_per_seg = tps;
     p.thresh = h->thresh;
     p.corr_hist_zero = h->corr_hist_zero;
-    const int evi = (int)(h->ncalls_prof % aisx_corr::NEV);
-    if (h->prof)
-        AISX_HIPCHK(hipEventRecord(h->ev0[evi], st));
+    int rc;
+    if ((rc = h->prof.begin(st)) != AISX_OK)
+        return rc;
 #ifdef AISX_EXPERIMENTS
     if (h->F == CF_F && !dma)
         hipLaunchKernelGGL(k_corr_main, dim3(nseg, h->nchan), dim3(CF_T), CF_LDS_BYTES, st, p);
@@ -689,10 +627,8 @@ extern "C" int aisx_corr_process(aisx_corr* h, const aisx_cf32* d_in, long in_st
     else
         hipLaunchKernelGGL(corr2d_pick(h->N), dim3(nseg, h->nchan), dim3(CF_T), C2_LDS_BYTES, st, p);
     AISX_HIPCHK(hipGetLastError());
-    if (h->prof) {
-        AISX_HIPCHK(hipEventRecord(h->ev1[evi], st));
-        h->ncalls_prof++;
-    }
+    if ((rc = h->prof.end(st)) != AISX_OK)
+        return rc;
 
     ResolveParams r;
     r.abits = h->d_abits;
@@ -731,45 +667,13 @@ extern "C" int aisx_corr_process(aisx_corr* h, const aisx_cf32* d_in, long in_st
     return AISX_OK;
 }
 
-extern "C" int aisx_corr_set_profiling(aisx_corr* h, int on)
-{
-    if (!h)
-        return AISX_ERR_INVALID;
-    if (on && !h->ev0[0]) {
-        for (int k = 0; k < aisx_corr::NEV; k++) {
-            AISX_HIPCHK(hipEventCreate(&h->ev0[k]));
-            AISX_HIPCHK(hipEventCreate(&h->ev1[k]));
-        }
-    }
-    h->prof = on ? 1 : 0;
-    h->ncalls_prof = 0;
-    return AISX_OK;
-}
+extern "C" int aisx_corr_set_profiling(aisx_corr* h, int on) { return h ? h->prof.set_profiling(on) : AISX_ERR_INVALID; }
 
-extern "C" int aisx_corr_last_kernel_ms(aisx_corr* h, float* ms)
-{
-    if (!h || !ms || !h->ev0[0] || h->ncalls_prof < 1)
-        return AISX_ERR_INVALID;
-    const int evi = (int)((h->ncalls_prof - 1) % aisx_corr::NEV);
-    AISX_HIPCHK(hipEventSynchronize(h->ev1[evi]));
-    AISX_HIPCHK(hipEventElapsedTime(ms, h->ev0[evi], h->ev1[evi]));
-    return AISX_OK;
-}
+extern "C" int aisx_corr_last_kernel_ms(aisx_corr* h, float* ms) { return h && ms ? h->prof.last_ms(ms) : AISX_ERR_INVALID; }
 
 extern "C" int aisx_corr_kernel_ms_history(aisx_corr* h, float* ms, int cap, int* n)
 {
-    if (!h || !ms || !n || !h->ev0[0])
-        return AISX_ERR_INVALID;
-    const long have = h->ncalls_prof < aisx_corr::NEV ? h->ncalls_prof : aisx_corr::NEV;
-    int w = 0;
-    for (long k = h->ncalls_prof - have; k < h->ncalls_prof && w < cap; k++) {
-        const int evi = (int)(k % aisx_corr::NEV);
-        AISX_HIPCHK(hipEventSynchronize(h->ev1[evi]));
-        AISX_HIPCHK(hipEventElapsedTime(&ms[w], h->ev0[evi], h->ev1[evi]));
-        w++;
-    }
-    *n = w;
-    return AISX_OK;
+    return h && ms && n ? h->prof.history(ms, cap, n) : AISX_ERR_INVALID;
 }
 
 extern "C" int aisx_corr_set_lds_claim(aisx_corr* h, int bytes)
@@ -868,25 +772,16 @@ extern "C" int aisx_corr_work_host(aisx_corr* h, const aisx_cf32* in, aisx_cf32*
         return AISX_ERR_INVALID;
     }
     const int n = noutput_items;
-    if (n > h->st_cap) {
-        dev_free(h->d_st_in);
-        dev_free(h->d_st_out);
-        dev_free(h->d_st_corr);
-        int rc = dev_alloc(&h->d_st_in, n, false);
-        if (rc == AISX_OK)
-            rc = dev_alloc(&h->d_st_out, n, false);
-        if (rc == AISX_OK)
-            rc = dev_alloc(&h->d_st_corr, n, false);
-        if (rc != AISX_OK)
-            return rc;
-        h->st_cap = n;
-    }
+    int rc;
+    if ((rc = h->d_st_in.reserve(n, false)) != AISX_OK || (rc = h->d_st_out.reserve(n, false)) != AISX_OK ||
+        (rc = h->d_st_corr.reserve(n, false)) != AISX_OK)
+        return rc;
     // in[0 .. N) is the block's history, in[N .. N+n) the new items (:180-188)
     AISX_HIPCHK(hipMemcpy(h->d_hist[h->hist_cur], in, sizeof(cf) * h->N, hipMemcpyHostToDevice));
     AISX_HIPCHK(hipMemcpy(h->d_st_in, in + h->N, sizeof(cf) * n, hipMemcpyHostToDevice));
     h->written = nitems_written;
-    int rc = aisx_corr_process(h, (aisx_cf32*)h->d_st_in, n, (aisx_cf32*)h->d_st_out, n,
-                               corr ? (aisx_cf32*)h->d_st_corr : nullptr, n, n, nullptr);
+    rc = aisx_corr_process(h, (aisx_cf32*)h->d_st_in.get(), n, (aisx_cf32*)h->d_st_out.get(), n,
+                           corr ? (aisx_cf32*)h->d_st_corr.get() : nullptr, n, n, nullptr);
     if (rc != AISX_OK)
         return rc;
     AISX_HIPCHK(hipMemcpy(out, h->d_st_out, sizeof(cf) * n, hipMemcpyDeviceToHost));

@@ -24,10 +24,10 @@ __global__ __launch_bounds__(MSG_T) void k_msg(MsgParams p)
 struct aisx_msg_batch {
     int dev = 0;
     int nchan = 0, max_pdus = 0, lmax = 0, groups = 0;
-    uint32_t* d_tab = nullptr; // [MSG_TAB_WORDS]
-    int32_t* d_cols = nullptr; // [MSG_NCOL][max_pdus]
-    uint32_t* d_strs = nullptr; // [max_pdus][MSG_STR_WORDS]
-    int* d_count = nullptr;    // [0] found, [1] rows written, [2] bad-input flag
+    DevBuf<uint32_t> d_tab;  // [MSG_TAB_WORDS]
+    DevBuf<int32_t> d_cols;  // [MSG_NCOL][max_pdus]
+    DevBuf<uint32_t> d_strs; // [max_pdus][MSG_STR_WORDS]
+    DevBuf<int> d_count;     // [0] found, [1] rows written, [2] bad-input flag
 };
 
 extern "C" int aisx_msg_batch_destroy(aisx_msg_batch* h)
@@ -35,10 +35,6 @@ extern "C" int aisx_msg_batch_destroy(aisx_msg_batch* h)
     if (!h)
         return AISX_OK;
     OnDevice on(h->dev);
-    dev_free(h->d_tab);
-    dev_free(h->d_cols);
-    dev_free(h->d_strs);
-    dev_free(h->d_count);
     delete h;
     return AISX_OK;
 }
@@ -55,30 +51,21 @@ extern "C" int aisx_msg_batch_create(aisx_msg_batch** out, int nchan, int max_pd
     int rc = require_device();
     if (rc != AISX_OK)
         return rc;
-    aisx_msg_batch* h = new aisx_msg_batch();
-    if (hipGetDevice(&h->dev) != hipSuccess) {
-        delete h;
-        set_err("aisx_msg_batch_create: hipGetDevice failed");
-        return AISX_ERR_HIP;
-    }
+    HandlePtr<aisx_msg_batch, aisx_msg_batch_destroy> h(new aisx_msg_batch());
+    AISX_HIPCHK(hipGetDevice(&h->dev));
     h->nchan = nchan;
     h->max_pdus = max_pdus;
     h->lmax = length_max;
     const long long groups = ((long long)max_pdus + MSG_T - 1) / MSG_T;
     h->groups = (int)(groups < MSG_MAX_GROUPS ? groups : MSG_MAX_GROUPS);
-    if ((rc = dev_alloc(&h->d_tab, (size_t)MSG_TAB_WORDS, false)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_cols, (size_t)MSG_NCOL * max_pdus, false)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_strs, (size_t)MSG_STR_WORDS * max_pdus, false)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_count, 4)) != AISX_OK) {
-        aisx_msg_batch_destroy(h);
+    if ((rc = h->d_tab.alloc((size_t)MSG_TAB_WORDS, false)) != AISX_OK || (rc = h->d_cols.alloc((size_t)MSG_NCOL * max_pdus, false)) != AISX_OK ||
+        (rc = h->d_strs.alloc((size_t)MSG_STR_WORDS * max_pdus, false)) != AISX_OK || (rc = h->d_count.alloc(4)) != AISX_OK)
         return rc;
-    }
     if (hipMemcpy(h->d_tab, &MSG_TAB, sizeof(MsgTab), hipMemcpyHostToDevice) != hipSuccess) {
         set_err("aisx_msg_batch_create: copying the field table failed");
-        aisx_msg_batch_destroy(h);
         return AISX_ERR_HIP;
     }
-    *out = h;
+    *out = h.release();
     return AISX_OK;
 }
 
@@ -119,7 +106,7 @@ extern "C" int aisx_msg_batch_results_device(const aisx_msg_batch* h, const int3
     if (col_stride)
         *col_stride = h->max_pdus;
     if (d_strs)
-        *d_strs = (const char*)h->d_strs;
+        *d_strs = (const char*)h->d_strs.get();
     if (d_count)
         *d_count = h->d_count;
     return AISX_OK;

@@ -4,6 +4,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 #include "aisx_devctx.h"
@@ -134,82 +135,81 @@ static int msk_launch(const MskParams& p, int nwg, hipStream_t st)
 struct aisx_msk {
     int nchan = 0, max_items = 0, out_cap = 0, osps = 1;
     // measurement hook (aisx_msk_set_profiling): hipEvents around the recovery kernel of every stream call
-    int prof = 0;
-    static constexpr int NEV = 64;
-    hipEvent_t pev0[NEV] = {}, pev1[NEV] = {};
-    long ncalls_prof = 0;
+    EventRing prof;
     int lpw = 64; // channels per wave of the timing-recovery kernel
     int inline_tags = 1; // (AISX_MSK_INLINE_TAGS=0: every tag reset through the general steps, for A/B runs)
     float d_sps = 0, gain = 0, gain_omega = 0, limit = 0;
     static constexpr int carry_cap = MSK_CARRY_MAX, ctag_cap = 64;
-    float *d_mu = nullptr, *d_omega = nullptr;
-    int* d_div = nullptr;
-    cf *d_dly1 = nullptr, *d_dly2 = nullptr, *d_diff1 = nullptr;
+    DevBuf<float> d_mu, d_omega;
+    DevBuf<int> d_div;
+    DevBuf<cf> d_dly1, d_dly2, d_diff1;
     // bit tail state (previous symbol, previous sliced bit): read from [tcur], written to [tcur ^ 1]
-    cf* d_tprev[2] = { nullptr, nullptr };
-    unsigned char* d_tbit[2] = { nullptr, nullptr };
+    DevBuf<cf> d_tprev[2];
+    DevBuf<unsigned char> d_tbit[2];
     int tcur = 0;
     // symbols for the bit tail when the caller takes bits only; two, alternating, so that the
     // bit tail of call k may still read one while call k+1 writes the other (tail stream)
-    cf* d_symscratch[2] = { nullptr, nullptr };
-    size_t symscratch_len[2] = { 0, 0 };
+    DevBuf<cf> d_symscratch[2];
     int callpar = 0;
     // optional: the bit tail on a stream of its own (aisx_msk_set_tail_stream)
     bool tail_on = false;
-    hipStream_t tail_stream = nullptr;
-    hipEvent_t ev_msk = nullptr, ev_tail[2] = { nullptr, nullptr };
+    hipStream_t tail_stream = nullptr; // the caller's
+    Event ev_msk, ev_tail[2];
     unsigned head_start_ticks = 0; // aisx_msk_set_head_start
-    hipEvent_t ev_prep = nullptr; // behind the tag prepass of the last aisx_msk_process_stream (aisx_msk_wait_prepass)
+    Event ev_prep; // behind the tag prepass of the last aisx_msk_process_stream (aisx_msk_wait_prepass)
     bool ev_prep_set = false;
     bool ev_tail_set[2] = { false, false };
-    int* d_produced2 = nullptr; // second internal `produced` array (alternates with d_produced)
-    unsigned long long* d_nread = nullptr;
-    cf* d_carry[2] = { nullptr, nullptr };
-    int* d_carry_len[2] = { nullptr, nullptr };
-    tag_rec* d_ctag[2] = { nullptr, nullptr };
-    int* d_ctag_n[2] = { nullptr, nullptr };
-    msk_ctag* d_ct = nullptr; // this call's time_est tags, compacted (k_msk_tagprep)
-    int* d_ct_n = nullptr;
-    int ct_cap = 0;
+    DevBuf<int> d_produced2; // second internal `produced` array (alternates with d_produced)
+    DevBuf<unsigned long long> d_nread;
+    DevBuf<cf> d_carry[2];
+    DevBuf<int> d_carry_len[2];
+    DevBuf<tag_rec> d_ctag[2];
+    DevBuf<int> d_ctag_n[2];
+    DevBuf<msk_ctag> d_ct; // this call's time_est tags, compacted (k_msk_tagprep): nchan x ct_cap()
+    DevBuf<int> d_ct_n;
+    int ct_cap() const { return (int)(d_ct.cap() / (size_t)nchan); }
     int cur = 0;
-    int *d_produced = nullptr, *d_consumed = nullptr, *d_status = nullptr;
-    float *d_mmse = nullptr, *d_atan = nullptr;
+    DevBuf<int> d_produced, d_consumed, d_status;
+    DevBuf<float> d_mmse, d_atan;
     // time-parallel path (k_mskp.h)
     int tp_smax = 0;       // the time-parallel recovery (k_mskp.h): restart points per channel at most; 0 = off, the serial kernel alone
     int tp_min_gap = 64;   // items between restart points at least
     int tp_jw = 16;        // channels per wave of the join kernel
     int tp_join = 1;       // the join: 1 = the serial kernel with fast-forward (k_msk.h, MskParams::ff), 0 = k_mskp_join
     int tp_max_span = 4096; // no unit from a restart point further than this from the next one (tp_join = 1: the serial kernel is faster there)
-    int* d_ct_nc = nullptr;
-    // the units run on a stream of their own, one call ahead of the join (which needs the previous call's
-    // state): everything the prepass and the units leave for the join exists twice, by the call's parity
-    hipStream_t s_units = nullptr;
-    hipEvent_t ev_entry = nullptr, ev_units[2] = { nullptr, nullptr }, ev_join[2] = { nullptr, nullptr };
-    bool ev_join_set[2] = { false, false };
     int max_noutput = 0;   // set_max_noutput_items(): output items one general_work call is offered at most (0: what fits)
     unsigned long long total_in = 0; // items handed to the block so far = absolute offset of the next row's item 0
-    msk_ctag* d_ctl = nullptr;
-    int* d_ctl_n = nullptr;
-    int ctl_cap = 0;
-    int* d_nrst = nullptr;
-    mskp_rst* d_rst = nullptr;
-    mskp_res* d_res = nullptr;
-    cf* d_stage[2] = { nullptr, nullptr };
-    long stage_stride = 0;
-    int* d_ucount = nullptr; // units per length class
-    int* d_ulist = nullptr;  // ... and which
-    mskp_piece* d_pieces[2] = { nullptr, nullptr };
-    int* d_npieces[2] = { nullptr, nullptr };
-    long tp_calls = 0;
+    // Everything the time-parallel path allocates on first use (and nothing else): set up = the struct exists;
+    // without it the handle is as if the path had never run.
+    struct Tp {
+        // the units run on a stream of their own, one call ahead of the join (which needs the previous call's
+        // state): everything the prepass and the units leave for the join exists twice, by the call's parity
+        Stream s_units;
+        Event ev_entry, ev_units[2], ev_join[2];
+        bool ev_join_set[2] = { false, false };
+        DevBuf<msk_ctag> d_ctl; // 2 x nchan x ctl_cap
+        int ctl_cap = 0;
+        DevBuf<int> d_ctl_n, d_nrst;
+        DevBuf<mskp_rst> d_rst;
+        DevBuf<mskp_res> d_res;
+        DevBuf<int> d_ct_nc;
+        DevBuf<cf> d_stage[2];
+        long stage_stride = 0;
+        DevBuf<int> d_ucount; // units per length class
+        DevBuf<int> d_ulist;  // ... and which
+        DevBuf<mskp_piece> d_pieces[2];
+        DevBuf<int> d_npieces[2];
+        long tp_calls = 0;
+    };
+    std::unique_ptr<Tp> tp;
     // GNU Radio path staging
-    cf *d_st_in = nullptr, *d_st_sym = nullptr; // (d_st_sym = d_st_blk + 2: the symbols behind their 16-byte header)
-    cf* d_st_blk = nullptr;
+    DevBuf<cf> d_st_in, d_st_blk;
+    cf* d_st_sym = nullptr; // (= d_st_blk + 2: the symbols behind their 16-byte header)
     std::vector<cf> st_host; // where header + symbols land on the host
-    float *d_st_err = nullptr, *d_st_mu = nullptr;
-    unsigned char* d_st_bits = nullptr;
-    tag_rec* d_st_tags = nullptr;
-    int* d_st_tagn = nullptr;
-    int st_in_cap = 0, st_out_cap = 0, st_tag_cap = 0;
+    DevBuf<float> d_st_err, d_st_mu;
+    DevBuf<unsigned char> d_st_bits;
+    DevBuf<tag_rec> d_st_tags;
+    DevBuf<int> d_st_tagn;
 };
 
 // What the kernel's LDS rings and the carry buffer are sized for (k_msk.h): one general_work call
@@ -288,7 +288,7 @@ extern "C" int aisx_msk_create(aisx_msk** out, float sps, float gain, float limi
         return rc;
     if ((rc = msk_check_geometry(msk_setup(sps, gain).d_sps, gain, limit)) != AISX_OK)
         return rc;
-    aisx_msk* h = new aisx_msk();
+    HandlePtr<aisx_msk, aisx_msk_destroy> h(new aisx_msk());
     h->nchan = nchan;
     h->max_items = max_items;
     h->osps = osps;
@@ -296,7 +296,7 @@ extern "C" int aisx_msk_create(aisx_msk** out, float sps, float gain, float limi
     h->d_sps = msk_setup(sps, gain).d_sps; // :70
     h->gain = gain;
     h->gain_omega = msk_setup(sps, gain).gain_omega; // :83
-    h->out_cap = msk_out_cap(h);
+    h->out_cap = msk_out_cap(h.get());
     {
         // 8 channels per wave, four waves (one per SIMD), 32 channels and 90 KB of LDS per
         // workgroup: fewer lanes per wave = fewer events of other lanes to wait for (a tag costs
@@ -327,147 +327,40 @@ extern "C" int aisx_msk_create(aisx_msk** out, float sps, float gain, float limi
                 h->lpw = v;
         }
     }
-#define CK(e)               \
-    do {                    \
-        rc = (e);           \
-        if (rc != AISX_OK) { \
-            aisx_msk_destroy(h); \
-            return rc;      \
-        }                   \
-    } while (0)
-    CK(dev_alloc(&h->d_mu, nchan));
-    CK(dev_alloc(&h->d_omega, nchan));
-    CK(dev_alloc(&h->d_div, nchan));
-    CK(dev_alloc(&h->d_dly1, nchan));
-    CK(dev_alloc(&h->d_dly2, nchan));
-    CK(dev_alloc(&h->d_diff1, nchan));
-    for (int k = 0; k < 2; k++) {
-        CK(dev_alloc(&h->d_tprev[k], nchan));
-        CK(dev_alloc(&h->d_tbit[k], nchan));
-    }
-    CK(dev_alloc(&h->d_nread, nchan));
-    for (int k = 0; k < 2; k++) {
-        CK(dev_alloc(&h->d_carry[k], (size_t)nchan * aisx_msk::carry_cap));
-        CK(dev_alloc(&h->d_carry_len[k], nchan));
-        CK(dev_alloc(&h->d_ctag[k], (size_t)nchan * aisx_msk::ctag_cap));
-        CK(dev_alloc(&h->d_ctag_n[k], nchan));
-    }
-    CK(dev_alloc(&h->d_produced, nchan));
-    CK(dev_alloc(&h->d_produced2, nchan));
-    CK(dev_alloc(&h->d_consumed, nchan));
-    CK(dev_alloc(&h->d_status, nchan));
-    CK(dev_alloc(&h->d_mmse, 129 * 8));
-    CK(dev_alloc(&h->d_atan, 257));
+    const size_t nc = (size_t)nchan;
+    if ((rc = h->d_mu.alloc(nc)) != AISX_OK || (rc = h->d_omega.alloc(nc)) != AISX_OK || (rc = h->d_div.alloc(nc)) != AISX_OK ||
+        (rc = h->d_dly1.alloc(nc)) != AISX_OK || (rc = h->d_dly2.alloc(nc)) != AISX_OK || (rc = h->d_diff1.alloc(nc)) != AISX_OK ||
+        (rc = h->d_nread.alloc(nc)) != AISX_OK)
+        return rc;
+    for (int k = 0; k < 2; k++)
+        if ((rc = h->d_tprev[k].alloc(nc)) != AISX_OK || (rc = h->d_tbit[k].alloc(nc)) != AISX_OK ||
+            (rc = h->d_carry[k].alloc(nc * aisx_msk::carry_cap)) != AISX_OK || (rc = h->d_carry_len[k].alloc(nc)) != AISX_OK ||
+            (rc = h->d_ctag[k].alloc(nc * aisx_msk::ctag_cap)) != AISX_OK || (rc = h->d_ctag_n[k].alloc(nc)) != AISX_OK)
+            return rc;
+    if ((rc = h->d_produced.alloc(nc)) != AISX_OK || (rc = h->d_produced2.alloc(nc)) != AISX_OK ||
+        (rc = h->d_consumed.alloc(nc)) != AISX_OK || (rc = h->d_status.alloc(nc)) != AISX_OK ||
+        (rc = h->d_mmse.alloc(129 * 8)) != AISX_OK || (rc = h->d_atan.alloc(257)) != AISX_OK)
+        return rc;
     if (hipMemcpy(h->d_mmse, aisx_mmse_taps, sizeof(float) * 129 * 8, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(h->d_atan, aisx_atan_table, sizeof(float) * 257, hipMemcpyHostToDevice) != hipSuccess) {
         set_err("aisx_msk_create: table upload failed");
-        aisx_msk_destroy(h);
         return AISX_ERR_HIP;
     }
-    CK(msk_init_state(h));
-    // the compacted tag list for the usual hand-over capacity; grown on demand
-    h->ct_cap = aisx_msk::ctag_cap + 1024;
-    CK(dev_alloc(&h->d_ct, (size_t)nchan * (size_t)h->ct_cap));
-    CK(dev_alloc(&h->d_ct_n, nchan));
-    if (hipDeviceSynchronize() != hipSuccess) {
-        aisx_msk_destroy(h);
-        return AISX_ERR_HIP;
-    }
-#undef CK
-    *out = h;
+    // (the compacted tag list for the usual hand-over capacity; grown on demand)
+    if ((rc = msk_init_state(h.get())) != AISX_OK || (rc = h->d_ct.alloc(nc * (aisx_msk::ctag_cap + 1024))) != AISX_OK ||
+        (rc = h->d_ct_n.alloc(nc)) != AISX_OK)
+        return rc;
+    AISX_HIPCHK(hipDeviceSynchronize());
+    *out = h.release();
     return AISX_OK;
-}
-
-// everything the time-parallel path allocates on first use (and nothing else): after this the handle is as if
-// the path had never run
-static void msk_tp_free(aisx_msk* h)
-{
-    if (h->s_units) {
-        (void)hipStreamSynchronize(h->s_units);
-        (void)hipStreamDestroy(h->s_units);
-        h->s_units = nullptr;
-    }
-    auto drop = [](auto*& p) {
-        dev_free(p);
-        p = nullptr;
-    };
-    drop(h->d_ctl);
-    h->ctl_cap = 0;
-    drop(h->d_ctl_n);
-    drop(h->d_nrst);
-    drop(h->d_rst);
-    drop(h->d_res);
-    drop(h->d_ucount);
-    drop(h->d_ulist);
-    drop(h->d_ct_nc);
-    if (h->ev_entry)
-        (void)hipEventDestroy(h->ev_entry);
-    h->ev_entry = nullptr;
-    for (int k = 0; k < 2; k++) {
-        if (h->ev_units[k])
-            (void)hipEventDestroy(h->ev_units[k]);
-        if (h->ev_join[k])
-            (void)hipEventDestroy(h->ev_join[k]);
-        h->ev_units[k] = h->ev_join[k] = nullptr;
-        h->ev_join_set[k] = false;
-        drop(h->d_stage[k]);
-        drop(h->d_pieces[k]);
-        drop(h->d_npieces[k]);
-    }
 }
 
 extern "C" int aisx_msk_destroy(aisx_msk* h)
 {
     if (!h)
         return AISX_OK;
-    dev_free(h->d_mu);
-    dev_free(h->d_omega);
-    dev_free(h->d_div);
-    dev_free(h->d_dly1);
-    dev_free(h->d_dly2);
-    dev_free(h->d_diff1);
-    for (int k = 0; k < 2; k++) {
-        dev_free(h->d_tprev[k]);
-        dev_free(h->d_tbit[k]);
-    }
-    dev_free(h->d_symscratch[0]);
-    dev_free(h->d_symscratch[1]);
-    dev_free(h->d_produced2);
-    if (h->ev_msk)
-        (void)hipEventDestroy(h->ev_msk);
-    for (int k = 0; k < 2; k++)
-        if (h->ev_tail[k])
-            (void)hipEventDestroy(h->ev_tail[k]);
-    if (h->ev_prep)
-        (void)hipEventDestroy(h->ev_prep);
-    for (int k = 0; k < aisx_msk::NEV; k++) {
-        if (h->pev0[k])
-            (void)hipEventDestroy(h->pev0[k]);
-        if (h->pev1[k])
-            (void)hipEventDestroy(h->pev1[k]);
-    }
-    dev_free(h->d_ct);
-    dev_free(h->d_ct_n);
-    msk_tp_free(h);
-    dev_free(h->d_nread);
-    for (int k = 0; k < 2; k++) {
-        dev_free(h->d_carry[k]);
-        dev_free(h->d_carry_len[k]);
-        dev_free(h->d_ctag[k]);
-        dev_free(h->d_ctag_n[k]);
-    }
-    dev_free(h->d_produced);
-    dev_free(h->d_consumed);
-    dev_free(h->d_status);
-    dev_free(h->d_mmse);
-    dev_free(h->d_atan);
-    dev_free(h->d_st_in);
-    dev_free(h->d_st_blk);
-    dev_free(h->d_st_err);
-    dev_free(h->d_st_mu);
-    dev_free(h->d_st_bits);
-    dev_free(h->d_st_tags);
-    dev_free(h->d_st_tagn);
+    if (h->tp) // the units' stream comes to rest before anything it uses is released
+        (void)hipStreamSynchronize(h->tp->s_units);
     delete h;
     return AISX_OK;
 }
@@ -577,7 +470,7 @@ static void msk_fill_common(aisx_msk* h, MskParams& p)
     p.ctag_cap = aisx_msk::ctag_cap;
     p.ct = h->d_ct;
     p.ct_n = h->d_ct_n;
-    p.ct_cap = h->ct_cap;
+    p.ct_cap = h->ct_cap();
     p.consumed = h->d_consumed;
     p.status = h->d_status;
     p.mmse = h->d_mmse;
@@ -598,24 +491,30 @@ static void msk_fill_common(aisx_msk* h, MskParams& p)
     p.ct_nc = nullptr;
 }
 
-// compacts (carried tags + this call's tags) into h->d_ct for the kernel launch that follows
-static int msk_launch_tagprep(aisx_msk* h, const tag_rec* d_tags, const int* d_tag_counts, int tag_cap, hipStream_t st, int* d_ct_nc = nullptr)
+// room in h->d_ct for `need` tags per channel; a list that grows in mid-life waits for the work on `st` that reads the old one
+static int msk_ct_reserve(aisx_msk* h, int need, hipStream_t st)
 {
-    const int need = aisx_msk::ctag_cap + (d_tags ? tag_cap : 0);
-    int rc;
-    if (need > h->ct_cap || !h->d_ct) {
-        AISX_HIPCHK(hipStreamSynchronize(st));
-        dev_free(h->d_ct);
-        h->d_ct = nullptr;
-        h->ct_cap = 0;
-        if ((rc = dev_alloc(&h->d_ct, (size_t)h->nchan * (size_t)need)) != AISX_OK)
-            return rc;
-        h->ct_cap = need;
-        if (!h->d_ct_n && (rc = dev_alloc(&h->d_ct_n, h->nchan)) != AISX_OK)
-            return rc;
-        // dev_alloc's zero fill runs on the null stream: it must not trail into the kernels on `st`
-        AISX_HIPCHK(hipDeviceSynchronize());
-    }
+    if (h->d_ct && need <= h->ct_cap())
+        return AISX_OK;
+    AISX_HIPCHK(hipStreamSynchronize(st));
+    const int rc = h->d_ct.reserve((size_t)h->nchan * (size_t)need);
+    if (rc != AISX_OK)
+        return rc;
+    // dev_alloc's zero fill runs on the null stream: it must not trail into the kernels on `st`
+    AISX_HIPCHK(hipDeviceSynchronize());
+    return AISX_OK;
+}
+
+// compacts (carried tags + this call's tags [+ the prepass's list `ctl_new`, time-parallel join]) into h->d_ct for the
+// kernel launch that follows
+static int msk_launch_tagprep(aisx_msk* h, const tag_rec* d_tags, const int* d_tag_counts, int tag_cap, hipStream_t st,
+                              int* d_ct_nc = nullptr, const msk_ctag* ctl_new = nullptr, const int* ctl_new_n = nullptr,
+                              int ctl_new_cap = 0)
+{
+    const int need = aisx_msk::ctag_cap + (ctl_new ? ctl_new_cap - MSKP_TPRE : (d_tags ? tag_cap : 0));
+    const int rc = msk_ct_reserve(h, need, st);
+    if (rc != AISX_OK)
+        return rc;
     TagPrepParams t;
     t.nchan = h->nchan;
     t.ctag_in = h->d_ctag[h->cur];
@@ -627,13 +526,13 @@ static int msk_launch_tagprep(aisx_msk* h, const tag_rec* d_tags, const int* d_t
     t.nread = h->d_nread;
     t.ct = h->d_ct;
     t.ct_n = h->d_ct_n;
-    t.ct_cap = h->ct_cap;
+    t.ct_cap = h->ct_cap();
     t.ct_nc = d_ct_nc;
-    t.ctl_new = nullptr;
-    t.ctl_new_n = nullptr;
-    t.ctl_new_cap = 0;
-    t.ctl_new_pre = 0;
-    t.W = 0;
+    t.ctl_new = ctl_new;
+    t.ctl_new_n = ctl_new_n;
+    t.ctl_new_cap = ctl_new_cap;
+    t.ctl_new_pre = ctl_new ? MSKP_TPRE : 0;
+    t.W = ctl_new ? h->total_in : 0;
     hipLaunchKernelGGL(k_msk_tagprep, dim3((h->nchan + 3) / 4), dim3(256), 0, st, t); // a wave per channel
     AISX_HIPCHK(hipGetLastError());
     return AISX_OK;
@@ -674,53 +573,37 @@ static bool msk_tp_applies(const aisx_msk* h, const float* d_err, const float* d
 static int msk_tp_buffers(aisx_msk* h, int tag_cap, hipStream_t st)
 {
     int rc;
+    const size_t nc = (size_t)h->nchan;
     const int need = MSKP_TPRE + tag_cap + 1;
-    bool fresh = false;
-    if (need > h->ctl_cap || !h->d_ctl) {
-        AISX_HIPCHK(hipStreamSynchronize(st));
-        if (h->s_units)
-            AISX_HIPCHK(hipStreamSynchronize(h->s_units));
-        dev_free(h->d_ctl);
-        h->d_ctl = nullptr;
-        h->ctl_cap = 0;
-        if ((rc = dev_alloc(&h->d_ctl, 2 * (size_t)h->nchan * (size_t)need)) != AISX_OK)
+    if (h->tp && need <= h->tp->ctl_cap)
+        return AISX_OK;
+    AISX_HIPCHK(hipStreamSynchronize(st));
+    if (!h->tp) {
+        // (all or nothing: a failed allocation half way leaves a handle on which the path never ran)
+        auto t = std::make_unique<aisx_msk::Tp>();
+        t->stage_stride = mskp_stage_stride(h->max_items + aisx_msk::carry_cap, h->d_sps, h->gain, h->limit);
+        if ((rc = t->d_ctl.alloc(2 * nc * (size_t)need)) != AISX_OK || (rc = t->d_ctl_n.alloc(2 * nc)) != AISX_OK ||
+            (rc = t->d_nrst.alloc(2 * nc)) != AISX_OK || (rc = t->d_rst.alloc(2 * nc * MSKP_SMAX)) != AISX_OK ||
+            (rc = t->d_res.alloc(2 * nc * MSKP_SMAX)) != AISX_OK || (rc = t->d_ucount.alloc(16)) != AISX_OK ||
+            (rc = t->d_ct_nc.alloc(nc)) != AISX_OK || (rc = t->d_ulist.alloc(2 * nc * MSKP_SMAX * MSKP_NCLS)) != AISX_OK ||
+            (rc = t->s_units.create_nonblocking()) != AISX_OK || (rc = t->ev_entry.create(hipEventDisableTiming)) != AISX_OK)
             return rc;
-        h->ctl_cap = need;
-        fresh = true;
-    }
-    if (!h->d_rst) {
-        // (all or nothing: a failed allocation half way must not leave a handle that looks set up)
-        struct Undo {
-            aisx_msk* h;
-            bool armed = true;
-            ~Undo()
-            {
-                if (armed)
-                    msk_tp_free(h);
-            }
-        } undo{ h };
-        const size_t nc = (size_t)h->nchan;
-        h->stage_stride = mskp_stage_stride(h->max_items + aisx_msk::carry_cap, h->d_sps, h->gain, h->limit);
-        if ((rc = dev_alloc(&h->d_ctl_n, 2 * nc)) != AISX_OK || (rc = dev_alloc(&h->d_nrst, 2 * nc)) != AISX_OK ||
-            (rc = dev_alloc(&h->d_rst, 2 * nc * MSKP_SMAX)) != AISX_OK || (rc = dev_alloc(&h->d_res, 2 * nc * MSKP_SMAX)) != AISX_OK ||
-            (rc = dev_alloc(&h->d_ucount, 16)) != AISX_OK || (rc = dev_alloc(&h->d_ct_nc, nc)) != AISX_OK ||
-            (rc = dev_alloc(&h->d_ulist, 2 * nc * MSKP_SMAX * MSKP_NCLS)) != AISX_OK)
-            return rc;
-        AISX_HIPCHK(hipStreamCreateWithFlags(&h->s_units, hipStreamNonBlocking));
-        AISX_HIPCHK(hipEventCreateWithFlags(&h->ev_entry, hipEventDisableTiming));
-        for (int k = 0; k < 2; k++) {
-            AISX_HIPCHK(hipEventCreateWithFlags(&h->ev_units[k], hipEventDisableTiming));
-            AISX_HIPCHK(hipEventCreateWithFlags(&h->ev_join[k], hipEventDisableTiming));
-        }
         for (int k = 0; k < 2; k++)
-            if ((rc = dev_alloc(&h->d_stage[k], nc * (size_t)h->stage_stride)) != AISX_OK ||
-                (rc = dev_alloc(&h->d_pieces[k], nc * MSKP_SMAX)) != AISX_OK || (rc = dev_alloc(&h->d_npieces[k], nc)) != AISX_OK)
+            if ((rc = t->ev_units[k].create(hipEventDisableTiming)) != AISX_OK || (rc = t->ev_join[k].create(hipEventDisableTiming)) != AISX_OK ||
+                (rc = t->d_stage[k].alloc(nc * (size_t)t->stage_stride)) != AISX_OK ||
+                (rc = t->d_pieces[k].alloc(nc * MSKP_SMAX)) != AISX_OK || (rc = t->d_npieces[k].alloc(nc)) != AISX_OK)
                 return rc;
-        undo.armed = false;
-        fresh = true;
+        t->ctl_cap = need;
+        h->tp = std::move(t);
+    } else {
+        AISX_HIPCHK(hipStreamSynchronize(h->tp->s_units));
+        h->tp->ctl_cap = 0; // (until the new list exists)
+        if ((rc = h->tp->d_ctl.alloc(2 * nc * (size_t)need)) != AISX_OK)
+            return rc;
+        h->tp->ctl_cap = need;
     }
-    if (fresh) // dev_alloc's zero fill runs on the null stream: it must not trail into the kernels on `st`
-        AISX_HIPCHK(hipDeviceSynchronize());
+    // dev_alloc's zero fill runs on the null stream: it must not trail into the kernels on `st`
+    AISX_HIPCHK(hipDeviceSynchronize());
     return AISX_OK;
 }
 
@@ -753,16 +636,18 @@ static int msk_process_stream(aisx_msk* h, const aisx_cf32* d_in, long in_stride
     mskp_rst* rst = nullptr;
     mskp_res* res = nullptr;
     hipStream_t su = st; // where the prepass and the units run
+    aisx_msk::Tp* T = nullptr;
     if (tp) {
         if ((rc = msk_tp_buffers(h, d_tags ? tag_cap : 0, st)) != AISX_OK)
             return rc;
-        ctl = h->d_ctl + (size_t)par * nc * (size_t)h->ctl_cap;
-        ctl_n = h->d_ctl_n + par * nc;
-        nrst = h->d_nrst + par * nc;
-        rst = h->d_rst + par * nc * MSKP_SMAX;
-        res = h->d_res + par * nc * MSKP_SMAX;
-        ucount = h->d_ucount + par * 8;
-        ulist = h->d_ulist + par * nc * MSKP_SMAX * MSKP_NCLS;
+        T = h->tp.get();
+        ctl = T->d_ctl + (size_t)par * nc * (size_t)T->ctl_cap;
+        ctl_n = T->d_ctl_n + par * nc;
+        nrst = T->d_nrst + par * nc;
+        rst = T->d_rst + par * nc * MSKP_SMAX;
+        res = T->d_res + par * nc * MSKP_SMAX;
+        ucount = T->d_ucount + par * 8;
+        ulist = T->d_ulist + par * nc * MSKP_SMAX * MSKP_NCLS;
         // The units need the samples and the tags of this call, nothing of the call before: they run
         // on their own stream, beside the join of the previous call.  They start when the caller says
         // the inputs are there (ready_event; without one: when `stream` gets here), when the join of
@@ -770,16 +655,16 @@ static int msk_process_stream(aisx_msk* h, const aisx_cf32* d_in, long in_stride
         // (experiment switches, read once: units on the call's stream; unsorted unit list)
         static const bool one_stream = exp_env("AISX_MSK_TP_ONE_STREAM") != nullptr;
         if (!one_stream)
-            su = h->s_units;
+            su = T->s_units;
         if (su != st) {
             if (ready_event) {
                 AISX_HIPCHK(hipStreamWaitEvent(su, (hipEvent_t)ready_event, 0));
             } else {
-                AISX_HIPCHK(hipEventRecord(h->ev_entry, st));
-                AISX_HIPCHK(hipStreamWaitEvent(su, h->ev_entry, 0));
+                AISX_HIPCHK(hipEventRecord(T->ev_entry, st));
+                AISX_HIPCHK(hipStreamWaitEvent(su, T->ev_entry, 0));
             }
-            if (h->ev_join_set[par])
-                AISX_HIPCHK(hipStreamWaitEvent(su, h->ev_join[par], 0));
+            if (T->ev_join_set[par])
+                AISX_HIPCHK(hipStreamWaitEvent(su, T->ev_join[par], 0));
         }
         if (h->tail_on && h->ev_tail_set[par])
             AISX_HIPCHK(hipStreamWaitEvent(su, h->ev_tail[par], 0));
@@ -795,14 +680,14 @@ static int msk_process_stream(aisx_msk* h, const aisx_cf32* d_in, long in_stride
         t.limit = h->limit;
         t.ctl = ctl;
         t.ctl_n = ctl_n;
-        t.ctl_cap = h->ctl_cap;
+        t.ctl_cap = T->ctl_cap;
         // (units run blind to the general_work calls: with a max_noutput_items the call boundaries must
         // leave an un-blocked loop alone, which needs d_sps >= 2 -- see mskp_body's walk)
         t.smax = (h->max_noutput > 0 && h->d_sps < 2.0f) ? 0 : h->tp_smax;
         t_smax = t.smax;
         t.nrst = nrst;
         t.rst = rst;
-        t.stage_stride = h->stage_stride;
+        t.stage_stride = T->stage_stride;
         t.tail = mskp_tail(h->d_sps);
         t.min_gap = h->tp_min_gap;
         t.max_span = h->tp_join ? h->tp_max_span : 0x3fffffff;
@@ -828,15 +713,11 @@ static int msk_process_stream(aisx_msk* h, const aisx_cf32* d_in, long in_stride
         AISX_HIPCHK(hipStreamWaitEvent(st, h->ev_tail[par], 0));
     if (!syms) { // the kernel always writes symbols (the bit tail reads them back): give them a home
         const size_t need = (size_t)h->nchan * (size_t)out_stride;
-        if (need > h->symscratch_len[par]) {
+        if (need > h->d_symscratch[par].cap()) {
             AISX_HIPCHK(hipStreamSynchronize(st));
-            dev_free(h->d_symscratch[par]);
-            h->d_symscratch[par] = nullptr;
-            h->symscratch_len[par] = 0;
-            if ((rc = dev_alloc(&h->d_symscratch[par], need)) != AISX_OK)
+            if ((rc = h->d_symscratch[par].reserve(need)) != AISX_OK)
                 return rc;
             AISX_HIPCHK(hipDeviceSynchronize()); // (the zero fill runs on the null stream)
-            h->symscratch_len[par] = need;
         }
         syms = h->d_symscratch[par];
     }
@@ -871,18 +752,18 @@ static int msk_process_stream(aisx_msk* h, const aisx_cf32* d_in, long in_stride
         p.ctag_cap = aisx_msk::ctag_cap;
         p.ctl = ctl;
         p.ctl_n = ctl_n;
-        p.ctl_cap = h->ctl_cap;
+        p.ctl_cap = T->ctl_cap;
         p.smax = h->tp_smax;
         p.nrst = nrst;
         p.rst = rst;
         p.res = res;
-        p.stage = h->d_stage[par];
-        p.stage_stride = h->stage_stride;
+        p.stage = T->d_stage[par];
+        p.stage_stride = T->stage_stride;
         p.syms = syms;
         p.out_stride = out_stride;
         p.out_cap = out_cap;
-        p.pieces = h->d_pieces[par];
-        p.npieces = h->d_npieces[par];
+        p.pieces = T->d_pieces[par];
+        p.npieces = T->d_npieces[par];
         p.produced = produced;
         p.consumed = h->d_consumed;
         p.status = h->d_status;
@@ -906,43 +787,14 @@ static int msk_process_stream(aisx_msk* h, const aisx_cf32* d_in, long in_stride
             AISX_HIPCHK(hipGetLastError());
         }
         if (su != st) { // the join, on the caller's stream, behind the units
-            AISX_HIPCHK(hipEventRecord(h->ev_units[par], su));
-            AISX_HIPCHK(hipStreamWaitEvent(st, h->ev_units[par], 0));
+            AISX_HIPCHK(hipEventRecord(T->ev_units[par], su));
+            AISX_HIPCHK(hipStreamWaitEvent(st, T->ev_units[par], 0));
         }
         if (h->tp_join) {
             // the serial kernel as the join: the loop from the carried state, fast-forwarded through the units;
             // its tag list = the tags the scheduler still held + this call's, as the prepass compacted them
-            const int need = aisx_msk::ctag_cap + (h->ctl_cap - MSKP_TPRE);
-            if (need > h->ct_cap || !h->d_ct) {
-                AISX_HIPCHK(hipStreamSynchronize(st));
-                dev_free(h->d_ct);
-                h->d_ct = nullptr;
-                h->ct_cap = 0;
-                if ((rc = dev_alloc(&h->d_ct, nc * (size_t)need)) != AISX_OK)
-                    return rc;
-                h->ct_cap = need;
-                AISX_HIPCHK(hipDeviceSynchronize());
-            }
-            TagPrepParams tg;
-            tg.nchan = h->nchan;
-            tg.ctag_in = h->d_ctag[h->cur];
-            tg.ctag_n_in = h->d_ctag_n[h->cur];
-            tg.ctag_cap = aisx_msk::ctag_cap;
-            tg.tags = nullptr;
-            tg.tag_count = nullptr;
-            tg.tag_cap = 0;
-            tg.nread = h->d_nread;
-            tg.ct = h->d_ct;
-            tg.ct_n = h->d_ct_n;
-            tg.ct_cap = h->ct_cap;
-            tg.ct_nc = h->d_ct_nc;
-            tg.ctl_new = ctl;
-            tg.ctl_new_n = ctl_n;
-            tg.ctl_new_cap = h->ctl_cap;
-            tg.ctl_new_pre = MSKP_TPRE;
-            tg.W = h->total_in;
-            hipLaunchKernelGGL(k_msk_tagprep, dim3((h->nchan + 3) / 4), dim3(256), 0, st, tg);
-            AISX_HIPCHK(hipGetLastError());
+            if ((rc = msk_launch_tagprep(h, nullptr, nullptr, 0, st, T->d_ct_nc, ctl, ctl_n, T->ctl_cap)) != AISX_OK)
+                return rc;
             MskParams m;
             msk_fill_common(h, m);
             m.in = (const cf*)d_in;
@@ -963,9 +815,9 @@ static int msk_process_stream(aisx_msk* h, const aisx_cf32* d_in, long in_stride
             m.nrst = nrst;
             m.rst = rst;
             m.res = res;
-            m.pieces = h->d_pieces[par];
-            m.npieces = h->d_npieces[par];
-            m.ct_nc = h->d_ct_nc;
+            m.pieces = T->d_pieces[par];
+            m.npieces = T->d_npieces[par];
+            m.ct_nc = T->d_ct_nc;
             if ((rc = msk_launch(m, (h->nchan + msk_wg_channels(h->lpw) - 1) / msk_wg_channels(h->lpw), st)) != AISX_OK)
                 return rc;
         } else {
@@ -973,10 +825,10 @@ static int msk_process_stream(aisx_msk* h, const aisx_cf32* d_in, long in_stride
             AISX_HIPCHK(hipGetLastError());
         }
         if (su != st) {
-            AISX_HIPCHK(hipEventRecord(h->ev_join[par], st));
-            h->ev_join_set[par] = true;
+            AISX_HIPCHK(hipEventRecord(T->ev_join[par], st));
+            T->ev_join_set[par] = true;
         }
-        h->tp_calls++;
+        T->tp_calls++;
     } else {
         MskParams p;
         msk_fill_common(h, p);
@@ -993,25 +845,20 @@ static int msk_process_stream(aisx_msk* h, const aisx_cf32* d_in, long in_stride
         p.sym_al16 = ((uintptr_t)syms % 16 == 0) && (out_stride % 2 == 0);
         p.out_cap = out_cap;
         p.produced = produced;
-        const int evi = (int)(h->ncalls_prof % aisx_msk::NEV);
-        if (h->prof)
-            AISX_HIPCHK(hipEventRecord(h->pev0[evi], st));
-        if ((rc = msk_launch(p, (h->nchan + msk_wg_channels(h->lpw) - 1) / msk_wg_channels(h->lpw), st)) != AISX_OK)
+        if ((rc = h->prof.begin(st)) != AISX_OK ||
+            (rc = msk_launch(p, (h->nchan + msk_wg_channels(h->lpw) - 1) / msk_wg_channels(h->lpw), st)) != AISX_OK ||
+            (rc = h->prof.end(st)) != AISX_OK)
             return rc;
-        if (h->prof) {
-            AISX_HIPCHK(hipEventRecord(h->pev1[evi], st));
-            h->ncalls_prof++;
-        }
     }
     h->cur ^= 1;
     h->total_in += (unsigned long long)n;
     MskpGatherParams g;
     if (tp) {
         g.nchan = h->nchan;
-        g.pieces = h->d_pieces[par];
-        g.npieces = h->d_npieces[par];
-        g.stage = h->d_stage[par];
-        g.stage_stride = h->stage_stride;
+        g.pieces = T->d_pieces[par];
+        g.npieces = T->d_npieces[par];
+        g.stage = T->d_stage[par];
+        g.stage_stride = T->stage_stride;
         g.syms = syms;
         g.out_stride = out_stride;
         if (d_syms || !d_bits || !h->tail_on) { // the caller's own symbol rows are complete when `stream` is
@@ -1020,8 +867,8 @@ static int msk_process_stream(aisx_msk* h, const aisx_cf32* d_in, long in_stride
             // this gather reads d_stage[par] / d_res[par], which the units of the call after next overwrite on
             // their own stream: they wait for ev_join[par], so it has to stand BEHIND the gather (without a
             // bit tail on another stream nothing else orders the two)
-            if (h->ev_join_set[par])
-                AISX_HIPCHK(hipEventRecord(h->ev_join[par], st));
+            if (T->ev_join_set[par])
+                AISX_HIPCHK(hipEventRecord(T->ev_join[par], st));
         }
     }
     if (d_bits) {
@@ -1074,11 +921,10 @@ extern "C" int aisx_msk_set_tail_stream(aisx_msk* h, void* tail_stream, int enab
         h->tail_on = false;
         return AISX_OK;
     }
-    if (!h->ev_msk)
-        AISX_HIPCHK(hipEventCreateWithFlags(&h->ev_msk, hipEventDisableTiming));
-    for (int k = 0; k < 2; k++)
-        if (!h->ev_tail[k])
-            AISX_HIPCHK(hipEventCreateWithFlags(&h->ev_tail[k], hipEventDisableTiming));
+    int rc;
+    if ((rc = h->ev_msk.ensure(hipEventDisableTiming)) != AISX_OK || (rc = h->ev_tail[0].ensure(hipEventDisableTiming)) != AISX_OK ||
+        (rc = h->ev_tail[1].ensure(hipEventDisableTiming)) != AISX_OK)
+        return rc;
     h->tail_stream = (hipStream_t)tail_stream;
     h->tail_on = true;
     return AISX_OK;
@@ -1099,10 +945,8 @@ extern "C" int aisx_msk_wait_prepass(aisx_msk* h, void* stream)
 {
     if (!h)
         return AISX_ERR_INVALID;
-    if (!h->ev_prep) { // first use: from now on every aisx_msk_process_stream records the event
-        AISX_HIPCHK(hipEventCreateWithFlags(&h->ev_prep, hipEventDisableTiming));
-        return AISX_OK;
-    }
+    if (!h->ev_prep) // first use: from now on every aisx_msk_process_stream records the event
+        return h->ev_prep.ensure(hipEventDisableTiming);
     if (h->ev_prep_set) {
         AISX_HIPCHK(hipStreamWaitEvent((hipStream_t)stream, h->ev_prep, 0));
         // The event fires when the tag prepass ends -- the same moment the recovery kernel behind
@@ -1155,63 +999,24 @@ extern "C" int aisx_msk_placement(const aisx_msk* h, int* workgroups, int* lds_b
     return AISX_OK;
 }
 
-// what the time-parallel path made of the last call (diagnostics; waits for `stream`)
-extern "C" int aisx_msk_set_profiling(aisx_msk* h, int on)
-{
-    if (!h)
-        return AISX_ERR_INVALID;
-    if (on && !h->pev0[0]) {
-        // all events or none: created into temporaries, committed to the handle once every one exists
-        hipEvent_t e0[aisx_msk::NEV] = {}, e1[aisx_msk::NEV] = {};
-        bool ok = true;
-        for (int k = 0; k < aisx_msk::NEV && ok; k++)
-            ok = hipEventCreate(&e0[k]) == hipSuccess && hipEventCreate(&e1[k]) == hipSuccess;
-        if (!ok) {
-            for (int k = 0; k < aisx_msk::NEV; k++) {
-                if (e0[k])
-                    (void)hipEventDestroy(e0[k]);
-                if (e1[k])
-                    (void)hipEventDestroy(e1[k]);
-            }
-            set_err("aisx_msk_set_profiling: hipEventCreate failed");
-            return AISX_ERR_HIP;
-        }
-        for (int k = 0; k < aisx_msk::NEV; k++) {
-            h->pev0[k] = e0[k];
-            h->pev1[k] = e1[k];
-        }
-    }
-    h->prof = on ? 1 : 0;
-    h->ncalls_prof = 0;
-    return AISX_OK;
-}
+extern "C" int aisx_msk_set_profiling(aisx_msk* h, int on) { return h ? h->prof.set_profiling(on) : AISX_ERR_INVALID; }
 
 extern "C" int aisx_msk_kernel_ms_history(aisx_msk* h, float* ms, int cap, int* n)
 {
-    if (!h || !ms || !n || !h->pev0[0])
-        return AISX_ERR_INVALID;
-    const long have = h->ncalls_prof < aisx_msk::NEV ? h->ncalls_prof : aisx_msk::NEV;
-    int w = 0;
-    for (long k = h->ncalls_prof - have; k < h->ncalls_prof && w < cap; k++) {
-        const int evi = (int)(k % aisx_msk::NEV);
-        AISX_HIPCHK(hipEventSynchronize(h->pev1[evi]));
-        AISX_HIPCHK(hipEventElapsedTime(&ms[w], h->pev0[evi], h->pev1[evi]));
-        w++;
-    }
-    *n = w;
-    return AISX_OK;
+    return h && ms && n ? h->prof.history(ms, cap, n) : AISX_ERR_INVALID;
 }
 
+// what the time-parallel path made of the last call (diagnostics; waits for `stream`)
 extern "C" int aisx_msk_restart_stats(aisx_msk* h, long long* out10, void* stream)
 {
     if (!h || !out10)
         return AISX_ERR_INVALID;
-    long long* const out6 = out10; // (ten entries: include/aisx.h)
-    for (int i = 0; i < 10; i++)
-        out6[i] = 0;
-    out6[5] = h->tp_calls;
-    if (!h->d_rst || h->tp_calls == 0)
+    for (int i = 0; i < 10; i++) // (ten entries: include/aisx.h)
+        out10[i] = 0;
+    const aisx_msk::Tp* T = h->tp.get();
+    if (!T || T->tp_calls == 0) // (the path never ran on this handle)
         return AISX_OK;
+    out10[5] = T->tp_calls;
     const int par = h->callpar ^ 1; // the call before this one
     const size_t nc = (size_t)h->nchan;
     std::vector<int> nrst(nc), np(nc);
@@ -1220,29 +1025,29 @@ extern "C" int aisx_msk_restart_stats(aisx_msk* h, long long* out10, void* strea
     std::vector<mskp_rst> rp(nc * MSKP_SMAX);
     AISX_HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     // (a pipelined caller's join runs on a stream of its own: its records are complete behind ev_join)
-    if (h->ev_join_set[par])
-        AISX_HIPCHK(hipEventSynchronize(h->ev_join[par]));
-    AISX_HIPCHK(hipMemcpy(nrst.data(), h->d_nrst + par * nc, sizeof(int) * nc, hipMemcpyDeviceToHost));
-    AISX_HIPCHK(hipMemcpy(np.data(), h->d_npieces[par], sizeof(int) * nc, hipMemcpyDeviceToHost));
-    AISX_HIPCHK(hipMemcpy(pc.data(), h->d_pieces[par], sizeof(mskp_piece) * pc.size(), hipMemcpyDeviceToHost));
-    AISX_HIPCHK(hipMemcpy(rs.data(), h->d_res + par * nc * MSKP_SMAX, sizeof(mskp_res) * rs.size(), hipMemcpyDeviceToHost));
-    AISX_HIPCHK(hipMemcpy(rp.data(), h->d_rst + par * nc * MSKP_SMAX, sizeof(mskp_rst) * rp.size(), hipMemcpyDeviceToHost));
+    if (T->ev_join_set[par])
+        AISX_HIPCHK(hipEventSynchronize(T->ev_join[par]));
+    AISX_HIPCHK(hipMemcpy(nrst.data(), T->d_nrst + par * nc, sizeof(int) * nc, hipMemcpyDeviceToHost));
+    AISX_HIPCHK(hipMemcpy(np.data(), T->d_npieces[par], sizeof(int) * nc, hipMemcpyDeviceToHost));
+    AISX_HIPCHK(hipMemcpy(pc.data(), T->d_pieces[par], sizeof(mskp_piece) * pc.size(), hipMemcpyDeviceToHost));
+    AISX_HIPCHK(hipMemcpy(rs.data(), T->d_res + par * nc * MSKP_SMAX, sizeof(mskp_res) * rs.size(), hipMemcpyDeviceToHost));
+    AISX_HIPCHK(hipMemcpy(rp.data(), T->d_rst + par * nc * MSKP_SMAX, sizeof(mskp_rst) * rp.size(), hipMemcpyDeviceToHost));
     for (size_t c = 0; c < nc; c++) {
-        out6[0] += nrst[c];                     // restart points chosen
-        out6[1] += np[c];                       // units whose run was taken over
+        out10[0] += nrst[c];                     // restart points chosen
+        out10[1] += np[c];                       // units whose run was taken over
         for (int i = 0; i < np[c]; i++)
-            out6[2] += pc[c * MSKP_SMAX + i].cnt; // symbols that came from units
+            out10[2] += pc[c * MSKP_SMAX + i].cnt; // symbols that came from units
         for (int i = 0; i < nrst[c]; i++) {
-            out6[3] += rs[c * MSKP_SMAX + i].kind == MSKP_KIND_NEXT;    // units that ended at the next restart point
-            out6[4] += rs[c * MSKP_SMAX + i].kind == MSKP_KIND_HANDOFF; // ... somewhere else (stale tag, end of the row)
+            out10[3] += rs[c * MSKP_SMAX + i].kind == MSKP_KIND_NEXT;    // units that ended at the next restart point
+            out10[4] += rs[c * MSKP_SMAX + i].kind == MSKP_KIND_HANDOFF; // ... somewhere else (stale tag, end of the row)
             const long long span = rs[c * MSKP_SMAX + i].end.a - rp[c * MSKP_SMAX + i].relA;
-            out6[8] = std::max(out6[8], span); // longest unit, items
-            out6[9] += span;
+            out10[8] = std::max(out10[8], span); // longest unit, items
+            out10[9] += span;
             // links: a unit that ended at the next restart point with exactly the delay registers that one assumed
             if (i + 1 < nrst[c] && rs[c * MSKP_SMAX + i].kind == MSKP_KIND_NEXT) {
                 const mskp_res &a = rs[c * MSKP_SMAX + i], &b = rs[c * MSKP_SMAX + i + 1];
-                out6[6] += mskp_same_bits(a.end.y, b.ay) && mskp_same_bits(a.end.nl, b.anl);
-                out6[7] += 1;
+                out10[6] += mskp_same_bits(a.end.y, b.ay) && mskp_same_bits(a.end.nl, b.anl);
+                out10[7] += 1;
             }
         }
     }
@@ -1307,44 +1112,23 @@ extern "C" int aisx_msk_general_work_host(aisx_msk* h, int noutput_items, int ni
     int rc;
     // the interpolator reads up to in[ninput_items] (one past): stage one spare item
     const int nin = ninput_items + 1;
-    if (nin > h->st_in_cap) {
-        h->st_in_cap = 0; // (until the new buffer exists: a failed allocation leaves no stale capacity behind)
-        dev_free(h->d_st_in);
-        if ((rc = dev_alloc(&h->d_st_in, nin)) != AISX_OK)
-            return rc;
-        h->st_in_cap = nin;
-    }
-    if (noutput_items > h->st_out_cap) {
-        h->st_out_cap = 0;
-        dev_free(h->d_st_blk);
-        h->d_st_blk = nullptr;
-        h->d_st_sym = nullptr;
-        dev_free(h->d_st_err);
-        dev_free(h->d_st_mu);
-        dev_free(h->d_st_bits);
-        // (symbols behind a 16-byte header {produced, consumed, status, 0}: one copy brings back both)
-        if ((rc = dev_alloc(&h->d_st_blk, (size_t)noutput_items + 2)) != AISX_OK || (rc = dev_alloc(&h->d_st_err, noutput_items)) != AISX_OK ||
-            (rc = dev_alloc(&h->d_st_mu, noutput_items)) != AISX_OK || (rc = dev_alloc(&h->d_st_bits, noutput_items)) != AISX_OK)
-            return rc;
-        h->d_st_sym = h->d_st_blk + 2;
-        h->st_out_cap = noutput_items;
+    // (symbols behind a 16-byte header {produced, consumed, status, 0}: one copy brings back both)
+    bool grown = false;
+    if ((rc = h->d_st_in.reserve(nin)) != AISX_OK || (rc = h->d_st_blk.reserve((size_t)noutput_items + 2, true, &grown)) != AISX_OK ||
+        (rc = h->d_st_err.reserve(noutput_items)) != AISX_OK || (rc = h->d_st_mu.reserve(noutput_items)) != AISX_OK ||
+        (rc = h->d_st_bits.reserve(noutput_items)) != AISX_OK || (rc = h->d_st_tags.reserve(ntags + 1)) != AISX_OK ||
+        (rc = h->d_st_tagn.reserve(1)) != AISX_OK)
+        return rc;
+    h->d_st_sym = h->d_st_blk + 2;
+    if (grown)
         h->st_host.resize((size_t)noutput_items + 2);
-    }
-    if (ntags + 1 > h->st_tag_cap) {
-        h->st_tag_cap = 0;
-        dev_free(h->d_st_tags);
-        dev_free(h->d_st_tagn);
-        if ((rc = dev_alloc(&h->d_st_tags, ntags + 1)) != AISX_OK || (rc = dev_alloc(&h->d_st_tagn, 1)) != AISX_OK)
-            return rc;
-        h->st_tag_cap = ntags + 1;
-    }
     AISX_HIPCHK(hipMemcpy(h->d_st_in, in, sizeof(cf) * (in_has_lookahead ? nin : ninput_items), hipMemcpyHostToDevice));
     if (!in_has_lookahead)
         AISX_HIPCHK(hipMemset(h->d_st_in + ninput_items, 0, sizeof(cf)));
     if (ntags > 0)
         AISX_HIPCHK(hipMemcpy(h->d_st_tags, tags, sizeof(tag_rec) * ntags, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_msk_host_setup, dim3(1), dim3(1), 0, 0, h->d_st_tagn, ntags, h->d_nread, (unsigned long long)nitems_read,
-                       h->d_carry_len[h->cur], h->d_ctag_n[h->cur]);
+    hipLaunchKernelGGL(k_msk_host_setup, dim3(1), dim3(1), 0, 0, h->d_st_tagn.get(), ntags, h->d_nread.get(),
+                       (unsigned long long)nitems_read, h->d_carry_len[h->cur].get(), h->d_ctag_n[h->cur].get());
     AISX_HIPCHK(hipGetLastError());
     if ((rc = msk_launch_tagprep(h, h->d_st_tags, h->d_st_tagn, ntags + 1, 0)) != AISX_OK)
         return rc;
@@ -1371,7 +1155,7 @@ extern "C" int aisx_msk_general_work_host(aisx_msk* h, int noutput_items, int ni
     if (out_bits && (rc = msk_launch_bittail(h, h->d_st_sym, noutput_items, h->d_produced, h->d_st_bits, noutput_items,
                                              noutput_items, 0)) != AISX_OK)
         return rc;
-    hipLaunchKernelGGL(k_msk_host_pack, dim3(1), dim3(1), 0, 0, (int*)h->d_st_blk, h->d_produced, h->d_consumed, h->d_status);
+    hipLaunchKernelGGL(k_msk_host_pack, dim3(1), dim3(1), 0, 0, (int*)h->d_st_blk.get(), h->d_produced.get(), h->d_consumed.get(), h->d_status.get());
     AISX_HIPCHK(hipGetLastError());
     // header + every symbol the call may have produced in one copy (at most noutput_items of them: a few KB)
     AISX_HIPCHK(hipMemcpy(h->st_host.data(), h->d_st_blk, sizeof(cf) * ((size_t)noutput_items + 2), hipMemcpyDeviceToHost));

@@ -3,6 +3,8 @@
 // (nmea_write_body).  Everything is queued on the caller's stream; the record count is read on the device.
 #include <string.h>
 
+#include <vector>
+
 #include "aisx_devctx.h"
 #include "aisx_host.h"
 #include "k_nmea.h"
@@ -28,11 +30,11 @@ struct aisx_nmea_batch {
     int dev = 0;
     int nchan = 0, max_pdus = 0, lmax = 0, write_groups = 0;
     long long text_cap = 0;
-    char* d_desig = nullptr;         // [nchan][NM_DESIG]
-    unsigned char* d_dlen = nullptr; // [nchan]
-    HdlcRec* d_out = nullptr;        // [max_pdus]
-    char* d_text = nullptr;          // [text_cap]
-    int* d_count = nullptr;          // [0] found, [1] records written, [2] bad-input flag
+    DevBuf<char> d_desig;         // [nchan][NM_DESIG]
+    DevBuf<unsigned char> d_dlen; // [nchan]
+    DevBuf<HdlcRec> d_out;        // [max_pdus]
+    DevBuf<char> d_text;          // [text_cap]
+    DevBuf<int> d_count;          // [0] found, [1] records written, [2] bad-input flag
 };
 
 extern "C" int aisx_nmea_batch_destroy(aisx_nmea_batch* h)
@@ -40,11 +42,6 @@ extern "C" int aisx_nmea_batch_destroy(aisx_nmea_batch* h)
     if (!h)
         return AISX_OK;
     OnDevice on(h->dev);
-    dev_free(h->d_desig);
-    dev_free(h->d_dlen);
-    dev_free(h->d_out);
-    dev_free(h->d_text);
-    dev_free(h->d_count);
     delete h;
     return AISX_OK;
 }
@@ -72,12 +69,8 @@ extern "C" int aisx_nmea_batch_create(aisx_nmea_batch** out, const char* const* 
     int rc = require_device();
     if (rc != AISX_OK)
         return rc;
-    aisx_nmea_batch* h = new aisx_nmea_batch();
-    if (hipGetDevice(&h->dev) != hipSuccess) {
-        delete h;
-        set_err("aisx_nmea_batch_create: hipGetDevice failed");
-        return AISX_ERR_HIP;
-    }
+    HandlePtr<aisx_nmea_batch, aisx_nmea_batch_destroy> h(new aisx_nmea_batch());
+    AISX_HIPCHK(hipGetDevice(&h->dev));
     h->nchan = nchan;
     h->max_pdus = max_pdus;
     h->lmax = length_max;
@@ -86,31 +79,22 @@ extern "C" int aisx_nmea_batch_create(aisx_nmea_batch** out, const char* const* 
     h->text_cap = text_cap == 0 || text_cap > worst ? worst : text_cap;
     const long long groups = ((long long)max_pdus + NM_W_T / 64 - 1) / (NM_W_T / 64);
     h->write_groups = (int)(groups < NM_W_MAX_GROUPS ? groups : NM_W_MAX_GROUPS);
-    char* desig = new char[(size_t)nchan * NM_DESIG]();
-    unsigned char* dlen = new unsigned char[nchan];
+    std::vector<char> desig((size_t)nchan * NM_DESIG, 0);
+    std::vector<unsigned char> dlen(nchan);
     for (int c = 0; c < nchan; c++) {
         dlen[c] = (unsigned char)strlen(designators[c]);
-        memcpy(desig + (size_t)c * NM_DESIG, designators[c], dlen[c]);
+        memcpy(desig.data() + (size_t)c * NM_DESIG, designators[c], dlen[c]);
     }
-    if ((rc = dev_alloc(&h->d_desig, (size_t)nchan * NM_DESIG, false)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_dlen, (size_t)nchan, false)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_out, (size_t)max_pdus, false)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_text, (size_t)h->text_cap, false)) != AISX_OK || (rc = dev_alloc(&h->d_count, 4)) != AISX_OK) {
-        delete[] desig;
-        delete[] dlen;
-        aisx_nmea_batch_destroy(h);
+    if ((rc = h->d_desig.alloc((size_t)nchan * NM_DESIG, false)) != AISX_OK || (rc = h->d_dlen.alloc((size_t)nchan, false)) != AISX_OK ||
+        (rc = h->d_out.alloc((size_t)max_pdus, false)) != AISX_OK || (rc = h->d_text.alloc((size_t)h->text_cap, false)) != AISX_OK ||
+        (rc = h->d_count.alloc(4)) != AISX_OK)
         return rc;
-    }
-    const hipError_t e1 = hipMemcpy(h->d_desig, desig, (size_t)nchan * NM_DESIG, hipMemcpyHostToDevice);
-    const hipError_t e2 = hipMemcpy(h->d_dlen, dlen, (size_t)nchan, hipMemcpyHostToDevice);
-    delete[] desig;
-    delete[] dlen;
-    if (e1 != hipSuccess || e2 != hipSuccess) {
+    if (hipMemcpy(h->d_desig, desig.data(), desig.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(h->d_dlen, dlen.data(), dlen.size(), hipMemcpyHostToDevice) != hipSuccess) {
         set_err("aisx_nmea_batch_create: copying the designators failed");
-        aisx_nmea_batch_destroy(h);
         return AISX_ERR_HIP;
     }
-    *out = h;
+    *out = h.release();
     return AISX_OK;
 }
 
@@ -157,7 +141,7 @@ extern "C" int aisx_nmea_batch_results_device(const aisx_nmea_batch* h, const ai
     if (!h)
         return AISX_ERR_INVALID;
     if (d_recs)
-        *d_recs = (const aisx_pdu*)h->d_out;
+        *d_recs = (const aisx_pdu*)h->d_out.get();
     if (d_text)
         *d_text = h->d_text;
     if (d_count)

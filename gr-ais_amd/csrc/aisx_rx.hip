@@ -99,18 +99,18 @@ struct aisx_rx {
     const int32_t* d_mg_cols = nullptr;
     const char* d_mg_strs = nullptr;
     const int* d_mg_count = nullptr;
-    hipStream_t s_copy = nullptr, s_filt = nullptr, s_tail = nullptr;
-    char* h_in[RX_NPIN] = {};          // pinned [ns][block_items] items
-    char* d_raw[RX_NRAW] = {};
-    cf* d_row[RX_NROW] = {};           // [ns * nch][T]
-    uint8_t* d_bits[RX_NOUT] = {};     // [ns * nch][cap]
-    int* d_prod[RX_NOUT] = {};
-    int* d_meta = nullptr;
-    char* h_res[RX_NRES] = {};         // pinned: int meta[RX_META], aisx_pdu recs[max_pdus], char text[text_cap]
-    hipEvent_t ev_copy[RX_NPIN] = {};  // the slot's copy to the device has finished
-    hipEvent_t ev_filt[RX_NRAW] = {};  // the raw buffer's filter call has finished
-    hipEvent_t ev_tail[RX_NOUT] = {};  // the deframer has read this set of bits / produced
-    hipEvent_t ev_res[RX_NRES] = {};   // the result slot is complete
+    Stream s_copy, s_filt, s_tail;     // (before the buffers and events used on them: destroyed after those)
+    PinnedBuf<char> h_in[RX_NPIN];     // pinned [ns][block_items] items
+    DevBuf<char> d_raw[RX_NRAW];
+    DevBuf<cf> d_row[RX_NROW];         // [ns * nch][T]
+    DevBuf<uint8_t> d_bits[RX_NOUT];   // [ns * nch][cap]
+    DevBuf<int> d_prod[RX_NOUT];
+    DevBuf<int> d_meta;
+    PinnedBuf<char> h_res[RX_NRES];    // pinned: int meta[RX_META], aisx_pdu recs[max_pdus], char text[text_cap]
+    Event ev_copy[RX_NPIN];            // the slot's copy to the device has finished
+    Event ev_filt[RX_NRAW];            // the raw buffer's filter call has finished
+    Event ev_tail[RX_NOUT];            // the deframer has read this set of bits / produced
+    Event ev_res[RX_NRES];             // the result slot is complete
     const int* d_msk_status = nullptr;
     const aisx_pdu *d_hd_pdus = nullptr, *d_nm_recs = nullptr;
     const uint8_t* d_hd_bytes = nullptr;
@@ -140,9 +140,9 @@ extern "C" int aisx_rx_destroy(aisx_rx* h)
     if (!h)
         return AISX_OK;
     OnDevice on(h->dev);
-    for (hipStream_t s : { h->s_copy, h->s_filt, h->s_tail })
-        if (s)
-            (void)hipStreamSynchronize(s);
+    for (const Stream* s : { &h->s_copy, &h->s_filt, &h->s_tail })
+        if (*s)
+            (void)hipStreamSynchronize(*s);
     if (h->chain) {
         (void)aisx_chain_synchronize(h->chain);
         (void)aisx_chain_destroy(h->chain); // (before the stage handles it borrows)
@@ -157,33 +157,7 @@ extern "C" int aisx_rx_destroy(aisx_rx* h)
     (void)aisx_agc_destroy(h->agc);
     (void)aisx_freqsync_destroy(h->fs);
     (void)aisx_xlate_destroy(h->xl);
-    for (char*& p : h->h_in)
-        if (p)
-            (void)hipHostFree(p);
-    for (char*& p : h->h_res)
-        if (p)
-            (void)hipHostFree(p);
-    for (char*& p : h->d_raw)
-        dev_free(p);
-    for (cf*& p : h->d_row)
-        dev_free(p);
-    for (uint8_t*& p : h->d_bits)
-        dev_free(p);
-    for (int*& p : h->d_prod)
-        dev_free(p);
-    dev_free(h->d_meta);
-    auto drop = [](hipEvent_t* e, int n) {
-        for (int i = 0; i < n; i++)
-            if (e[i])
-                (void)hipEventDestroy(e[i]);
-    };
-    drop(h->ev_copy, RX_NPIN);
-    drop(h->ev_filt, RX_NRAW);
-    drop(h->ev_tail, RX_NOUT);
-    drop(h->ev_res, RX_NRES);
-    for (hipStream_t s : { h->s_copy, h->s_filt, h->s_tail })
-        if (s)
-            (void)hipStreamDestroy(s);
+    // (the sub-handles are gone before the receiver's own buffers, events and, last, streams)
     delete h;
     return AISX_OK;
 }
@@ -216,36 +190,35 @@ static int rx_build(aisx_rx* h, double rate, const double* center_freqs, const c
         return rc;
     h->raw_bytes = (size_t)h->ns * h->block_items * h->item_bytes;
     h->res_bytes = sizeof(int) * RX_META + sizeof(aisx_pdu) * (size_t)h->max_pdus + (size_t)h->text_cap;
-    for (char*& p : h->d_raw)
-        if ((rc = dev_alloc(&p, h->raw_bytes, false)) != AISX_OK)
+    for (auto& b : h->d_raw)
+        if ((rc = b.alloc(h->raw_bytes, false)) != AISX_OK)
             return rc;
-    for (cf*& p : h->d_row)
-        if ((rc = dev_alloc(&p, (size_t)rows * T, false)) != AISX_OK)
+    for (auto& b : h->d_row)
+        if ((rc = b.alloc((size_t)rows * T, false)) != AISX_OK)
             return rc;
-    for (uint8_t*& p : h->d_bits)
-        if ((rc = dev_alloc(&p, (size_t)rows * h->cap, false)) != AISX_OK)
+    for (int i = 0; i < RX_NOUT; i++)
+        if ((rc = h->d_bits[i].alloc((size_t)rows * h->cap, false)) != AISX_OK || (rc = h->d_prod[i].alloc((size_t)rows)) != AISX_OK)
             return rc;
-    for (int*& p : h->d_prod)
-        if ((rc = dev_alloc(&p, (size_t)rows)) != AISX_OK)
-            return rc;
-    if ((rc = dev_alloc(&h->d_meta, RX_META)) != AISX_OK)
+    if ((rc = h->d_meta.alloc(RX_META)) != AISX_OK)
         return rc;
-    for (char*& p : h->h_in)
-        AISX_HIPCHK(hipHostMalloc((void**)&p, h->raw_bytes));
-    for (char*& p : h->h_res)
-        AISX_HIPCHK(hipHostMalloc((void**)&p, h->res_bytes));
-    for (hipStream_t* s : { &h->s_copy, &h->s_filt, &h->s_tail })
-        AISX_HIPCHK(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
-    auto make = [](hipEvent_t* e, int n) {
-        for (int i = 0; i < n; i++)
-            if (hipEventCreateWithFlags(&e[i], hipEventDisableTiming) != hipSuccess)
-                return false;
-        return true;
+    for (auto& b : h->h_in)
+        if ((rc = b.alloc(h->raw_bytes)) != AISX_OK)
+            return rc;
+    for (auto& b : h->h_res)
+        if ((rc = b.alloc(h->res_bytes)) != AISX_OK)
+            return rc;
+    for (Stream* s : { &h->s_copy, &h->s_filt, &h->s_tail })
+        if ((rc = s->create_nonblocking()) != AISX_OK)
+            return rc;
+    auto make = [](Event* e, int n) {
+        int rc = AISX_OK;
+        for (int i = 0; i < n && rc == AISX_OK; i++)
+            rc = e[i].create(hipEventDisableTiming);
+        return rc;
     };
-    if (!make(h->ev_copy, RX_NPIN) || !make(h->ev_filt, RX_NRAW) || !make(h->ev_tail, RX_NOUT) || !make(h->ev_res, RX_NRES)) {
-        set_err("aisx_rx_create: hipEventCreateWithFlags failed");
-        return AISX_ERR_HIP;
-    }
+    if ((rc = make(h->ev_copy, RX_NPIN)) != AISX_OK || (rc = make(h->ev_filt, RX_NRAW)) != AISX_OK ||
+        (rc = make(h->ev_tail, RX_NOUT)) != AISX_OK || (rc = make(h->ev_res, RX_NRES)) != AISX_OK)
+        return rc;
     AISX_HIPCHK(hipDeviceSynchronize()); // (the buffers were zeroed on the null stream, which the handle's streams do not follow)
     return AISX_OK;
 }
@@ -298,12 +271,8 @@ extern "C" int aisx_rx_create(aisx_rx** out, double rate, int nstreams, int ncha
     int rc = require_device();
     if (rc != AISX_OK)
         return rc;
-    aisx_rx* h = new aisx_rx();
-    if (hipGetDevice(&h->dev) != hipSuccess) {
-        delete h;
-        set_err("aisx_rx_create: hipGetDevice failed");
-        return AISX_ERR_HIP;
-    }
+    HandlePtr<aisx_rx, aisx_rx_destroy> h(new aisx_rx());
+    AISX_HIPCHK(hipGetDevice(&h->dev));
     h->fmt = fmt;
     h->item_bytes = xlate_item_bytes(fmt);
     h->scale = scale;
@@ -314,13 +283,13 @@ extern "C" int aisx_rx_create(aisx_rx** out, double rate, int nstreams, int ncha
     h->block_items = block_items;
     h->T = block_items / D;
     h->max_pdus = max_pdus_per_block;
-    if ((rc = rx_build(h, rate, center_freqs, designators, taps, ntaps, tmpl, ntmpl, max_dlen)) != AISX_OK) {
+    if ((rc = rx_build(h.get(), rate, center_freqs, designators, taps, ntaps, tmpl, ntmpl, max_dlen)) != AISX_OK) {
         const std::string msg = aisx_last_error();
-        aisx_rx_destroy(h);
+        h.reset(); // (destroying the stages may leave a message of its own)
         set_err("%s", msg.c_str());
         return rc;
     }
-    *out = h;
+    *out = h.release();
     return AISX_OK;
 }
 
@@ -372,7 +341,7 @@ static int rx_issue(aisx_rx* h, long long k, const cf* next)
     if (k >= RX_NOUT) // the deframer has read this set's bits of step k - NOUT
         AISX_HIPCHK(hipStreamWaitEvent(h->s_filt, h->ev_tail[set], 0));
     long long step = -1;
-    if ((rc = aisx_chain_step(h->chain, (const aisx_cf32*)h->d_row[k % RX_NROW], T, T, (const aisx_cf32*)next, T, next ? T : 0, nullptr,
+    if ((rc = aisx_chain_step(h->chain, (const aisx_cf32*)h->d_row[k % RX_NROW].get(), T, T, (const aisx_cf32*)next, T, next ? T : 0, nullptr,
                               h->d_bits[set], h->cap, h->d_prod[set], h->s_filt, &step)) != AISX_OK)
         return rc;
     if (step != k) {
@@ -444,7 +413,7 @@ extern "C" int aisx_rx_submit(aisx_rx* h, long long* block)
             return rc; // (the row buffer was last read by step b - NROW)
         int nout = 0;
         if ((rc = aisx_xlate_process_fmt(h->xl, h->d_raw[raw], h->fmt, h->scale, h->bias, h->block_items, h->block_items,
-                                         (aisx_cf32*)h->d_row[row], h->T, &nout, h->s_filt)) != AISX_OK)
+                                         (aisx_cf32*)h->d_row[row].get(), h->T, &nout, h->s_filt)) != AISX_OK)
             return rc;
         AISX_HIPCHK(hipEventRecord(h->ev_filt[raw], h->s_filt));
         if (nout != h->T) {
@@ -594,32 +563,26 @@ extern "C" int aisx_rx_enable_messages(aisx_rx* h)
     // the result slots grow by the table: nothing is in flight yet, so they are simply made again
     const size_t msg_off = (h->res_bytes + 15) & ~(size_t)15;
     const size_t bytes = msg_off + (sizeof(int32_t) * AISX_MSG_NCOL + AISX_MSG_STR) * (size_t)h->max_pdus;
-    char* slots[RX_NRES] = {};
-    aisx_msg_batch* mg = nullptr;
-    int rc = aisx_msg_batch_create(&mg, h->ns * h->nch, h->max_pdus, RX_LMAX);
+    PinnedBuf<char> slots[RX_NRES];
+    aisx_msg_batch* made = nullptr;
+    int rc = aisx_msg_batch_create(&made, h->ns * h->nch, h->max_pdus, RX_LMAX);
+    HandlePtr<aisx_msg_batch, aisx_msg_batch_destroy> mg(made);
     for (int i = 0; rc == AISX_OK && i < RX_NRES; i++)
-        if (hipHostMalloc((void**)&slots[i], bytes) != hipSuccess) {
+        if ((rc = slots[i].alloc(bytes)) != AISX_OK)
             set_err("aisx_rx_enable_messages: %zu bytes of pinned memory for result slot %d could not be had", bytes, i);
-            rc = AISX_ERR_HIP;
-        }
     if (rc == AISX_OK)
-        rc = aisx_msg_batch_results_device(mg, &h->d_mg_cols, nullptr, &h->d_mg_strs, &h->d_mg_count);
-    if (rc != AISX_OK) { // (the handle stays as it was)
+        rc = aisx_msg_batch_results_device(mg.get(), &h->d_mg_cols, nullptr, &h->d_mg_strs, &h->d_mg_count);
+    if (rc != AISX_OK) { // (the handle stays as it was; what is released on the way out must not replace the message)
         const std::string msg = aisx_last_error();
-        for (char* p : slots)
-            if (p)
-                (void)hipHostFree(p);
-        (void)aisx_msg_batch_destroy(mg);
+        mg.reset();
         set_err("%s", msg.c_str());
         return rc;
     }
-    for (int i = 0; i < RX_NRES; i++) {
-        (void)hipHostFree(h->h_res[i]);
-        h->h_res[i] = slots[i];
-    }
+    for (int i = 0; i < RX_NRES; i++)
+        h->h_res[i] = std::move(slots[i]);
     h->msg_off = msg_off;
     h->res_bytes = bytes;
-    h->mg = mg;
+    h->mg = mg.release();
     return AISX_OK;
 }
 

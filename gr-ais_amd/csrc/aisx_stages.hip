@@ -93,24 +93,20 @@ extern "C" int aisx_util_agc_rcp_mismatches(float reference, unsigned long long*
         set_err("aisx_util_agc_rcp_mismatches: %g is not a reference the reciprocal form serves", reference);
         return AISX_ERR_INVALID;
     }
-    unsigned long long* d_count = nullptr;
-    unsigned* d_ex = nullptr;
-    if ((rc = dev_alloc(&d_count, 1)) != AISX_OK || (rc = dev_alloc(&d_ex, 1)) != AISX_OK) {
-        dev_free(d_count);
+    DevBuf<unsigned long long> d_count;
+    DevBuf<unsigned> d_ex;
+    if ((rc = d_count.alloc(1)) != AISX_OK || (rc = d_ex.alloc(1)) != AISX_OK)
         return rc;
-    }
     unsigned lo, hi, ex = 0;
     const float flo = AGW_RCP_LO, fhi = AGW_RCP_HI;
     memcpy(&lo, &flo, 4);
     memcpy(&hi, &fhi, 4);
-    hipLaunchKernelGGL(k_agc_rcp_sweep, dim3(256 * 32), dim3(256), 0, 0, reference, lo, hi, d_count, d_ex);
+    hipLaunchKernelGGL(k_agc_rcp_sweep, dim3(256 * 32), dim3(256), 0, 0, reference, lo, hi, d_count.get(), d_ex.get());
     hipError_t e = hipGetLastError();
     if (e == hipSuccess)
         e = hipMemcpy(count, d_count, sizeof(*count), hipMemcpyDeviceToHost);
     if (e == hipSuccess)
         e = hipMemcpy(&ex, d_ex, sizeof(ex), hipMemcpyDeviceToHost);
-    dev_free(d_count);
-    dev_free(d_ex);
     if (e != hipSuccess) {
         set_err("aisx_util_agc_rcp_mismatches: %s", hipGetErrorString(e));
         return AISX_ERR_HIP;
@@ -130,37 +126,23 @@ __global__ __launch_bounds__(AGC_T) void k_agc(AgcParams p)
 // ---------------------------------------------------------------------------
 // GNU Radio path staging: device buffers the *_work_host calls copy through, kept between calls and only ever
 // grown (a scheduler calls work() thousands of times a second with similar sizes)
-template <class T>
-static int stage_grow(T** buf, size_t* cap, size_t need)
-{
-    if (need <= *cap)
-        return AISX_OK;
-    dev_free(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    const int rc = dev_alloc(buf, need, false);
-    if (rc == AISX_OK)
-        *cap = need;
-    return rc;
-}
-
+// (DevBuf::reserve, not zeroed: every item a call reads back was written by that call)
 struct aisx_freqsync {
-    cf *d_hst_in = nullptr, *d_hst_out = nullptr; // aisx_freqsync_work_host
-    float* d_hst_fh = nullptr;
-    size_t hst_in_cap = 0, hst_out_cap = 0, hst_fh_cap = 0;
+    DevBuf<cf> d_hst_in, d_hst_out; // aisx_freqsync_work_host
+    DevBuf<float> d_hst_fh;
     int nchan = 0, fftlen = 0, max_items = 0, offset = 0, max_vec = 0;
     // made by aisx_freqest_create with a vector length the freq_sync kernels do not implement: the handle serves
     // aisx_freqest_work / aisx_freqest_work_host only (the search over bins needs no transform of ours)
     bool est_only = false;
     int walk_claim = 0; // aisx_freqsync_set_walk_lds_claim: LDS a workgroup of the phase walk claims beyond the 3 KB it uses
     float binsize = 0, sensitivity = 0;
-    cf* d_pend[2] = { nullptr, nullptr };
+    DevBuf<cf> d_pend[2];
     int cur = 0, npend = 0;
-    cf* d_wtab = nullptr;
+    DevBuf<cf> d_wtab;
     int* d_maxpos = nullptr;   // = slot[0].d_maxpos (the two-pass path)
     float* d_phase = nullptr;  // the committed NCO phase, = d_phase3[phase_cur]
     // (three copies in rotation: the committed one and the end phases of up to two walks prepared ahead)
-    float* d_phase3[3] = { nullptr, nullptr, nullptr };
+    DevBuf<float> d_phase3[3];
     int phase_cur = 0;
     // Fused front end (aisx_freqsync_agc_process).  What a call's sample pass needs from the
     // frequency estimator -- maxpos per vector, the walked NCO phases phi[c][i] (4 bytes per sample,
@@ -168,17 +150,17 @@ struct aisx_freqsync {
     // k + 1 can be prepared on another stream (aisx_freqsync_estimate_ahead) while call k's pass
     // still reads its own.
     struct Slot {
-        int* d_maxpos = nullptr;
-        float* d_phases = nullptr; // phi[c][8 j]: every eighth phase of the walk (FSW_CK)
-        float* d_dvec = nullptr;   // the phase increment of each vector
-        float* d_fhat = nullptr;
-        hipEvent_t ev_read = nullptr; // the last sample pass that read this slot
+        DevBuf<int> d_maxpos;
+        DevBuf<float> d_phases; // phi[c][8 j]: every eighth phase of the walk (FSW_CK)
+        DevBuf<float> d_dvec;   // the phase increment of each vector
+        DevBuf<float> d_fhat;
+        Event ev_read; // the last sample pass that read this slot
         bool read_pending = false;
-        hipEvent_t ev_ready = nullptr; // behind the walk that filled this slot (estimates prepared ahead)
+        Event ev_ready; // behind the walk that filled this slot (estimates prepared ahead)
     } slot[2];
     long phases_stride = 0;
     int slot_cur = 0; // the slot the next process call uses
-    hipEvent_t ev_walk = nullptr, ev_proc = nullptr, ev_est = nullptr;
+    Event ev_walk, ev_proc, ev_est;
     bool walk_pending = false, proc_pending = false;
     // estimates prepared ahead, in call order: [0] for the next aisx_freqsync_agc_process call (in
     // slot[slot_cur]), [1] for the one after (slot[slot_cur ^ 1]), each for exactly these arguments
@@ -188,11 +170,10 @@ struct aisx_freqsync {
         int n = 0;
     } ahead_q[2];
     int ahead_cnt = 0;
-    float* d_sintab = nullptr; // gr::fxpt's sine table
+    DevBuf<float> d_sintab; // gr::fxpt's sine table
     // GNU Radio path staging (aisx_freqest_work_host)
-    cf* d_st_vec = nullptr;
-    float* d_st_out = nullptr;
-    int st_cap = 0;
+    DevBuf<cf> d_st_vec;
+    DevBuf<float> d_st_out;
 };
 
 static int fs_whole(const aisx_freqsync* h, const char* who)
@@ -223,7 +204,7 @@ extern "C" int aisx_freqsync_create(aisx_freqsync** out, double samplerate, doub
     int rc = require_device();
     if (rc != AISX_OK)
         return rc;
-    aisx_freqsync* h = new aisx_freqsync();
+    HandlePtr<aisx_freqsync, aisx_freqsync_destroy> h(new aisx_freqsync());
     h->nchan = nchan;
     h->fftlen = fftlen;
     h->max_items = max_items;
@@ -240,34 +221,19 @@ extern "C" int aisx_freqsync_create(aisx_freqsync** out, double samplerate, doub
         double a = -2.0 * M_PI * (double)k / (double)FS_F;
         w[k] = mk((float)cos(a), (float)sin(a));
     }
-#define CK(e)               \
-    do {                    \
-        rc = (e);           \
-        if (rc != AISX_OK) { \
-            aisx_freqsync_destroy(h); \
-            return rc;      \
-        }                   \
-    } while (0)
-    CK(dev_alloc(&h->d_pend[0], (size_t)nchan * fftlen));
-    CK(dev_alloc(&h->d_pend[1], (size_t)nchan * fftlen));
-    CK(dev_alloc(&h->d_wtab, FS_F));
-    CK(dev_alloc(&h->slot[0].d_maxpos, (size_t)nchan * h->max_vec));
-    h->d_maxpos = h->slot[0].d_maxpos;
-    for (int k = 0; k < 3; k++)
-        CK(dev_alloc(&h->d_phase3[k], nchan));
-    h->d_phase = h->d_phase3[0];
-#undef CK
-    if ((rc = dev_alloc(&h->d_sintab, NCO_TAB_FLOATS)) != AISX_OK) {
-        aisx_freqsync_destroy(h);
+    if ((rc = h->d_pend[0].alloc((size_t)nchan * fftlen)) != AISX_OK || (rc = h->d_pend[1].alloc((size_t)nchan * fftlen)) != AISX_OK ||
+        (rc = h->d_wtab.alloc(FS_F)) != AISX_OK || (rc = h->slot[0].d_maxpos.alloc((size_t)nchan * h->max_vec)) != AISX_OK ||
+        (rc = h->d_phase3[0].alloc(nchan)) != AISX_OK || (rc = h->d_phase3[1].alloc(nchan)) != AISX_OK ||
+        (rc = h->d_phase3[2].alloc(nchan)) != AISX_OK || (rc = h->d_sintab.alloc(NCO_TAB_FLOATS)) != AISX_OK)
         return rc;
-    }
+    h->d_maxpos = h->slot[0].d_maxpos;
+    h->d_phase = h->d_phase3[0];
     if (hipMemcpy(h->d_wtab, w.data(), sizeof(cf) * FS_F, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(h->d_sintab, aisx_sine_table, sizeof(float) * NCO_TAB_FLOATS, hipMemcpyHostToDevice) != hipSuccess) {
         set_err("aisx_freqsync_create: table upload failed");
-        aisx_freqsync_destroy(h);
         return AISX_ERR_HIP;
     }
-    *out = h;
+    *out = h.release();
     return AISX_OK;
 }
 
@@ -340,30 +306,6 @@ extern "C" int aisx_freqsync_destroy(aisx_freqsync* h)
 {
     if (!h)
         return AISX_OK;
-    dev_free(h->d_pend[0]);
-    dev_free(h->d_pend[1]);
-    dev_free(h->d_wtab);
-    for (int k = 0; k < 2; k++) {
-        dev_free(h->slot[k].d_maxpos);
-        dev_free(h->slot[k].d_phases);
-        dev_free(h->slot[k].d_dvec);
-        dev_free(h->slot[k].d_fhat);
-        if (h->slot[k].ev_read)
-            (void)hipEventDestroy(h->slot[k].ev_read);
-        if (h->slot[k].ev_ready)
-            (void)hipEventDestroy(h->slot[k].ev_ready);
-    }
-    for (int k = 0; k < 3; k++)
-        dev_free(h->d_phase3[k]);
-    for (hipEvent_t e : { h->ev_walk, h->ev_proc, h->ev_est })
-        if (e)
-            (void)hipEventDestroy(e);
-    dev_free(h->d_st_vec);
-    dev_free(h->d_st_out);
-    dev_free(h->d_hst_in);
-    dev_free(h->d_hst_out);
-    dev_free(h->d_hst_fh);
-    dev_free(h->d_sintab);
     delete h;
     return AISX_OK;
 }
@@ -496,11 +438,11 @@ extern "C" int aisx_freqsync_work_host(aisx_freqsync* h, const aisx_cf32* in, in
         set_err("aisx_freqsync_work_host: output buffer too small for %d vectors", nvec);
         return AISX_ERR_INVALID;
     }
-    int rc = stage_grow(&h->d_hst_in, &h->hst_in_cap, (size_t)n);
+    int rc = h->d_hst_in.reserve((size_t)n, false);
     if (rc == AISX_OK)
-        rc = stage_grow(&h->d_hst_out, &h->hst_out_cap, (size_t)nvec * h->fftlen + 1);
+        rc = h->d_hst_out.reserve((size_t)nvec * h->fftlen + 1, false);
     if (rc == AISX_OK && fhat)
-        rc = stage_grow(&h->d_hst_fh, &h->hst_fh_cap, (size_t)nvec + 1);
+        rc = h->d_hst_fh.reserve((size_t)nvec + 1, false);
     cf *d_in = h->d_hst_in, *d_out = h->d_hst_out;
     float* d_fh = fhat ? h->d_hst_fh : nullptr;
     int nout = 0;
@@ -532,18 +474,12 @@ extern "C" int aisx_freqest_work_host(aisx_freqsync* h, int noutput_items, const
     if (noutput_items == 0)
         return 0;
     int rc;
-    if (noutput_items > h->st_cap) {
-        dev_free(h->d_st_vec);
-        dev_free(h->d_st_out);
-        h->st_cap = 0;
-        if ((rc = dev_alloc(&h->d_st_vec, (size_t)noutput_items * h->fftlen, false)) != AISX_OK ||
-            (rc = dev_alloc(&h->d_st_out, noutput_items, false)) != AISX_OK)
-            return rc;
-        h->st_cap = noutput_items;
-    }
+    if ((rc = h->d_st_vec.reserve((size_t)noutput_items * h->fftlen, false)) != AISX_OK ||
+        (rc = h->d_st_out.reserve(noutput_items, false)) != AISX_OK)
+        return rc;
     const size_t nitems = (size_t)noutput_items * h->fftlen;
     AISX_HIPCHK(hipMemcpy(h->d_st_vec, in, sizeof(cf) * nitems, hipMemcpyHostToDevice));
-    if ((rc = aisx_freqest_work(h, (const aisx_cf32*)h->d_st_vec, (long)nitems, h->d_st_out, noutput_items, noutput_items,
+    if ((rc = aisx_freqest_work(h, (const aisx_cf32*)h->d_st_vec.get(), (long)nitems, h->d_st_out, noutput_items, noutput_items,
                                 nullptr)) != AISX_OK)
         return rc;
     AISX_HIPCHK(hipMemcpy(out, h->d_st_out, sizeof(float) * noutput_items, hipMemcpyDeviceToHost));
@@ -554,12 +490,11 @@ extern "C" int aisx_freqest_work_host(aisx_freqsync* h, int noutput_items, const
 struct aisx_agc {
     int nchan = 0, W = 0, max_items = 0;
     float reference = 0, floor_env = AGC_FLOOR_DEFAULT;
-    cf* d_hist[2] = { nullptr, nullptr };
+    DevBuf<cf> d_hist[2];
     int cur = 0;
     bool tiles_only = false; // aisx_agc_set_streaming(h, 0): the tile kernels for every call
     int lds_claim = 0; // aisx_agc_set_lds_claim: LDS a streaming workgroup claims beyond the 8 KB it uses
-    cf *d_hst_in = nullptr, *d_hst_out = nullptr; // aisx_agc_work_host's staging (grown, never shrunk)
-    size_t hst_in_cap = 0, hst_out_cap = 0;
+    DevBuf<cf> d_hst_in, d_hst_out; // aisx_agc_work_host's staging (grown, never shrunk)
 };
 
 extern "C" int aisx_agc_geometry(const aisx_agc* h, int* nchan, int* max_items, int* nsamples, int* fused_ok)
@@ -593,26 +528,22 @@ extern "C" int aisx_agc_create(aisx_agc** out, int nsamples, float reference, in
     int rc = require_device();
     if (rc != AISX_OK)
         return rc;
-    aisx_agc* h = new aisx_agc();
+    HandlePtr<aisx_agc, aisx_agc_destroy> h(new aisx_agc());
     h->nchan = nchan;
     h->W = nsamples;
     h->max_items = max_items;
     h->reference = reference;
     if (const char* e = exp_env("AISX_AGC_STREAMING")) // (experiments; the API is aisx_agc_set_streaming)
         h->tiles_only = atoi(e) == 0;
-    if ((rc = dev_alloc(&h->d_hist[0], (size_t)nchan * nsamples)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_hist[1], (size_t)nchan * nsamples)) != AISX_OK) {
-        aisx_agc_destroy(h);
+    if ((rc = h->d_hist[0].alloc((size_t)nchan * nsamples)) != AISX_OK || (rc = h->d_hist[1].alloc((size_t)nchan * nsamples)) != AISX_OK)
         return rc;
-    }
     // dev_alloc's zero fill runs on the null stream; callers launch on their own (non-blocking)
     // streams, which do not order against it
     if (hipDeviceSynchronize() != hipSuccess) {
         set_err("aisx_agc_create: device synchronisation failed");
-        aisx_agc_destroy(h);
         return AISX_ERR_HIP;
     }
-    *out = h;
+    *out = h.release();
     return AISX_OK;
 }
 
@@ -680,10 +611,6 @@ extern "C" int aisx_agc_destroy(aisx_agc* h)
 {
     if (!h)
         return AISX_OK;
-    dev_free(h->d_hist[0]);
-    dev_free(h->d_hist[1]);
-    dev_free(h->d_hst_in);
-    dev_free(h->d_hst_out);
     delete h;
     return AISX_OK;
 }
@@ -743,30 +670,17 @@ extern "C" int aisx_agc_process(aisx_agc* h, const aisx_cf32* d_in, long in_stri
 static int fs_fused_prepare(aisx_freqsync* h)
 {
     int rc;
-    if (!h->ev_walk) {
-        AISX_HIPCHK(hipEventCreateWithFlags(&h->ev_walk, hipEventDisableTiming));
-        AISX_HIPCHK(hipEventCreateWithFlags(&h->ev_proc, hipEventDisableTiming));
-        AISX_HIPCHK(hipEventCreateWithFlags(&h->ev_est, hipEventDisableTiming));
-    }
-    for (int k = 0; k < 2; k++) {
-        aisx_freqsync::Slot& s = h->slot[k];
-        if (!s.ev_read)
-            AISX_HIPCHK(hipEventCreateWithFlags(&s.ev_read, hipEventDisableTiming));
-        if (!s.ev_ready)
-            AISX_HIPCHK(hipEventCreateWithFlags(&s.ev_ready, hipEventDisableTiming));
-        if (!s.d_maxpos && (rc = dev_alloc(&s.d_maxpos, (size_t)h->nchan * h->max_vec)) != AISX_OK)
+    if ((rc = h->ev_walk.ensure(hipEventDisableTiming)) != AISX_OK || (rc = h->ev_proc.ensure(hipEventDisableTiming)) != AISX_OK ||
+        (rc = h->ev_est.ensure(hipEventDisableTiming)) != AISX_OK)
+        return rc;
+    const size_t nv = (size_t)h->nchan * h->max_vec;
+    h->phases_stride = ((long)h->max_vec * (h->fftlen / FSW_CK) + 3) & ~3L;
+    // (first use; each under its own test: a call that failed half way is finished by the next one)
+    for (aisx_freqsync::Slot& s : h->slot)
+        if ((rc = s.ev_read.ensure(hipEventDisableTiming)) != AISX_OK || (rc = s.ev_ready.ensure(hipEventDisableTiming)) != AISX_OK ||
+            (rc = s.d_maxpos.reserve(nv)) != AISX_OK || (rc = s.d_fhat.reserve(nv)) != AISX_OK || (rc = s.d_dvec.reserve(nv)) != AISX_OK ||
+            (rc = s.d_phases.reserve((size_t)h->nchan * (size_t)h->phases_stride, false)) != AISX_OK)
             return rc;
-        if (!s.d_fhat && (rc = dev_alloc(&s.d_fhat, (size_t)h->nchan * h->max_vec)) != AISX_OK)
-            return rc;
-        // (each allocation under its own test: a call that failed half way is finished by the next one)
-        if (!s.d_dvec && (rc = dev_alloc(&s.d_dvec, (size_t)h->nchan * h->max_vec)) != AISX_OK)
-            return rc;
-        if (!s.d_phases) {
-            h->phases_stride = ((long)h->max_vec * (h->fftlen / FSW_CK) + 3) & ~3L;
-            if ((rc = dev_alloc(&s.d_phases, (size_t)h->nchan * (size_t)h->phases_stride, false)) != AISX_OK)
-                return rc;
-        }
-    }
     return AISX_OK;
 }
 
@@ -984,9 +898,9 @@ extern "C" int aisx_agc_work_host(aisx_agc* h, int noutput_items, const aisx_cf3
         return AISX_ERR_INVALID;
     }
     const int H = h->W - 1, n = noutput_items;
-    int rc = stage_grow(&h->d_hst_in, &h->hst_in_cap, (size_t)n);
+    int rc = h->d_hst_in.reserve((size_t)n, false);
     if (rc == AISX_OK)
-        rc = stage_grow(&h->d_hst_out, &h->hst_out_cap, (size_t)n);
+        rc = h->d_hst_out.reserve((size_t)n, false);
     cf *d_in = h->d_hst_in, *d_out = h->d_hst_out;
     // the block's history comes from the scheduler's buffer, not from the handle
     if (rc == AISX_OK && H > 0 && hipMemcpy(h->d_hist[h->cur], in, sizeof(cf) * H, hipMemcpyHostToDevice) != hipSuccess)
@@ -1014,9 +928,9 @@ __global__ __launch_bounds__(PFB_T) void k_pfb(PfbParams p)
 
 struct aisx_pfb {
     int nstreams = 0, D = 0, K = 0, Lh = 0, max_frames = 0;
-    float* d_taps = nullptr;
-    cf* d_wtab = nullptr;
-    cf* d_hist[2] = { nullptr, nullptr };
+    DevBuf<float> d_taps;
+    DevBuf<cf> d_wtab;
+    DevBuf<cf> d_hist[2];
     int cur = 0;
     long frame0 = 0;
 };
@@ -1034,7 +948,7 @@ extern "C" int aisx_pfb_create(aisx_pfb** out, int nlanes, int decim, const floa
     int rc = require_device();
     if (rc != AISX_OK)
         return rc;
-    aisx_pfb* h = new aisx_pfb();
+    HandlePtr<aisx_pfb, aisx_pfb_destroy> h(new aisx_pfb());
     h->nstreams = nstreams;
     h->D = decim;
     h->K = (ntaps + PFB_M - 1) / PFB_M;
@@ -1048,19 +962,15 @@ extern "C" int aisx_pfb_create(aisx_pfb** out, int nlanes, int decim, const floa
         double a = -2.0 * M_PI * (double)k / (double)PFB_M;
         w[k] = mk((float)cos(a), (float)sin(a));
     }
-    if ((rc = dev_alloc(&h->d_taps, h->Lh)) != AISX_OK || (rc = dev_alloc(&h->d_wtab, PFB_M)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_hist[0], (size_t)nstreams * h->Lh)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_hist[1], (size_t)nstreams * h->Lh)) != AISX_OK) {
-        aisx_pfb_destroy(h);
+    if ((rc = h->d_taps.alloc(h->Lh)) != AISX_OK || (rc = h->d_wtab.alloc(PFB_M)) != AISX_OK ||
+        (rc = h->d_hist[0].alloc((size_t)nstreams * h->Lh)) != AISX_OK || (rc = h->d_hist[1].alloc((size_t)nstreams * h->Lh)) != AISX_OK)
         return rc;
-    }
     if (hipMemcpy(h->d_taps, pad.data(), sizeof(float) * h->Lh, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(h->d_wtab, w.data(), sizeof(cf) * PFB_M, hipMemcpyHostToDevice) != hipSuccess) {
         set_err("aisx_pfb_create: table upload failed");
-        aisx_pfb_destroy(h);
         return AISX_ERR_HIP;
     }
-    *out = h;
+    *out = h.release();
     return AISX_OK;
 }
 
@@ -1068,10 +978,6 @@ extern "C" int aisx_pfb_destroy(aisx_pfb* h)
 {
     if (!h)
         return AISX_OK;
-    dev_free(h->d_taps);
-    dev_free(h->d_wtab);
-    dev_free(h->d_hist[0]);
-    dev_free(h->d_hist[1]);
     delete h;
     return AISX_OK;
 }

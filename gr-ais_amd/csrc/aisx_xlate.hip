@@ -32,13 +32,13 @@ struct aisx_xlate {
     XlateHost hs;                          // geometry, plan, phases, stream position (k_xlate.h)
     int hsel = 0;                          // which history buffer holds the current history
     bool dirty = true;                     // phases / tables differ from the device's copy
-    cf* d_hist[2] = { nullptr, nullptr };  // [ns][Lh] each
-    float* d_taps = nullptr;               // [Utot][R]
-    cf* d_tab = nullptr;                   // [nrows][XL_B]
-    unsigned long long* d_par = nullptr;   // [nrows][2]
-    cf* h_tab = nullptr;                   // pinned staging of the uploads
-    unsigned long long* h_par = nullptr;
-    hipEvent_t ev_up = nullptr, ev_done = nullptr;
+    DevBuf<cf> d_hist[2];                  // [ns][Lh] each
+    DevBuf<float> d_taps;                  // [Utot][R]
+    DevBuf<cf> d_tab;                      // [nrows][XL_B]
+    DevBuf<unsigned long long> d_par;      // [nrows][2]
+    PinnedBuf<cf> h_tab;                   // pinned staging of the uploads
+    PinnedBuf<unsigned long long> h_par;
+    Event ev_up, ev_done;
 };
 
 extern "C" int aisx_xlate_destroy(aisx_xlate* h)
@@ -50,19 +50,6 @@ extern "C" int aisx_xlate_destroy(aisx_xlate* h)
         (void)hipEventSynchronize(h->ev_done);
     if (h->ev_up)
         (void)hipEventSynchronize(h->ev_up);
-    dev_free(h->d_hist[0]);
-    dev_free(h->d_hist[1]);
-    dev_free(h->d_taps);
-    dev_free(h->d_tab);
-    dev_free(h->d_par);
-    if (h->h_tab)
-        (void)hipHostFree(h->h_tab);
-    if (h->h_par)
-        (void)hipHostFree(h->h_par);
-    if (h->ev_up)
-        (void)hipEventDestroy(h->ev_up);
-    if (h->ev_done)
-        (void)hipEventDestroy(h->ev_done);
     delete h;
     return AISX_OK;
 }
@@ -80,32 +67,19 @@ extern "C" int aisx_xlate_create(aisx_xlate** out, int decim, const float* taps,
     int rc = require_device();
     if (rc != AISX_OK)
         return rc;
-    aisx_xlate* h = new aisx_xlate();
-    if (hipGetDevice(&h->dev) != hipSuccess) {
-        delete h;
-        set_err("aisx_xlate_create: hipGetDevice failed");
-        return AISX_ERR_HIP;
-    }
+    HandlePtr<aisx_xlate, aisx_xlate_destroy> h(new aisx_xlate());
+    AISX_HIPCHK(hipGetDevice(&h->dev));
     XlateHost& hs = h->hs;
     hs.init(decim, taps, ntaps, center_freqs, nchan_per_stream, samp_rate, nstreams, max_items, XL_T);
     const size_t hist = (size_t)nstreams * hs.Lh, nrows = (size_t)hs.nrows();
-    if ((rc = dev_alloc(&h->d_hist[0], hist)) != AISX_OK || (rc = dev_alloc(&h->d_hist[1], hist)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_taps, hs.taps.size(), false)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_tab, nrows * XL_B, false)) != AISX_OK ||
-        (rc = dev_alloc(&h->d_par, nrows * 2, false)) != AISX_OK) {
-        aisx_xlate_destroy(h);
+    if ((rc = h->d_hist[0].alloc(hist)) != AISX_OK || (rc = h->d_hist[1].alloc(hist)) != AISX_OK ||
+        (rc = h->d_taps.alloc(hs.taps.size(), false)) != AISX_OK || (rc = h->d_tab.alloc(nrows * XL_B, false)) != AISX_OK ||
+        (rc = h->d_par.alloc(nrows * 2, false)) != AISX_OK || (rc = h->h_tab.alloc(nrows * XL_B)) != AISX_OK ||
+        (rc = h->h_par.alloc(nrows * 2)) != AISX_OK || (rc = h->ev_up.create(hipEventDisableTiming)) != AISX_OK ||
+        (rc = h->ev_done.create(hipEventDisableTiming)) != AISX_OK)
         return rc;
-    }
-    if (hipHostMalloc((void**)&h->h_tab, sizeof(cf) * nrows * XL_B) != hipSuccess ||
-        hipHostMalloc((void**)&h->h_par, sizeof(unsigned long long) * nrows * 2) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_up, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming) != hipSuccess ||
-        hipMemcpy(h->d_taps, hs.taps.data(), sizeof(float) * hs.taps.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        set_err("aisx_xlate_create: allocating or uploading the tables failed");
-        aisx_xlate_destroy(h);
-        return AISX_ERR_HIP;
-    }
-    *out = h;
+    AISX_HIPCHK(hipMemcpy(h->d_taps, hs.taps.data(), sizeof(float) * hs.taps.size(), hipMemcpyHostToDevice));
+    *out = h.release();
     return AISX_OK;
 }
 
