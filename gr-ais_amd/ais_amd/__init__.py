@@ -34,7 +34,8 @@ def __getattr__(name):
         from . import blocks
 
         return getattr(blocks, name)
-    if name in ("hdlc_deframer_batch", "pdu_to_nmea_batch", "pdu_decode_batch", "PDU_DTYPE"):
+    if name in ("hdlc_deframer_batch", "pdu_to_nmea_batch", "pdu_decode_batch", "PDU_DTYPE", "vessel_table", "vessel_table_batch",
+                "TRACK_COLUMNS", "TRACK_COUNTS", "TRACK_DTYPE"):
         from . import batch_framing
 
         return getattr(batch_framing, name)

@@ -220,6 +220,24 @@ def lib(device=True):
     sig("aisx_msg_batch_read", i32, [vp, vp, lng, vp, i32, pi32, pi32, vp])
     sig("aisx_rx_enable_messages", i32, [vp])
     sig("aisx_rx_pop_messages", i32, [vp, i32, pll, vp, lng, plng, vp, i32, pi32, vp, lng, vp, pi32])
+    sig("aisx_track_create", i32, [pvp, i32])
+    sig("aisx_track_destroy", i32, [vp])
+    sig("aisx_track_update", i32, [vp, vp, lng, vp, vp, i32, i32, vp])
+    sig("aisx_track_expire", i32, [vp, i32, vp])
+    sig("aisx_track_data", i32, [vp, pvp, plng, pvp, pi32])
+    sig("aisx_track_changed", i32, [vp, pvp, pi32])
+    sig("aisx_track_batch_create", i32, [pvp, i32, i32])
+    sig("aisx_track_batch_destroy", i32, [vp])
+    sig("aisx_track_batch_reset", i32, [vp])
+    sig("aisx_track_batch_process", i32, [vp, vp, lng, vp, vp, vp, i32, vp])
+    sig("aisx_track_batch_expire", i32, [vp, i32, vp])
+    sig("aisx_track_batch_results_device", i32, [vp, pvp, plng, pvp, pvp, pvp])
+    sig("aisx_track_batch_read", i32, [vp, i32, i32, vp, lng, vp, pi32, vp])
+    sig("aisx_track_batch_counts", i32, [vp, vp, vp])
+    sig("aisx_track_batch_read_changed", i32, [vp, vp, vp, lng, vp, i32, pi32, vp])
+    sig("aisx_rx_enable_tracks", i32, [vp, i32])
+    sig("aisx_rx_read_tracks", i32, [vp, i32, i32, vp, lng, vp, pi32, pll])
+    sig("aisx_rx_read_changed_tracks", i32, [vp, vp, vp, lng, vp, i32, pi32, pll])
     _lib = L
     return L
 

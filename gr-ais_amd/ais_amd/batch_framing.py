@@ -2,7 +2,9 @@
 `ais_demod.work_pipelined`: the batched HDLC deframer (aisx_hdlc_batch_*, `hdlc_deframer_bp(11, 64)`,
 python/radio.py:64) and, queued behind it on the same stream, the batched `pdu_to_nmea` (aisx_nmea_batch_*,
 python/radio.py:73) and the batched ITU-R M.1371 field decoder (aisx_msg_batch_*).  One copy per step brings back the
-PDUs, a newline-terminated NMEA stream or a table of decoded messages -- or the table stays on the device as tensors."""
+PDUs, a newline-terminated NMEA stream or a table of decoded messages -- or the table stays on the device as tensors.
+Behind the decoder, the vessel table (aisx_track_*): the latest state per MMSI, kept in device memory and merged from
+every step's decoded rows, of which only the vessels a step touched are read back."""
 import ctypes as C
 
 import numpy as np
@@ -299,3 +301,242 @@ class pdu_decode_batch:
         if not (rc == _lib.AISX_ERR_OVERFLOW and overflow_ok):
             check(rc, "pdu_decode_batch.messages")
         return msg_table(self._cols, self._strs, n.value)
+
+
+# the columns of a vessel, in the order of include/aisx.h's AISX_MSG_COL_* and AISX_TRK_COL_*, and the counts of AISX_TRK_CNT_*
+def _track_names():
+    from .framing import MSG_COLUMNS
+
+    return tuple(MSG_COLUMNS) + ("COUNT", "STAMP", "POS_STAMP", "CHAN")
+
+
+TRACK_COLUMNS = _track_names()
+TRACK_COUNTS = ("vessels", "merged", "skipped", "dropped", "changed", "removed", "full", "bad_input")
+# one vessel on the host: an int32 per column (lower-case names) and the three strings; a changed vessel also has its index
+TRACK_DTYPE = np.dtype([(c.lower(), "<i4") for c in TRACK_COLUMNS] + [("callsign", "S7"), ("name", "S20"), ("destination", "S20")])
+TRACK_CHANGED_DTYPE = np.dtype([("vessel", "<i4")] + TRACK_DTYPE.descr)
+
+
+def _track_table(cols, strs, n, idx=None):
+    """int32 [ncol][>= n] and uint8 [>= n][48] on the host -> a TRACK_DTYPE array of n vessels (TRACK_CHANGED_DTYPE
+    with their indices when idx is given)"""
+    out = np.zeros(n, dtype=TRACK_DTYPE if idx is None else TRACK_CHANGED_DTYPE)
+    if idx is not None:
+        out["vessel"] = idx[:n]
+    for k, c in enumerate(TRACK_COLUMNS):
+        out[c.lower()] = cols[k, :n]
+    s = np.ascontiguousarray(strs[:n])
+    out["callsign"] = s[:, 0:7].copy().view("S7").ravel()
+    out["name"] = s[:, 8:28].copy().view("S20").ravel()
+    out["destination"] = s[:, 28:48].copy().view("S20").ravel()
+    return out
+
+
+def _rows_of(messages):
+    """a MSG_DTYPE array (pop_messages' / messages') -> (int32 cols [ncol][n], uint8 strs [n][48])"""
+    from .framing import MSG_COLUMNS
+
+    m = np.asarray(messages)
+    cols = np.ascontiguousarray(np.stack([m[c.lower()] for c in MSG_COLUMNS]).astype(np.int32)) if len(m) else \
+        np.zeros((len(MSG_COLUMNS), 0), dtype=np.int32)
+    strs = np.zeros((len(m), _lib.AISX_MSG_STR), dtype=np.uint8)
+    for name, lo, w in (("callsign", 0, 7), ("name", 8, 20), ("destination", 28, 20)):
+        if len(m):
+            strs[:, lo:lo + w] = np.frombuffer(m[name].astype("S%d" % w).tobytes(), dtype=np.uint8).reshape(len(m), w)
+    return cols, strs
+
+
+class vessel_table:
+    """The vessel table on the host (aisx_track_*, plain C++: the specification of vessel_table_batch): the latest
+    state per MMSI, at most `capacity` vessels, vessel v the v-th distinct MMSI accepted.  update() merges the rows of
+    a decoded table in row order -- a column that is not MSG_NA and a string slot that is carried replace the vessel's,
+    so type 5 / 24 static data and type 1-3 / 18 / 19 positions meet in one row; expire() forgets the vessels whose
+    last update is older than a stamp.  Values are kept as transmitted (the protocol's own "not available" codes are
+    values like any other)."""
+
+    def __init__(self, capacity):
+        h = C.c_void_p()
+        check(_lib.lib(device=False).aisx_track_create(C.byref(h), int(capacity)), "vessel_table")
+        self._h = h
+        self.capacity = int(capacity)
+        self.counts = dict.fromkeys(TRACK_COUNTS, 0)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            _lib.lib(device=False).aisx_track_destroy(h)
+            self._h = None
+
+    def _set_counts(self, cnt):
+        self.counts = {k: int(v) for k, v in zip(TRACK_COUNTS, cnt)}
+        return self.counts
+
+    def update(self, cols, strs, stamp, recs=None):
+        """cols: int32 [len(MSG_COLUMNS)][n], strs: uint8 [n][48] (or cols a MSG_DTYPE array and strs None); recs: the
+        rows' PDU_DTYPE records, for CHAN.  Returns the counts of this call as a dict of TRACK_COUNTS."""
+        if strs is None:
+            cols, strs = _rows_of(cols)
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        strs = np.ascontiguousarray(strs, dtype=np.uint8)
+        n = cols.shape[1]
+        if strs.shape != (n, _lib.AISX_MSG_STR) or (recs is not None and len(recs) < n):
+            raise ValueError("vessel_table.update: need cols [ncol][n], strs [n][48] and, if any, n records")
+        r = np.ascontiguousarray(recs, dtype=PDU_DTYPE) if recs is not None else None
+        cnt = np.zeros(len(TRACK_COUNTS), dtype=np.int32)
+        check(_lib.lib(device=False).aisx_track_update(self._h, cols.ctypes.data_as(C.c_void_p), n,
+                                                       strs.ctypes.data_as(C.c_void_p),
+                                                       r.ctypes.data_as(C.c_void_p) if r is not None else None, n, int(stamp),
+                                                       cnt.ctypes.data_as(C.c_void_p)), "vessel_table.update")
+        return self._set_counts(cnt)
+
+    def expire(self, min_stamp):
+        """forgets every vessel whose STAMP is below min_stamp; returns how many"""
+        cnt = np.zeros(len(TRACK_COUNTS), dtype=np.int32)
+        check(_lib.lib(device=False).aisx_track_expire(self._h, int(min_stamp), cnt.ctypes.data_as(C.c_void_p)), "vessel_table.expire")
+        return self._set_counts(cnt)["removed"]
+
+    def arrays(self):
+        """(cols int32 [len(TRACK_COLUMNS)][nvessels], strs uint8 [nvessels][48], changed int32 [nchanged]): copies"""
+        c, s, i = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        stride, nv, nc = C.c_long(), C.c_int(), C.c_int()
+        L = _lib.lib(device=False)
+        check(L.aisx_track_data(self._h, C.byref(c), C.byref(stride), C.byref(s), C.byref(nv)), "vessel_table")
+        check(L.aisx_track_changed(self._h, C.byref(i), C.byref(nc)), "vessel_table")
+        ncol = len(TRACK_COLUMNS)
+        cols = np.ctypeslib.as_array(C.cast(c, C.POINTER(C.c_int32)), shape=(ncol, stride.value))[:, : nv.value].copy()
+        strs = np.ctypeslib.as_array(C.cast(s, C.POINTER(C.c_uint8)), shape=(stride.value, _lib.AISX_MSG_STR))[: nv.value].copy()
+        chg = np.ctypeslib.as_array(C.cast(i, C.POINTER(C.c_int32)), shape=(nc.value,)).copy() if nc.value else np.zeros(0, np.int32)
+        return cols, strs, chg
+
+    def vessels(self):
+        """the table as a TRACK_DTYPE array, one row per vessel"""
+        cols, strs, _ = self.arrays()
+        return _track_table(cols, strs, cols.shape[1])
+
+    def changed(self):
+        """the vessels the last update merged a row into, ordered by the first row that touched each: a
+        TRACK_CHANGED_DTYPE array (field "vessel" = the index)"""
+        cols, strs, chg = self.arrays()
+        return _track_table(cols[:, chg], strs[chg], len(chg), chg)
+
+
+class vessel_table_batch:
+    """The vessel table in device memory (aisx_track_batch_*): the same table as vessel_table, bit for bit, updated from
+    the decoder's rows by kernels queued behind it -- at most max_rows rows per call -- so that the per-PDU table never
+    has to leave the device.  Only what a step changed is read back:
+
+        md = ais_amd.pdu_decode_batch(nchan, max_pdus, 64)
+        vt = ais_amd.vessel_table_batch(1 << 20, max_pdus)
+        hd.work(r["bits"], r["produced"], stream=s)      # deframe step k on s
+        md.work(hd, stream=s)                            # decode its PDUs
+        vt.work(md, stamp=k, stream=s, deframer=hd)      # and merge them, still on s: nothing waits
+        for v in vt.changed(stream=s):                   # the vessels step k touched (v["vessel"] = the index)
+            ...
+        vt.expire(k - 600, stream=s)                     # now and then: forget who fell silent
+
+    results_device() gives the table where it is, as torch views."""
+
+    def __init__(self, capacity, max_rows):
+        h = C.c_void_p()
+        check(_lib.lib().aisx_track_batch_create(C.byref(h), int(capacity), int(max_rows)), "vessel_table_batch")
+        self._h = h
+        self.capacity, self.max_rows = int(capacity), int(max_rows)
+        self.counts = dict.fromkeys(TRACK_COUNTS, 0)
+        self._cols = self._strs = self._idx = None  # read-back buffers of changed(), made on first use
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            _lib.lib().aisx_track_batch_destroy(h)
+            self._h = None
+
+    def reset(self):
+        check(_lib.lib().aisx_track_batch_reset(self._h), "vessel_table_batch.reset")
+
+    def work(self, decoder, stamp, stream=None, deframer=None):
+        """Merges the rows of the decoder's last call (queued on `stream`, default the current one; nothing waits),
+        count + 1 of them; deframer: the one whose records the decoder read, for the CHAN column."""
+        c, stride, s, n = decoder.results_device()
+        self.work_device(c, stride, s, n + 4, stamp, deframer.results_device()[0] if deframer is not None else None, stream)
+
+    def work_device(self, cols_ptr, col_stride, strs_ptr, nrows_ptr, stamp, pdus_ptr=None, stream=None):
+        """Device addresses: int32 cols [len(MSG_COLUMNS)][col_stride], char strs [rows][48], ONE int = rows to merge
+        and optionally the rows' aisx_pdu records.  Queued on `stream`; the count is read on the device."""
+        check(_lib.lib().aisx_track_batch_process(self._h, C.c_void_p(cols_ptr), int(col_stride), C.c_void_p(strs_ptr),
+                                                  C.c_void_p(pdus_ptr) if pdus_ptr else None, C.c_void_p(nrows_ptr), int(stamp),
+                                                  _stream_ptr(stream)), "vessel_table_batch.work")
+
+    def expire(self, min_stamp, stream=None):
+        """queues the removal of every vessel whose STAMP is below min_stamp (counts()["removed"] tells how many)"""
+        check(_lib.lib().aisx_track_batch_expire(self._h, int(min_stamp), _stream_ptr(stream)), "vessel_table_batch.expire")
+
+    def get_counts(self, stream=None):
+        """the counts as a dict of TRACK_COUNTS (synchronises `stream`)"""
+        cnt = np.zeros(len(TRACK_COUNTS), dtype=np.int32)
+        check(_lib.lib().aisx_track_batch_counts(self._h, cnt.ctypes.data_as(C.c_void_p), _stream_ptr(stream)),
+              "vessel_table_batch.counts")
+        self.counts = {k: int(v) for k, v in zip(TRACK_COUNTS, cnt)}
+        return self.counts
+
+    def results_device(self):
+        """torch views of the table where it is: {"cols": int32 [len(TRACK_COLUMNS)][capacity], "strs": uint8
+        [capacity][48], "changed": int32 [max_rows], "count": int32 [len(TRACK_COUNTS)]}.  An expire() moves the table
+        to the handle's other buffer: ask again after one."""
+        c, s, i, n, stride = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_long()
+        check(_lib.lib().aisx_track_batch_results_device(self._h, C.byref(c), C.byref(stride), C.byref(s), C.byref(i), C.byref(n)),
+              "vessel_table_batch.results_device")
+        dev = torch.device("cuda", torch.cuda.current_device())
+
+        class _Mem:  # (the handle owns the memory: a view keeps the handle alive through `owner`)
+            def __init__(self, owner, ptr, shape, typestr):
+                self.owner = owner
+                self.__cuda_array_interface__ = dict(shape=shape, typestr=typestr, data=(ptr, False), version=3)
+
+        return {"cols": torch.as_tensor(_Mem(self, c.value, (len(TRACK_COLUMNS), stride.value), "<i4"), device=dev),
+                "strs": torch.as_tensor(_Mem(self, s.value, (self.capacity, _lib.AISX_MSG_STR), "|u1"), device=dev),
+                "changed": torch.as_tensor(_Mem(self, i.value, (self.max_rows,), "<i4"), device=dev),
+                "count": torch.as_tensor(_Mem(self, n.value, (len(TRACK_COUNTS),), "<i4"), device=dev)}
+
+    def arrays(self, first=0, n=None, stream=None):
+        """(cols int32 [len(TRACK_COLUMNS)][k], strs uint8 [k][48]) of vessels [first, first + n) that exist
+        (synchronises `stream`); self.nvessels = vessels in the table"""
+        n = self.capacity if n is None else int(n)
+        cols = np.zeros((len(TRACK_COLUMNS), max(n, 1)), dtype=np.int32)
+        strs = np.zeros((max(n, 1), _lib.AISX_MSG_STR), dtype=np.uint8)
+        nv = C.c_int(0)
+        check(_lib.lib().aisx_track_batch_read(self._h, int(first), n, cols.ctypes.data_as(C.c_void_p), cols.shape[1],
+                                               strs.ctypes.data_as(C.c_void_p), C.byref(nv), _stream_ptr(stream)),
+              "vessel_table_batch.vessels")
+        self.nvessels = nv.value
+        k = max(0, min(n, nv.value - int(first)))
+        return cols[:, :k], strs[:k]
+
+    def vessels(self, first=0, n=None, stream=None):
+        """vessels [first, first + n) as a TRACK_DTYPE array (synchronises `stream`).  ValueError when a call since the
+        last read met a row count outside [0, max_rows] (it merged nothing)."""
+        cols, strs = self.arrays(first, n, stream)
+        return _track_table(cols, strs, cols.shape[1])
+
+    def changed_arrays(self, cap=None, stream=None):
+        """(idx int32 [k], cols int32 [len(TRACK_COLUMNS)][k], strs uint8 [k][48]) of the last update's changed list,
+        gathered on the device (synchronises `stream`).  OverflowError when more than `cap` vessels changed
+        (self.nchanged tells how many)."""
+        if self._cols is None:
+            self._idx = np.zeros(self.max_rows, dtype=np.int32)
+            self._cols = np.zeros((len(TRACK_COLUMNS), self.max_rows), dtype=np.int32)
+            self._strs = np.zeros((self.max_rows, _lib.AISX_MSG_STR), dtype=np.uint8)
+        cap = self.max_rows if cap is None else min(int(cap), self.max_rows)
+        nc = C.c_int(0)
+        rc = _lib.lib().aisx_track_batch_read_changed(self._h, self._idx.ctypes.data_as(C.c_void_p), self._cols.ctypes.data_as(C.c_void_p),
+                                                      self.max_rows, self._strs.ctypes.data_as(C.c_void_p), cap, C.byref(nc),
+                                                      _stream_ptr(stream))
+        self.nchanged = nc.value
+        check(rc, "vessel_table_batch.changed")
+        k = nc.value
+        return self._idx[:k].copy(), self._cols[:, :k].copy(), self._strs[:k].copy()
+
+    def changed(self, cap=None, stream=None):
+        """the vessels the last update merged a row into, ordered by the first row that touched each: a
+        TRACK_CHANGED_DTYPE array (field "vessel" = the index)"""
+        idx, cols, strs = self.changed_arrays(cap, stream)
+        return _track_table(cols, strs, len(idx), idx)

@@ -826,10 +826,14 @@ class ais_rx:
 
     decode=True queues the ITU-R M.1371 field decoder behind the NMEA stage; pop_messages() then returns (block,
     records, text, messages) with one MSG_DTYPE row (mmsi, lon, lat, sog, cog, name ...) per record.
+
+    tracks=capacity (implies decode=True) also keeps a vessel table of that many vessels on the device, merged from
+    every block's messages behind the decoder with stamp = the block's number: read_tracks() gives the table,
+    read_changed_tracks() the vessels the last issued block touched.
     """
 
     def __init__(self, freq, rate, designator, nstreams=1, fmt="cf32", scale=1.0, bias=0.0, block_items=None,
-                 preamble_symbols=None, taps=None, max_pdus_per_block=1 << 16, decode=False):
+                 preamble_symbols=None, taps=None, max_pdus_per_block=1 << 16, decode=False, tracks=None):
         from .batch_framing import PDU_DTYPE
         from .modulate import gmsk_mod, modulate_vector_bc
 
@@ -877,8 +881,11 @@ class ais_rx:
         self.status = 0  # of the block popped last (AISX_MSK_ST_* | AISX_RX_ST_*)
         self.decode = False
         self._cols = self._strs = None
+        self.tracks = 0
         if decode:
             self.enable_messages()
+        if tracks:
+            self.enable_tracks(tracks)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -963,6 +970,41 @@ class ais_rx:
         self.status = st.value
         return (b.value, self._recs[: nr.value].copy(), self._text[: tl.value].tobytes(),
                 msg_table(self._cols, self._strs, nr.value))
+
+    def enable_tracks(self, capacity):
+        """what tracks=capacity does: enable_messages(), and from the first block on the vessel table is updated
+        behind the decoder.  ValueError once a slot has been taken or a block pushed."""
+        check(_lib.lib().aisx_rx_enable_tracks(self._h, int(capacity)), "ais_rx.enable_tracks")
+        self.enable_messages()
+        self.tracks = int(capacity)
+
+    def read_tracks(self, first=0, n=None):
+        """(block, vessels): the table after the update of every block issued so far -- `block` the number of the
+        last of them (-1: none) -- as a TRACK_DTYPE array of vessels [first, first + n).  Waits for the tail stream."""
+        from .batch_framing import TRACK_COLUMNS, _track_table
+
+        n = self.tracks if n is None else int(n)
+        cols = np.zeros((len(TRACK_COLUMNS), max(n, 1)), dtype=np.int32)
+        strs = np.zeros((max(n, 1), _lib.AISX_MSG_STR), dtype=np.uint8)
+        nv, b = C.c_int(0), C.c_longlong(-1)
+        check(_lib.lib().aisx_rx_read_tracks(self._h, int(first), n, cols.ctypes.data_as(C.c_void_p), cols.shape[1],
+                                             strs.ctypes.data_as(C.c_void_p), C.byref(nv), C.byref(b)), "ais_rx.read_tracks")
+        return b.value, _track_table(cols, strs, max(0, min(n, nv.value - int(first))))
+
+    def read_changed_tracks(self):
+        """(block, vessels): the vessels the last issued block's update merged a row into, as a TRACK_CHANGED_DTYPE
+        array (field "vessel" = the index), ordered by the first row that touched each"""
+        from .batch_framing import TRACK_COLUMNS, _track_table
+
+        cap = max(self._recs.size, 1)
+        idx = np.zeros(cap, dtype=np.int32)
+        cols = np.zeros((len(TRACK_COLUMNS), cap), dtype=np.int32)
+        strs = np.zeros((cap, _lib.AISX_MSG_STR), dtype=np.uint8)
+        nc, b = C.c_int(0), C.c_longlong(-1)
+        check(_lib.lib().aisx_rx_read_changed_tracks(self._h, idx.ctypes.data_as(C.c_void_p), cols.ctypes.data_as(C.c_void_p), cap,
+                                                     strs.ctypes.data_as(C.c_void_p), cap, C.byref(nc), C.byref(b)),
+              "ais_rx.read_changed_tracks")
+        return b.value, _track_table(cols, strs, nc.value, idx)
 
     def set_center_freq(self, f, stream=None, chan=None):
         """from the next submitted block on; stream / chan None = all"""

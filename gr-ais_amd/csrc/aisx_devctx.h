@@ -261,6 +261,10 @@ struct DevCtx {
     __device__ __forceinline__ int ctz64(unsigned long long v) const { return __ffsll((long long)v) - 1; }
     __device__ __forceinline__ void atomic_or64(unsigned long long* p, unsigned long long v) const { atomicOr(p, v); }
     __device__ __forceinline__ int atomic_add_i32(int* p, int v) const { return atomicAdd(p, v); }
+    // k_track.h: the value before; the swap stores `desired` only where *p == expect
+    __device__ __forceinline__ int atomic_cas_i32(int* p, int expect, int desired) const { return atomicCAS(p, expect, desired); }
+    __device__ __forceinline__ int atomic_min_i32(int* p, int v) const { return atomicMin(p, v); }
+    __device__ __forceinline__ int atomic_max_i32(int* p, int v) const { return atomicMax(p, v); }
 
     // ---- raw buffers and LDS-DMA (k_corr4d.h) ------------------------------------------------
     // A raw buffer: wave-uniform base + byte count; an access whose byte offset (the VGPR part)

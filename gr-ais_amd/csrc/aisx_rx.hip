@@ -1,7 +1,8 @@
 // aisx_rx.hip -- C ABI of the host-fed receiver (include/aisx.h, aisx_rx_*): python/radio.py's ais_rx as one handle
 // for nstreams sources, fed from pinned host memory in the source's own sample format.  Nothing here computes: the
 // handle owns the filter (aisx_xlate), the four stage handles and their chain, the deframer and the NMEA stage (and,
-// once aisx_rx_enable_messages asked for it, the field decoder behind that), and the rings, streams and events that
+// once aisx_rx_enable_messages asked for it, the field decoder behind that, and after aisx_rx_enable_tracks the vessel
+// table behind the decoder), and the rings, streams and events that
 // order them (INTEGRATION.md states the rules; this file is their one home).
 //
 //   block b, submitted:   copy stream    pinned slot b % NPIN -> raw buffer b % NRAW      (after filter b - NRAW)
@@ -99,6 +100,7 @@ struct aisx_rx {
     const int32_t* d_mg_cols = nullptr;
     const char* d_mg_strs = nullptr;
     const int* d_mg_count = nullptr;
+    aisx_track_batch* tk = nullptr;    // only after aisx_rx_enable_tracks: the vessel table, updated behind the decoder
     Stream s_copy, s_filt, s_tail;     // (before the buffers and events used on them: destroyed after those)
     PinnedBuf<char> h_in[RX_NPIN];     // pinned [ns][block_items] items
     DevBuf<char> d_raw[RX_NRAW];
@@ -149,6 +151,7 @@ extern "C" int aisx_rx_destroy(aisx_rx* h)
     }
     if (h->s_tail)
         (void)hipStreamSynchronize(h->s_tail);
+    (void)aisx_track_batch_destroy(h->tk);
     (void)aisx_msg_batch_destroy(h->mg);
     (void)aisx_nmea_batch_destroy(h->nm);
     (void)aisx_hdlc_batch_destroy(h->hd);
@@ -363,6 +366,9 @@ static int rx_issue(aisx_rx* h, long long k, const cf* next)
     char* r = h->h_res[res];
     if (h->mg) { // the rows of the records the NMEA stage kept; its bad-input flag goes into the record's spare word
         if ((rc = aisx_msg_batch_process(h->mg, h->d_hd_pdus, h->d_hd_bytes, h->d_nm_count + 1, h->d_hd_count, st)) != AISX_OK)
+            return rc;
+        if (h->tk && (rc = aisx_track_batch_process(h->tk, h->d_mg_cols, h->max_pdus, h->d_mg_strs, h->d_hd_pdus, h->d_mg_count + 1,
+                                                    (int32_t)k, st)) != AISX_OK)
             return rc;
         AISX_HIPCHK(hipMemcpyAsync(h->d_meta + 7, h->d_mg_count + 2, sizeof(int), hipMemcpyDeviceToDevice, st));
         AISX_HIPCHK(hipMemsetAsync((void*)(h->d_mg_count + 2), 0, sizeof(int), st));
@@ -601,6 +607,63 @@ extern "C" int aisx_rx_pop_messages(aisx_rx* h, int wait, long long* block, char
     }
     return rx_pop(h, "aisx_rx_pop_messages", wait, block, text, text_cap, text_len, recs, rec_cap, nrecs, rec_cap > 0 ? cols : nullptr,
                   col_stride, strs, status);
+}
+
+extern "C" int aisx_rx_enable_tracks(aisx_rx* h, int capacity)
+{
+    if (!h) {
+        set_err("aisx_rx_enable_tracks: need a handle");
+        return AISX_ERR_INVALID;
+    }
+    if (h->failed != AISX_OK)
+        return rx_failed(h, "aisx_rx_enable_tracks");
+    if (h->tk || h->acquired || h->submitted > 0) {
+        set_err("aisx_rx_enable_tracks: once, and only before the first acquire, submit or push");
+        return AISX_ERR_INVALID;
+    }
+    OnDevice on(h->dev);
+    AISX_HIPCHK(on.err);
+    aisx_track_batch* made = nullptr;
+    int rc = aisx_track_batch_create(&made, capacity, h->max_pdus);
+    HandlePtr<aisx_track_batch, aisx_track_batch_destroy> tk(made);
+    if (rc == AISX_OK)
+        rc = aisx_rx_enable_messages(h);
+    if (rc != AISX_OK) { // (the handle stays as it was)
+        const std::string msg = aisx_last_error();
+        tk.reset();
+        set_err("%s", msg.c_str());
+        return rc;
+    }
+    h->tk = tk.release();
+    return AISX_OK;
+}
+
+// the two reads of the table, on the tail stream: behind the update of every block issued so far
+static int rx_tracks_ready(aisx_rx* h, const char* who, long long* block)
+{
+    if (!h || !h->tk) {
+        set_err("%s: need a handle on which aisx_rx_enable_tracks was called", who);
+        return AISX_ERR_INVALID;
+    }
+    if (h->failed != AISX_OK)
+        return rx_failed(h, who);
+    if (block)
+        *block = h->issued - 1;
+    return AISX_OK;
+}
+
+extern "C" int aisx_rx_read_tracks(aisx_rx* h, int first, int n, int32_t* cols, long col_stride, char* strs, int* nvessels,
+                                   long long* block)
+{
+    const int rc = rx_tracks_ready(h, "aisx_rx_read_tracks", block);
+    return rc != AISX_OK ? rc : aisx_track_batch_read(h->tk, first, n, cols, col_stride, strs, nvessels, (hipStream_t)h->s_tail);
+}
+
+extern "C" int aisx_rx_read_changed_tracks(aisx_rx* h, int* idx, int32_t* cols, long col_stride, char* strs, int cap, int* nchanged,
+                                           long long* block)
+{
+    const int rc = rx_tracks_ready(h, "aisx_rx_read_changed_tracks", block);
+    return rc != AISX_OK ? rc : aisx_track_batch_read_changed(h->tk, idx, cols, col_stride, strs, cap, nchanged, (hipStream_t)h->s_tail);
 }
 
 extern "C" int aisx_rx_set_center_freq(aisx_rx* h, int stream, int chan, double center_freq)

@@ -684,6 +684,92 @@ int aisx_msg_batch_read(aisx_msg_batch* h, int32_t* cols, long col_stride, char*
                         void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* the vessel table: the latest state per MMSI, merged from decoded tables    */
+/* call by call -- on the host (the specification), and in device memory,     */
+/* queued behind the field decoder                                            */
+/* ------------------------------------------------------------------------ */
+/* Columns of a vessel: the message columns with their indices, then */
+enum {
+    AISX_TRK_COL_COUNT = AISX_MSG_NCOL, /* rows merged into the vessel (stays at INT32_MAX once there) */
+    AISX_TRK_COL_STAMP,                 /* the stamp of the last update that merged a row */
+    AISX_TRK_COL_POS_STAMP,             /* ... that merged a row with LON and LAT both not AISX_MSG_NA; NA until then */
+    AISX_TRK_COL_CHAN,                  /* chan of the last merged row's PDU record; NA when no record list was given */
+    AISX_TRK_NCOL
+};
+/* what an update or expire reports: int counts[AISX_TRK_NCNT] */
+enum {
+    AISX_TRK_CNT_VESSELS = 0, /* vessels in the table */
+    AISX_TRK_CNT_MERGED,      /* the last update: rows merged, */
+    AISX_TRK_CNT_SKIPPED,     /* rows with AISX_MSG_FL_BAD_RECORD or without an MMSI, */
+    AISX_TRK_CNT_DROPPED,     /* rows of an unknown MMSI that met a full table, */
+    AISX_TRK_CNT_CHANGED,     /* vessels that merged at least one row (0 after an expire) */
+    AISX_TRK_CNT_REMOVED,     /* the last expire: vessels removed */
+    AISX_TRK_CNT_FULL,        /* the last update dropped a row */
+    AISX_TRK_CNT_BAD_INPUT,   /* device form only: a row count outside [0, max_rows] since the last read */
+    AISX_TRK_NCNT
+};
+/* The table holds `capacity` vessels as a struct of arrays, int32_t cols[AISX_TRK_NCOL][capacity] and char
+ * strs[capacity][AISX_MSG_STR]; vessel v is the v-th distinct MMSI ever accepted, in order of first appearance, so the
+ * table is dense in [0, nvessels).  An update takes the rows of a decoded table (the layout of aisx_msg_decode /
+ * aisx_msg_batch_read; recs, optional, the PDU records the rows were decoded from) in ascending row order:
+ *   - a row with AISX_MSG_FL_BAD_RECORD, or whose MMSI is AISX_MSG_NA, is skipped;
+ *   - a row of an unknown MMSI creates vessel nvessels++ (every column NA, strings NUL, COUNT 0), or is dropped when
+ *     the table is full;
+ *   - every message column of the row that is not NA replaces the vessel's (TYPE, REPEAT, MMSI and FLAGS always do),
+ *     every string slot ([0, 8), [8, 28), [28, 48)) whose first byte is not NUL replaces the vessel's slot whole;
+ *   - COUNT, STAMP, POS_STAMP and CHAN are set as described above.
+ * Values are kept as transmitted: the protocol's own "not available" codes (longitude 181 degrees, speed 1023 ...) are
+ * values like any other and replace what was known; mapping them is the caller's business.  Every int32 but
+ * AISX_MSG_NA is an MMSI (0 and 2^30 - 1 included).  The changed list of an update: the vessels that merged a row,
+ * ordered by the first row that touched each.  Plain C++, no device.  1 <= capacity <= 2^24. */
+typedef struct aisx_track aisx_track;
+int aisx_track_create(aisx_track** h, int capacity);
+int aisx_track_destroy(aisx_track* h);
+/* cols [AISX_MSG_NCOL][col_stride] (col_stride >= n), strs [n][AISX_MSG_STR], recs [n] or NULL, counts
+ * [AISX_TRK_NCNT] or NULL */
+int aisx_track_update(aisx_track* h, const int32_t* cols, long col_stride, const char* strs, const aisx_pdu* recs, int n,
+                      int32_t stamp, int* counts);
+/* removes every vessel whose STAMP is below min_stamp; the others keep their order and are renumbered from 0; the
+ * changed list becomes empty */
+int aisx_track_expire(aisx_track* h, int32_t min_stamp, int* counts);
+/* the table where it is (valid until the next update or expire): column c is *cols + c * *col_stride */
+int aisx_track_data(const aisx_track* h, const int32_t** cols, long* col_stride, const char** strs, int* nvessels);
+int aisx_track_changed(const aisx_track* h, const int** idx, int* nchanged);
+
+typedef struct aisx_track_batch aisx_track_batch;
+/* The same table on the device that was current here, updated from at most max_rows (<= 2^24) rows per call: two
+ * table buffers (expire compacts from one into the other), an open-addressing hash from MMSI to vessel of at least
+ * 2 * capacity slots, and a workspace in proportion to max_rows.  Table, changed list and counts equal the host
+ * form's, bit for bit, whatever order the device ran the rows in. */
+int aisx_track_batch_create(aisx_track_batch** h, int capacity, int max_rows);
+int aisx_track_batch_destroy(aisx_track_batch* h);
+int aisx_track_batch_reset(aisx_track_batch* h); /* an empty table; waits for the work queued before */
+/* d_cols / col_stride / d_strs as aisx_msg_batch_results_device gives them, d_pdus the records the rows were decoded
+ * from (or NULL), d_nrows ONE int on the device (for the decoder: d_count + 1).  Queued on `stream`; no host sync.  A
+ * count outside [0, max_rows] merges nothing and makes the next read say so. */
+int aisx_track_batch_process(aisx_track_batch* h, const int32_t* d_cols, long col_stride, const char* d_strs,
+                             const aisx_pdu* d_pdus, const int* d_nrows, int32_t stamp, void* stream);
+int aisx_track_batch_expire(aisx_track_batch* h, int32_t min_stamp, void* stream);
+/* the table in device memory: column c is d_cols + c * *col_stride (*col_stride = capacity), vessel v's strings
+ * d_strs + v * AISX_MSG_STR, d_changed [max_rows], d_count [AISX_TRK_NCNT].  d_cols and d_strs name the buffer that
+ * holds the table once the calls queued so far have run: an expire moves the table to the other one. */
+int aisx_track_batch_results_device(const aisx_track_batch* h, const int32_t** d_cols, long* col_stride,
+                                    const char** d_strs, const int** d_changed, const int** d_count);
+/* copies vessels [first, first + n) that exist to the host (synchronises `stream`): cols [AISX_TRK_NCOL][col_stride]
+ * with col_stride >= n, strs [n][AISX_MSG_STR]; *nvessels = vessels in the table.  AISX_ERR_INVALID when a call since
+ * the previous read met a bad count (the flag is then cleared). */
+int aisx_track_batch_read(aisx_track_batch* h, int first, int n, int32_t* cols, long col_stride, char* strs, int* nvessels,
+                          void* stream);
+/* d_count on the host (synchronises `stream`); the bad-input flag is reported and left as it is */
+int aisx_track_batch_counts(aisx_track_batch* h, int* counts, void* stream);
+/* the vessels of the last update's changed list, gathered on the device into one block and copied (synchronises
+ * `stream`): idx [cap], cols [AISX_TRK_NCOL][col_stride] with col_stride >= cap, strs [cap][AISX_MSG_STR], row j for
+ * vessel idx[j]; *nchanged = the list's length.  When cap is smaller than that: AISX_ERR_OVERFLOW, nothing copied.
+ * AISX_ERR_INVALID after a bad count, as aisx_track_batch_read. */
+int aisx_track_batch_read_changed(aisx_track_batch* h, int* idx, int32_t* cols, long col_stride, char* strs, int cap,
+                                  int* nchanged, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* ais_rx (python/radio.py:40-73) as ONE handle, fed from host memory in the  */
 /* source's own sample format: freq_xlating_fir_filter_ccf -> ais_demod ->    */
 /* hdlc_deframer_bp -> pdu_to_nmea for nstreams sources at once               */
@@ -749,6 +835,20 @@ int aisx_rx_enable_messages(aisx_rx* h);
  * AISX_ERR_INVALID on a handle without messages enabled. */
 int aisx_rx_pop_messages(aisx_rx* h, int wait, long long* block, char* text, long text_cap, long* text_len, aisx_pdu* recs,
                          int rec_cap, int* nrecs, int32_t* cols, long col_stride, char* strs, int* status);
+/* Opt-in, and implies aisx_rx_enable_messages: the handle also owns a vessel table of `capacity` vessels
+ * (aisx_track_batch_*, max_rows = max_pdus_per_block), and from the first block on the tail stream queues its update
+ * behind the field decoder, with stamp = the block's number (its low 32 bits) and the deframer's records for CHAN.
+ * Only before the first acquire, submit or push (AISX_ERR_INVALID afterwards); a handle on which this was never called
+ * allocates and queues nothing more.  The result slots do not carry the changed list: it is read on request. */
+int aisx_rx_enable_tracks(aisx_rx* h, int capacity);
+/* aisx_track_batch_read / aisx_track_batch_read_changed of the handle's table, queued on the tail stream (so behind
+ * the update of every block issued so far; the calling thread waits for them): *block (optional) = the number of the
+ * last block whose update the result includes, -1 before the first.  aisx_rx_read_changed_tracks gives that block's
+ * changed list.  AISX_ERR_INVALID on a handle without tracks enabled. */
+int aisx_rx_read_tracks(aisx_rx* h, int first, int n, int32_t* cols, long col_stride, char* strs, int* nvessels,
+                        long long* block);
+int aisx_rx_read_changed_tracks(aisx_rx* h, int* idx, int32_t* cols, long col_stride, char* strs, int cap, int* nchanged,
+                                long long* block);
 /* from the next submitted block on (aisx_xlate_set_center_freq of the handle's filter) */
 int aisx_rx_set_center_freq(aisx_rx* h, int stream, int chan, double center_freq);
 /* A failed block (a HIP error, the chain refusing) makes every later call but destroy return that block's error. */
