@@ -21,7 +21,7 @@ HW_QUEUES_SET_TOO_LATE = "GPU_MAX_HW_QUEUES" not in _os.environ and _t is not No
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 del _t
 
-from .framing import MSG_COLUMNS, MSG_DTYPE, MSG_NA, hdlc_deframer_bp, msg_decode, pdu_to_nmea  # noqa: F401
+from .framing import AIS_REPAIR_RULES, MSG_COLUMNS, MSG_DTYPE, MSG_NA, hdlc_deframer_bp, msg_decode, pdu_to_nmea  # noqa: F401
 from .modulate import gmsk_mod, modulate_vector_bc  # noqa: F401
 
 

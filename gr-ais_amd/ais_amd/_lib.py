@@ -24,6 +24,7 @@ AISX_ERR_RUNTIME = -6
 AISX_FMT_CF32, AISX_FMT_CS16, AISX_FMT_CS8, AISX_FMT_CU8 = 0, 1, 2, 3
 AISX_RX_ST_HDLC_OVERFLOW, AISX_RX_ST_NMEA_OVERFLOW, AISX_RX_ST_BAD_COUNT = 0x100, 0x200, 0x400
 AISX_MSG_NA, AISX_MSG_STR = -(1 << 31), 48
+AISX_HDLC_MAX_RULES = 16
 AISX_MSG_FL_COMPLETE, AISX_MSG_FL_NO_LAYOUT, AISX_MSG_FL_BAD_RECORD = 1, 2, 4
 
 KEY_CORR_START, KEY_PHASE_EST, KEY_TIME_EST, KEY_CORR_EST, KEY_PORT1 = 0, 1, 2, 3, 0x100
@@ -200,6 +201,8 @@ def lib(device=True):
     sig("aisx_hdlc_create", i32, [pvp, i32, i32])
     sig("aisx_hdlc_destroy", i32, [vp])
     sig("aisx_hdlc_work", i32, [vp, vp, i32, vp, i32, vp, i32, pi32])
+    sig("aisx_hdlc_set_repair", i32, [vp, vp, i32])
+    sig("aisx_hdlc_work_repair", i32, [vp, vp, i32, vp, i32, vp, vp, i32, pi32])
     sig("aisx_pdu_to_nmea", i32, [C.c_char_p, vp, i32, C.c_char_p, i32])
     sig("aisx_hdlc_batch_create", i32, [pvp, i32, i32, i32, i32, i32])
     sig("aisx_hdlc_batch_destroy", i32, [vp])
@@ -207,6 +210,11 @@ def lib(device=True):
     sig("aisx_hdlc_batch_process", i32, [vp, vp, lng, vp, vp])
     sig("aisx_hdlc_batch_results_device", i32, [vp, pvp, pvp, pvp])
     sig("aisx_hdlc_batch_read", i32, [vp, vp, i32, vp, lng, pi32, vp])
+    sig("aisx_hdlc_batch_set_repair", i32, [vp, vp, i32])
+    sig("aisx_hdlc_batch_repairs_device", i32, [vp, pvp])
+    sig("aisx_hdlc_batch_read_repairs", i32, [vp, vp, i32, pi32, vp])
+    sig("aisx_rx_enable_repair", i32, [vp, vp, i32])
+    sig("aisx_rx_popped_repairs", i32, [vp, vp, i32, pi32])
     sig("aisx_nmea_batch_create", i32, [pvp, C.POINTER(C.c_char_p), i32, i32, i32, lng])
     sig("aisx_nmea_batch_destroy", i32, [vp])
     sig("aisx_nmea_batch_process", i32, [vp, vp, vp, vp, vp, vp])

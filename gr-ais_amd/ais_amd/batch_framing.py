@@ -39,7 +39,7 @@ class hdlc_deframer_batch:
     writes its zero counts on another of the chain's streams; aisx_chain_wait orders every path.  A step's
     outputs rotate through AISX_CHAIN_DEPTH sets, so work() must be queued before the call that reuses them."""
 
-    def __init__(self, length_min, length_max, nchan, max_bits, max_pdus):
+    def __init__(self, length_min, length_max, nchan, max_bits, max_pdus, repair=None):
         h = C.c_void_p()
         check(_lib.lib().aisx_hdlc_batch_create(C.byref(h), int(length_min), int(length_max), int(nchan), int(max_bits),
                                                 int(max_pdus)), "hdlc_deframer_batch")
@@ -49,12 +49,31 @@ class hdlc_deframer_batch:
         self.found = 0  # PDUs the last call found (kept or not)
         self._recs = np.zeros(self.max_pdus, dtype=PDU_DTYPE)  # read-back buffers, reused by every call
         self._data = np.zeros(self.max_pdus * (self.length_max - 1) + 1, dtype=np.uint8)
+        self._fix = None  # read-back buffer of the repair marks, made on first use
+        if repair is not None:
+            self.set_repair(repair)
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h and _lib is not None:
             _lib.lib().aisx_hdlc_batch_destroy(h)
             self._h = None
+
+    def set_repair(self, rules):
+        """Single-bit repair by CRC syndrome for every channel (hdlc_deframer_bp.set_repair's rules, its results):
+        waits for the handle's queued work, applies from the next work() on.  None or empty: off."""
+        from .framing import repair_rules
+
+        r = repair_rules(rules)
+        check(_lib.lib().aisx_hdlc_batch_set_repair(self._h, r.ctypes.data_as(C.c_void_p) if r.size else None, r.size),
+              "hdlc_deframer_batch.set_repair")
+
+    def repairs_device(self):
+        """device address of the last call's repair marks (int32 [max_pdus], entry k for record k of results_device():
+        -1 = delivered as received, else the flipped bit's index in the frame)"""
+        p = C.c_void_p()
+        check(_lib.lib().aisx_hdlc_batch_repairs_device(self._h, C.byref(p)), "hdlc_deframer_batch.repairs_device")
+        return p.value
 
     def reset(self):
         check(_lib.lib().aisx_hdlc_batch_reset(self._h), "hdlc_deframer_batch.reset")
@@ -77,12 +96,13 @@ class hdlc_deframer_batch:
               "hdlc_deframer_batch.results_device")
         return p.value, b.value, n.value
 
-    def pdus(self, stream=None, as_list=False, overflow_ok=False):
+    def pdus(self, stream=None, as_list=False, overflow_ok=False, with_repairs=False):
         """The last call's PDUs (synchronises `stream`): (records, bytes) with records a PDU_DTYPE array (chan,
         end_bit, len, offset into bytes), or with as_list=True a list of (chan, end_bit, payload bytes).  When
         more than max_pdus were found, OverflowError -- or with overflow_ok=True the first max_pdus (self.found
         tells how many there were).  ValueError when a call since the last read met a count outside
-        [0, max_bits] (that channel was not advanced)."""
+        [0, max_bits] (that channel was not advanced).  with_repairs=True: a third item, the records' repair marks
+        (int32 array: -1 = delivered as received, else the flipped bit's index) -- in the list form a fourth field."""
         recs, data = self._recs, self._data
         n = C.c_int(0)
         rc = _lib.lib().aisx_hdlc_batch_read(self._h, recs.ctypes.data_as(C.c_void_p), self.max_pdus,
@@ -93,6 +113,19 @@ class hdlc_deframer_batch:
         recs = recs[: min(n.value, self.max_pdus)].copy()
         nb = int(recs["offset"][-1] + recs["len"][-1]) if len(recs) else 0
         data = data[:nb].copy()
+        if with_repairs:
+            if self._fix is None:
+                self._fix = np.zeros(self.max_pdus, dtype=np.int32)
+            m = C.c_int(0)
+            rc = _lib.lib().aisx_hdlc_batch_read_repairs(self._h, self._fix.ctypes.data_as(C.c_void_p), self.max_pdus, C.byref(m),
+                                                         _stream_ptr(stream))
+            if not (rc == _lib.AISX_ERR_OVERFLOW and overflow_ok):
+                check(rc, "hdlc_deframer_batch.pdus")
+            fix = self._fix[: len(recs)].copy()
+            if as_list:
+                return [(int(r["chan"]), int(r["end_bit"]), bytes(data[r["offset"]:r["offset"] + r["len"]]), int(f))
+                        for r, f in zip(recs, fix)]
+            return recs, data, fix
         if as_list:
             return [(int(r["chan"]), int(r["end_bit"]), bytes(data[r["offset"]:r["offset"] + r["len"]])) for r in recs]
         return recs, data

@@ -830,10 +830,14 @@ class ais_rx:
     tracks=capacity (implies decode=True) also keeps a vessel table of that many vessels on the device, merged from
     every block's messages behind the decoder with stamp = the block's number: read_tracks() gives the table,
     read_changed_tracks() the vessels the last issued block touched.
+
+    repair=rules (ais_amd.AIS_REPAIR_RULES, or as ais_amd.hdlc_deframer_bp takes them) turns the deframer's single-bit
+    repair on: a burst with one wrong bit still gives its sentence, and popped_repairs() tells which records of the
+    block popped last were put right.
     """
 
     def __init__(self, freq, rate, designator, nstreams=1, fmt="cf32", scale=1.0, bias=0.0, block_items=None,
-                 preamble_symbols=None, taps=None, max_pdus_per_block=1 << 16, decode=False, tracks=None):
+                 preamble_symbols=None, taps=None, max_pdus_per_block=1 << 16, decode=False, tracks=None, repair=None):
         from .batch_framing import PDU_DTYPE
         from .modulate import gmsk_mod, modulate_vector_bc
 
@@ -882,6 +886,9 @@ class ais_rx:
         self.decode = False
         self._cols = self._strs = None
         self.tracks = 0
+        self.repair = False
+        if repair is not None:
+            self.enable_repair(repair)
         if decode:
             self.enable_messages()
         if tracks:
@@ -970,6 +977,26 @@ class ais_rx:
         self.status = st.value
         return (b.value, self._recs[: nr.value].copy(), self._text[: tl.value].tobytes(),
                 msg_table(self._cols, self._strs, nr.value))
+
+    def enable_repair(self, rules):
+        """what repair=rules does: the deframer repairs single-bit errors by these rules from the first block on.
+        ValueError once a slot has been taken or a block pushed, and for rules the deframer (11, 64) cannot take."""
+        from .framing import repair_rules
+
+        r = repair_rules(rules)
+        check(_lib.lib().aisx_rx_enable_repair(self._h, r.ctypes.data_as(C.c_void_p) if r.size else None, r.size),
+              "ais_rx.enable_repair")
+        self.repair = True
+
+    def popped_repairs(self):
+        """the repair marks of the block popped last (by pop() or pop_messages()), one per record: an int32 array, -1 for
+        a frame delivered as received, else the index of the flipped bit in the frame (payload + FCS, bit 0 the first
+        received).  Needs repair= (ValueError otherwise)."""
+        fix = np.zeros(self._recs.size, dtype=np.int32)
+        n = C.c_int(0)
+        check(_lib.lib().aisx_rx_popped_repairs(self._h, fix.ctypes.data_as(C.c_void_p), fix.size, C.byref(n)),
+              "ais_rx.popped_repairs")
+        return fix[: n.value].copy()
 
     def enable_tracks(self, capacity):
         """what tracks=capacity does: enable_messages(), and from the first block on the vessel table is updated

@@ -11,12 +11,55 @@ from . import _lib
 from ._lib import check
 
 
+RULE_DTYPE = np.dtype([("payload_octets", "<i4"), ("reserved", "<i4"), ("type_mask", "<u8")])  # aisx_hdlc_rule
+ANY_TYPE = (1 << 64) - 1
+# Single-bit repair rules for the ITU-R M.1371 messages of fixed length: {payload octets: the message types sent at that
+# length}.  168 bits: 1-3 and 4 / 11, 9, 18, 24 part B; 424: 5; 312: 19; 160: 24 part A; 96: 27.
+AIS_REPAIR_RULES = {21: (1, 2, 3, 4, 9, 11, 18, 24), 53: (5,), 39: (19,), 20: (24,), 12: (27,)}
+
+
+def repair_rules(rules):
+    """rules as the deframers take them -> an aisx_hdlc_rule array: None or empty (repair off), a dict {payload octets:
+    iterable of message types, or None / ANY_TYPE for any content}, or a sequence of (payload octets, type mask)"""
+    if rules is None:
+        return np.zeros(0, dtype=RULE_DTYPE)
+    if isinstance(rules, np.ndarray) and rules.dtype == RULE_DTYPE:
+        return np.ascontiguousarray(rules)
+    items = list(rules.items()) if isinstance(rules, dict) else list(rules)
+    out = np.zeros(len(items), dtype=RULE_DTYPE)
+    for k, (octets, types) in enumerate(items):
+        if types is None:
+            types = ANY_TYPE
+        if not isinstance(types, (int, np.integer)):
+            mask = 0
+            for t in types:
+                if not 0 <= int(t) < 64:
+                    raise ValueError("repair rules: a message type is 0..63, got %r" % (t,))
+                mask |= 1 << int(t)
+            types = mask
+        out[k] = (int(octets), 0, int(types) & ANY_TYPE)
+    return out
+
+
 class hdlc_deframer_bp:
-    def __init__(self, length_min, length_max):
+    """digital.hdlc_deframer_bp(length_min, length_max).  repair: single-bit repair rules (repair_rules() says how
+    they are written, AIS_REPAIR_RULES is a ready set): a frame whose CRC fails by one wrong bit, of a length and
+    message type the rules allow, is put right and delivered; work(bits, with_repairs=True) marks those."""
+
+    def __init__(self, length_min, length_max, repair=None):
         h = C.c_void_p()
         check(_lib.lib(device=False).aisx_hdlc_create(C.byref(h), int(length_min), int(length_max)), "hdlc_deframer_bp")
         self._h = h
         self._max = int(length_max)
+        if repair is not None:
+            self.set_repair(repair)
+
+    def set_repair(self, rules):
+        """from the next frame that closes on; None or empty: off.  ValueError for rules the handle cannot take (more
+        than 16, a length outside [length_min - 2, length_max - 2] or given twice): it keeps the ones it had."""
+        r = repair_rules(rules)
+        check(_lib.lib(device=False).aisx_hdlc_set_repair(self._h, r.ctypes.data_as(C.c_void_p) if r.size else None, r.size),
+              "hdlc_deframer_bp.set_repair")
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -24,16 +67,24 @@ class hdlc_deframer_bp:
             _lib.lib(device=False).aisx_hdlc_destroy(h)
             self._h = None
 
-    def work(self, bits):
-        """bits: unpacked bits (one per item).  Returns the list of PDUs (bytes) whose CRC checked."""
+    def work(self, bits, with_repairs=False):
+        """bits: unpacked bits (one per item).  Returns the list of PDUs (bytes) whose CRC checked -- or, with repair
+        rules, was made to by flipping one bit.  with_repairs=True: (PDUs, marks), a mark -1 for a frame delivered as
+        received, else the index of the flipped bit in the frame (payload + FCS, bit 0 the first received)."""
         b = np.ascontiguousarray(bits, dtype=np.uint8)
         maxp = b.size // 16 + 2
         buf = np.zeros(maxp * (self._max + 2), dtype=np.uint8)
         offs = np.zeros(maxp + 1, dtype=np.int32)
         n = C.c_int(0)
-        check(_lib.lib(device=False).aisx_hdlc_work(self._h, b.ctypes.data_as(C.c_void_p), b.size, buf.ctypes.data_as(C.c_void_p),
-                                        buf.size, offs.ctypes.data_as(C.c_void_p), maxp, C.byref(n)), "hdlc work")
-        return [bytes(buf[offs[k]:offs[k + 1]]) for k in range(n.value)]
+        if not with_repairs:
+            check(_lib.lib(device=False).aisx_hdlc_work(self._h, b.ctypes.data_as(C.c_void_p), b.size, buf.ctypes.data_as(C.c_void_p),
+                                            buf.size, offs.ctypes.data_as(C.c_void_p), maxp, C.byref(n)), "hdlc work")
+            return [bytes(buf[offs[k]:offs[k + 1]]) for k in range(n.value)]
+        fix = np.full(maxp, -1, dtype=np.int32)
+        check(_lib.lib(device=False).aisx_hdlc_work_repair(self._h, b.ctypes.data_as(C.c_void_p), b.size, buf.ctypes.data_as(C.c_void_p),
+                                                           buf.size, offs.ctypes.data_as(C.c_void_p), fix.ctypes.data_as(C.c_void_p),
+                                                           maxp, C.byref(n)), "hdlc work")
+        return [bytes(buf[offs[k]:offs[k + 1]]) for k in range(n.value)], [int(v) for v in fix[: n.value]]
 
 
 class pdu_to_nmea:

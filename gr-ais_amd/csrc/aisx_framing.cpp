@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/aisx.h"
+#include "aisx_repair.h"
 
 namespace {
 
@@ -50,6 +51,33 @@ const X25Fcs& fcs()
     return f;
 }
 
+// Single-error syndromes of the FCS check.  The CRC is linear, so one wrong bit at distance d from the frame's last
+// bit (d = 0: the FCS's last bit) changes (computed FCS) xor (sent FCS) by a value that depends on d alone:
+// 0x8000 for d = 0, one more step of the shift register for every bit further from the end.  The values repeat after
+// 32767 steps; the first distance of each is kept.
+class X25Syndromes {
+public:
+    X25Syndromes() : inv_(65536, 0)
+    {
+        unsigned s = 0x8000u;
+        for (int d = 0; d < 32767; d++) {
+            if (!inv_[s])
+                inv_[s] = (uint16_t)(d + 1);
+            s = (s >> 1) ^ ((s & 1u) ? 0x8408u : 0u);
+        }
+    }
+    const uint16_t* inverse() const { return inv_.data(); } // [65536] distance + 1, 0 = no single error gives this
+
+private:
+    std::vector<uint16_t> inv_;
+};
+
+const X25Syndromes& syndromes()
+{
+    static const X25Syndromes s;
+    return s;
+}
+
 } // namespace
 
 // Receiver state: the run of ones seen so far (the de-stuffer), the octet being filled and the
@@ -60,6 +88,8 @@ struct aisx_hdlc {
     unsigned shift = 0;   // octet under construction, filled from the top and shifted down
     int nshift = 0;       // bits in it
     std::vector<uint8_t> frame;
+    int nrules = 0;       // single-bit repair (aisx_hdlc_set_repair): off without rules
+    aisx_hdlc_rule rules[AISX_HDLC_MAX_RULES] = {};
 
     void drop_frame()
     {
@@ -85,6 +115,25 @@ struct aisx_hdlc {
     }
     // six ones in a row: end of frame (or an abort / idle flags when nothing was collected).
     // Whole octets only; the flag's own leading bits sit in the partial octet and go with it.
+    // the FCS of the frame does not match: one wrong bit at a place the syndrome names, in a frame whose length has a
+    // rule and whose message type after the flip the rule allows, is put right and the frame delivered with the
+    // bit's index (bit 0 = the first bit received); everything else is dropped
+    template <class Sink>
+    void repair(unsigned syndrome, Sink&& deliver)
+    {
+        const int got = (int)frame.size();
+        const aisx_hdlc_rule* rule = nullptr;
+        for (int k = 0; k < nrules && !rule; k++)
+            if (rules[k].payload_octets == got - 2)
+                rule = &rules[k];
+        const int d1 = syndromes().inverse()[syndrome];
+        if (!rule || !d1 || d1 - 1 >= 8 * got)
+            return;
+        const int i = 8 * got - d1;
+        frame[(size_t)(i >> 3)] ^= (uint8_t)(1u << (i & 7)); // (in the FCS: the payload goes out as received)
+        if ((rule->type_mask >> (frame[0] >> 2)) & 1u)
+            deliver(frame.data(), got - 2, i);
+    }
     template <class Sink>
     void delimiter(Sink&& deliver)
     {
@@ -92,8 +141,11 @@ struct aisx_hdlc {
         if (got >= min_octets) {
             const int payload = got - 2;
             const unsigned sent = (unsigned)frame[payload] | ((unsigned)frame[payload + 1] << 8);
-            if (fcs()(frame.data(), (size_t)payload) == sent)
-                deliver(frame.data(), payload);
+            const unsigned syndrome = fcs()(frame.data(), (size_t)payload) ^ sent;
+            if (syndrome == 0)
+                deliver(frame.data(), payload, -1);
+            else if (nrules)
+                repair(syndrome, deliver);
         }
         drop_frame();
     }
@@ -118,19 +170,22 @@ extern "C" int aisx_hdlc_destroy(aisx_hdlc* h)
     return AISX_OK;
 }
 
-extern "C" int aisx_hdlc_work(aisx_hdlc* h, const uint8_t* bits, int nbits, uint8_t* pdu_bytes, int pdu_cap,
-                              int* pdu_offsets, int max_pdus, int* npdus)
+// aisx_hdlc_work and aisx_hdlc_work_repair (fix_bits may be null)
+static int hdlc_work(aisx_hdlc* h, const uint8_t* bits, int nbits, uint8_t* pdu_bytes, int pdu_cap, int* pdu_offsets,
+                     int32_t* fix_bits, int max_pdus, int* npdus)
 {
     if (!h || !bits || nbits < 0 || !npdus || (max_pdus > 0 && (!pdu_offsets || !pdu_bytes)))
         return AISX_ERR_INVALID;
     int found = 0, fill = 0, status = AISX_OK;
     if (max_pdus > 0)
         pdu_offsets[0] = 0;
-    auto deliver = [&](const uint8_t* octets, int count) {
+    auto deliver = [&](const uint8_t* octets, int count, int fixed_bit) {
         if (found < max_pdus && fill + count <= pdu_cap) {
             memcpy(pdu_bytes + fill, octets, (size_t)count);
             fill += count;
             pdu_offsets[found + 1] = fill;
+            if (fix_bits)
+                fix_bits[found] = fixed_bit;
         } else {
             status = AISX_ERR_OVERFLOW;
         }
@@ -147,6 +202,46 @@ extern "C" int aisx_hdlc_work(aisx_hdlc* h, const uint8_t* bits, int nbits, uint
     }
     *npdus = found;
     return status;
+}
+
+extern "C" int aisx_hdlc_work(aisx_hdlc* h, const uint8_t* bits, int nbits, uint8_t* pdu_bytes, int pdu_cap, int* pdu_offsets,
+                              int max_pdus, int* npdus)
+{
+    return hdlc_work(h, bits, nbits, pdu_bytes, pdu_cap, pdu_offsets, nullptr, max_pdus, npdus);
+}
+
+extern "C" int aisx_hdlc_work_repair(aisx_hdlc* h, const uint8_t* bits, int nbits, uint8_t* pdu_bytes, int pdu_cap, int* pdu_offsets,
+                                     int32_t* fix_bits, int max_pdus, int* npdus)
+{
+    if (max_pdus > 0 && !fix_bits)
+        return AISX_ERR_INVALID;
+    return hdlc_work(h, bits, nbits, pdu_bytes, pdu_cap, pdu_offsets, fix_bits, max_pdus, npdus);
+}
+
+int aisx::hdlc_rules_check(const aisx_hdlc_rule* rules, int nrules, int length_min, int length_max)
+{
+    if (nrules < 0 || nrules > AISX_HDLC_MAX_RULES || (nrules > 0 && !rules))
+        return AISX_ERR_INVALID;
+    for (int k = 0; k < nrules; k++) {
+        if (rules[k].reserved != 0 || rules[k].payload_octets < length_min - 2 || rules[k].payload_octets > length_max - 2)
+            return AISX_ERR_INVALID;
+        for (int j = 0; j < k; j++)
+            if (rules[j].payload_octets == rules[k].payload_octets)
+                return AISX_ERR_INVALID;
+    }
+    return AISX_OK;
+}
+
+const uint16_t* aisx::hdlc_syndrome_table() { return syndromes().inverse(); }
+
+extern "C" int aisx_hdlc_set_repair(aisx_hdlc* h, const aisx_hdlc_rule* rules, int nrules)
+{
+    if (!h || aisx::hdlc_rules_check(rules, nrules, h->min_octets, h->max_octets) != AISX_OK)
+        return AISX_ERR_INVALID;
+    h->nrules = nrules;
+    for (int k = 0; k < nrules; k++)
+        h->rules[k] = rules[k];
+    return AISX_OK;
 }
 
 namespace {

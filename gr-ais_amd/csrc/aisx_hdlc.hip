@@ -6,18 +6,28 @@
 
 #include "aisx_devctx.h"
 #include "aisx_host.h"
+#include "aisx_repair.h"
 #include "k_hdlc.h"
 
 using namespace aisx;
 
 static_assert(sizeof(HdlcRec) == sizeof(aisx_pdu), "pdu record layout");
-static_assert(HD_LDS_BYTES + 2 * HD_SCAN_T * 8 <= 64 * 1024, "static LDS");
+static_assert(sizeof(HdlcRule) == sizeof(aisx_hdlc_rule) && HD_MAX_RULES == AISX_HDLC_MAX_RULES, "repair rule layout");
+static_assert(HD_LDS_BYTES_REPAIR + 2 * HD_SCAN_T * 8 <= 64 * 1024, "static LDS");
 
 __global__ __launch_bounds__(HD_T) void k_hdlc_deframe(HdlcParams p)
 {
     __shared__ __attribute__((aligned(16))) char smem[HD_LDS_BYTES];
     DevCtx cx{ smem };
     hdlc_deframe_body(cx, p);
+}
+
+// the deframer of a handle with repair rules
+__global__ __launch_bounds__(HD_T) void k_hdlc_deframe_repair(HdlcParams p)
+{
+    __shared__ __attribute__((aligned(16))) char smem[HD_LDS_BYTES_REPAIR];
+    DevCtx cx{ smem };
+    hdlc_deframe_body<DevCtx, true>(cx, p);
 }
 
 __global__ __launch_bounds__(HD_SCAN_T) void k_hdlc_scan(HdlcScanParams p)
@@ -48,6 +58,12 @@ struct aisx_hdlc_batch {
     Event done;                // behind the last call's work (reset waits for it)
     DevBuf<HdlcRec> d_out;
     DevBuf<unsigned char> d_out_bytes;
+    DevBuf<int> d_fix;         // [max_pdus] the records' repair marks: all -1 while the handle has no rules
+    // single-bit repair, made by the first aisx_hdlc_batch_set_repair with rules
+    int nrules = 0;
+    DevBuf<HdlcRule> d_rules;
+    DevBuf<unsigned short> d_syn_inv;
+    DevBuf<int> d_sfix;        // [nchan][rec_cap]
 };
 
 extern "C" int aisx_hdlc_batch_destroy(aisx_hdlc_batch* h)
@@ -93,8 +109,9 @@ extern "C" int aisx_hdlc_batch_create(aisx_hdlc_batch** out, int length_min, int
         (rc = h->d_sbytes.alloc((size_t)nchan * h->byte_cap, false)) != AISX_OK || (rc = h->d_cnt.alloc(2 * (size_t)nchan)) != AISX_OK ||
         (rc = h->d_base.alloc(2 * (size_t)nchan)) != AISX_OK || (rc = h->d_count.alloc(4)) != AISX_OK ||
         (rc = h->d_out.alloc((size_t)max_pdus)) != AISX_OK || (rc = h->d_out_bytes.alloc((size_t)h->out_bytes_cap)) != AISX_OK ||
-        (rc = h->done.create(hipEventDisableTiming)) != AISX_OK)
+        (rc = h->d_fix.alloc((size_t)max_pdus, false)) != AISX_OK || (rc = h->done.create(hipEventDisableTiming)) != AISX_OK)
         return rc;
+    AISX_HIPCHK(hipMemset(h->d_fix, 0xFF, sizeof(int) * (size_t)max_pdus));
     *out = h.release();
     return AISX_OK;
 }
@@ -111,6 +128,39 @@ extern "C" int aisx_hdlc_batch_reset(aisx_hdlc_batch* h)
     AISX_HIPCHK(hipMemsetAsync(h->d_cnt, 0, sizeof(int) * 2 * h->nchan, nullptr));
     AISX_HIPCHK(hipMemsetAsync(h->d_count, 0, sizeof(int) * 4, nullptr));
     AISX_HIPCHK(hipStreamSynchronize(nullptr)); // (done before the next call, whatever stream that is queued on)
+    return AISX_OK;
+}
+
+extern "C" int aisx_hdlc_batch_set_repair(aisx_hdlc_batch* h, const aisx_hdlc_rule* rules, int nrules)
+{
+    if (!h || hdlc_rules_check(rules, nrules, h->lmin, h->lmax) != AISX_OK) {
+        set_err("aisx_hdlc_batch_set_repair: need a handle and at most %d rules with distinct payload lengths in "
+                "[length_min - 2, length_max - 2] and reserved = 0", AISX_HDLC_MAX_RULES);
+        return AISX_ERR_INVALID;
+    }
+    OnDevice on(h->dev);
+    AISX_HIPCHK(on.err);
+    AISX_HIPCHK(hipEventSynchronize(h->done)); // (the last call's kernels read the rules in place)
+    int rc;
+    if (nrules > 0) {
+        if (!h->d_syn_inv) {
+            DevBuf<HdlcRule> r;
+            DevBuf<unsigned short> t;
+            DevBuf<int> f;
+            if ((rc = r.alloc(HD_MAX_RULES)) != AISX_OK || (rc = t.alloc(65536, false)) != AISX_OK ||
+                (rc = f.alloc((size_t)h->nchan * h->rec_cap, false)) != AISX_OK)
+                return rc;
+            AISX_HIPCHK(hipMemcpy(t, hdlc_syndrome_table(), sizeof(unsigned short) * 65536, hipMemcpyHostToDevice));
+            h->d_rules = std::move(r);
+            h->d_syn_inv = std::move(t);
+            h->d_sfix = std::move(f);
+        }
+        AISX_HIPCHK(hipMemcpy(h->d_rules, rules, sizeof(HdlcRule) * nrules, hipMemcpyHostToDevice));
+    } else if (h->nrules > 0) {
+        AISX_HIPCHK(hipMemset(h->d_fix, 0xFF, sizeof(int) * (size_t)h->max_pdus)); // (nothing writes the marks without rules)
+        AISX_HIPCHK(hipStreamSynchronize(nullptr));
+    }
+    h->nrules = nrules;
     return AISX_OK;
 }
 
@@ -142,7 +192,15 @@ extern "C" int aisx_hdlc_batch_process(aisx_hdlc_batch* h, const uint8_t* d_bits
     p.cnt = h->d_cnt;
     p.nbytes = h->d_cnt + h->nchan;
     p.flags = h->d_count + 2;
-    hipLaunchKernelGGL(k_hdlc_deframe, dim3(h->nchan), dim3(HD_T), 0, st, p);
+    if (h->nrules > 0) {
+        p.rules = h->d_rules;
+        p.nrules = h->nrules;
+        p.syn_inv = h->d_syn_inv;
+        p.sfix = h->d_sfix;
+        hipLaunchKernelGGL(k_hdlc_deframe_repair, dim3(h->nchan), dim3(HD_T), 0, st, p);
+    } else {
+        hipLaunchKernelGGL(k_hdlc_deframe, dim3(h->nchan), dim3(HD_T), 0, st, p);
+    }
     AISX_HIPCHK(hipGetLastError());
     HdlcScanParams s;
     s.cnt = p.cnt;
@@ -166,6 +224,10 @@ extern "C" int aisx_hdlc_batch_process(aisx_hdlc_batch* h, const uint8_t* d_bits
     g.max_pdus = h->max_pdus;
     g.out = h->d_out;
     g.out_bytes = h->d_out_bytes;
+    if (h->nrules > 0) {
+        g.sfix = h->d_sfix;
+        g.out_fix = h->d_fix;
+    }
     hipLaunchKernelGGL(k_hdlc_gather, dim3(h->nchan), dim3(HD_T), 0, st, g);
     AISX_HIPCHK(hipGetLastError());
     AISX_HIPCHK(hipEventRecord(h->done, st));
@@ -217,6 +279,36 @@ extern "C" int aisx_hdlc_batch_read(aisx_hdlc_batch* h, aisx_pdu* pdus, int pdu_
     }
     if (k < cnt[0]) {
         set_err("aisx_hdlc_batch_read: %d PDUs found, %d kept", cnt[0], k);
+        return AISX_ERR_OVERFLOW;
+    }
+    return AISX_OK;
+}
+
+extern "C" int aisx_hdlc_batch_repairs_device(const aisx_hdlc_batch* h, const int32_t** d_fix_bits)
+{
+    if (!h || !d_fix_bits)
+        return AISX_ERR_INVALID;
+    *d_fix_bits = h->d_fix;
+    return AISX_OK;
+}
+
+extern "C" int aisx_hdlc_batch_read_repairs(aisx_hdlc_batch* h, int32_t* fix_bits, int cap, int* n, void* stream)
+{
+    if (!h || !n || cap < 0 || (cap > 0 && !fix_bits))
+        return AISX_ERR_INVALID;
+    OnDevice on(h->dev);
+    AISX_HIPCHK(on.err);
+    const hipStream_t st = (hipStream_t)stream;
+    int cnt[2] = { 0, 0 };
+    AISX_HIPCHK(hipMemcpyAsync(cnt, h->d_count, sizeof cnt, hipMemcpyDeviceToHost, st));
+    AISX_HIPCHK(hipStreamSynchronize(st));
+    const int k = cnt[1] < cap ? cnt[1] : cap;
+    if (k > 0)
+        AISX_HIPCHK(hipMemcpyAsync(fix_bits, h->d_fix, sizeof(int32_t) * k, hipMemcpyDeviceToHost, st));
+    AISX_HIPCHK(hipStreamSynchronize(st));
+    *n = cnt[0];
+    if (k < cnt[0]) {
+        set_err("aisx_hdlc_batch_read_repairs: %d PDUs found, the marks of %d kept", cnt[0], k);
         return AISX_ERR_OVERFLOW;
     }
     return AISX_OK;

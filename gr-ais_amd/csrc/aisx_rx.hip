@@ -101,6 +101,9 @@ struct aisx_rx {
     const char* d_mg_strs = nullptr;
     const int* d_mg_count = nullptr;
     aisx_track_batch* tk = nullptr;    // only after aisx_rx_enable_tracks: the vessel table, updated behind the decoder
+    const int32_t* d_fix = nullptr;    // only after aisx_rx_enable_repair: the deframer's marks,
+    size_t fix_off = 0;                // and where they go in a result slot: int32 fix_bits[max_pdus]
+    std::vector<int32_t> popped_fix;   // the marks of the block popped last
     Stream s_copy, s_filt, s_tail;     // (before the buffers and events used on them: destroyed after those)
     PinnedBuf<char> h_in[RX_NPIN];     // pinned [ns][block_items] items
     DevBuf<char> d_raw[RX_NRAW];
@@ -376,6 +379,8 @@ static int rx_issue(aisx_rx* h, long long k, const cf* next)
         AISX_HIPCHK(hipMemcpyAsync(r + h->msg_off, h->d_mg_cols, cols_bytes, hipMemcpyDeviceToHost, st));
         AISX_HIPCHK(hipMemcpyAsync(r + h->msg_off + cols_bytes, h->d_mg_strs, strs_bytes, hipMemcpyDeviceToHost, st));
     }
+    if (h->d_fix)
+        AISX_HIPCHK(hipMemcpyAsync(r + h->fix_off, h->d_fix, sizeof(int32_t) * (size_t)h->max_pdus, hipMemcpyDeviceToHost, st));
     AISX_HIPCHK(hipMemcpyAsync(r, h->d_meta, sizeof(int) * RX_META, hipMemcpyDeviceToHost, st));
     AISX_HIPCHK(hipMemcpyAsync(r + sizeof(int) * RX_META, h->d_nm_recs, sizeof(aisx_pdu) * (size_t)h->max_pdus, hipMemcpyDeviceToHost, st));
     AISX_HIPCHK(hipMemcpyAsync(r + sizeof(int) * RX_META + sizeof(aisx_pdu) * (size_t)h->max_pdus, h->d_nm_text, (size_t)h->text_cap,
@@ -533,6 +538,8 @@ static int rx_pop(aisx_rx* h, const char* who, int wait, long long* block, char*
             memcpy(cols + (size_t)c * col_stride, cc + (size_t)c * h->max_pdus, sizeof(int32_t) * (size_t)k);
         memcpy(strs, r + h->msg_off + sizeof(int32_t) * AISX_MSG_NCOL * (size_t)h->max_pdus, (size_t)AISX_MSG_STR * k);
     }
+    if (h->d_fix) // (the NMEA stage's records are the first k of the deframer's)
+        h->popped_fix.assign((const int32_t*)(r + h->fix_off), (const int32_t*)(r + h->fix_off) + k);
     if (status)
         *status = meta[0] | (meta[1] > meta[2] ? AISX_RX_ST_HDLC_OVERFLOW : 0) | (meta[5] < meta[2] ? AISX_RX_ST_NMEA_OVERFLOW : 0) |
                   ((meta[3] || meta[6] || meta[7]) ? AISX_RX_ST_BAD_COUNT : 0);
@@ -607,6 +614,60 @@ extern "C" int aisx_rx_pop_messages(aisx_rx* h, int wait, long long* block, char
     }
     return rx_pop(h, "aisx_rx_pop_messages", wait, block, text, text_cap, text_len, recs, rec_cap, nrecs, rec_cap > 0 ? cols : nullptr,
                   col_stride, strs, status);
+}
+
+extern "C" int aisx_rx_enable_repair(aisx_rx* h, const aisx_hdlc_rule* rules, int nrules)
+{
+    if (!h) {
+        set_err("aisx_rx_enable_repair: need a handle");
+        return AISX_ERR_INVALID;
+    }
+    if (h->failed != AISX_OK)
+        return rx_failed(h, "aisx_rx_enable_repair");
+    if (h->acquired || h->submitted > 0 || nrules < 1) {
+        set_err("aisx_rx_enable_repair: at least one rule, and only before the first acquire, submit or push");
+        return AISX_ERR_INVALID;
+    }
+    OnDevice on(h->dev);
+    AISX_HIPCHK(on.err);
+    // the result slots grow by the marks: nothing is in flight yet, so they are simply made again
+    const bool first = h->d_fix == nullptr;
+    const size_t fix_off = first ? (h->res_bytes + 15) & ~(size_t)15 : h->fix_off;
+    const size_t bytes = first ? fix_off + sizeof(int32_t) * (size_t)h->max_pdus : h->res_bytes;
+    PinnedBuf<char> slots[RX_NRES];
+    int rc = AISX_OK;
+    for (int i = 0; first && rc == AISX_OK && i < RX_NRES; i++)
+        if ((rc = slots[i].alloc(bytes)) != AISX_OK)
+            set_err("aisx_rx_enable_repair: %zu bytes of pinned memory for result slot %d could not be had", bytes, i);
+    const int32_t* d_fix = nullptr;
+    if (rc != AISX_OK || (rc = aisx_hdlc_batch_set_repair(h->hd, rules, nrules)) != AISX_OK ||
+        (rc = aisx_hdlc_batch_repairs_device(h->hd, &d_fix)) != AISX_OK)
+        return rc; // (the handle stays as it was)
+    if (first) {
+        for (int i = 0; i < RX_NRES; i++)
+            h->h_res[i] = std::move(slots[i]);
+        h->fix_off = fix_off;
+        h->res_bytes = bytes;
+    }
+    h->d_fix = d_fix;
+    return AISX_OK;
+}
+
+extern "C" int aisx_rx_popped_repairs(aisx_rx* h, int32_t* fix_bits, int cap, int* n)
+{
+    if (!h || !h->d_fix || !n || cap < 0 || (cap > 0 && !fix_bits)) {
+        set_err("aisx_rx_popped_repairs: need a handle on which aisx_rx_enable_repair was called, a count and a buffer for its capacity");
+        return AISX_ERR_INVALID;
+    }
+    const int have = (int)h->popped_fix.size(), k = have < cap ? have : cap;
+    *n = have;
+    if (k > 0)
+        memcpy(fix_bits, h->popped_fix.data(), sizeof(int32_t) * (size_t)k);
+    if (k < have) {
+        set_err("aisx_rx_popped_repairs: the block has %d records, the buffer holds %d", have, cap);
+        return AISX_ERR_OVERFLOW;
+    }
+    return AISX_OK;
 }
 
 extern "C" int aisx_rx_enable_tracks(aisx_rx* h, int capacity)

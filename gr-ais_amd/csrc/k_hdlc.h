@@ -17,6 +17,11 @@
 //            with a table in LDS, and the good ones written in bit order to the channel's staging area;
 //   carry    the last 64 bits, the stream position and the open frame's bits since its last start (at most
 //            8 (length_max + 1)) go to the next pass / call.
+// Single-bit repair (hdlc_deframe_body<Ctx, true>, launched only for a handle with rules): a frame whose FCS fails and
+// whose length has a rule looks its syndrome up in a 65536-entry table in global memory (one 2-byte load); a single
+// error inside the frame whose message type the rule allows makes the frame a good one, its bit flipped in the byte on
+// the way to staging (never in the LDS array: frames sharing a delimiter read it too) and its index kept beside the
+// record.
 // hdlc_scan_body then places every channel's records behind those of the channels before it (one workgroup,
 // a scan of the counts) and hdlc_gather_body copies them there: records ordered by channel and end bit, no
 // atomic decides where one goes.
@@ -34,6 +39,8 @@ constexpr int HD_LDS_SLOTS = 256 * 2;                               // behind th
 constexpr int HD_LDS_ARR = HD_LDS_SLOTS + 66 * 8;                   // 260 16-bit load slots (+ padding)
 constexpr int HD_LDS_BYTES = HD_LDS_ARR + HD_ARR_WORDS * 8;
 constexpr int HD_SCAN_T = 256;
+constexpr int HD_MAX_RULES = 16;                                    // AISX_HDLC_MAX_RULES
+constexpr int HD_LDS_BYTES_REPAIR = HD_LDS_BYTES + HD_MAX_RULES * 16; // the rules behind the array
 
 struct HdlcState {
     unsigned long long hist; // the last 64 bits of the stream, the newest in bit 63
@@ -49,6 +56,12 @@ struct HdlcRec {
     int chan, len;
 };
 
+// aisx_hdlc_rule's layout (static_assert in aisx_hdlc.hip)
+struct HdlcRule {
+    int payload_octets, reserved;
+    unsigned long long type_mask;
+};
+
 struct HdlcParams {
     const unsigned char* bits; long stride; // [nchan][stride] one bit per byte
     const int* nbits;                       // [nchan] bits of this call, read on the device
@@ -60,6 +73,10 @@ struct HdlcParams {
     unsigned char* sbytes; int byte_cap;    // [nchan][byte_cap]
     int* cnt; int* nbytes;                  // [nchan] records / payload bytes of this call
     int* flags;                             // [0] set when a channel's count was out of range
+    // single-bit repair (read by hdlc_deframe_body<Ctx, true> alone)
+    const HdlcRule* rules = nullptr; int nrules = 0;
+    const unsigned short* syn_inv = nullptr; // [65536] syndrome -> distance from the frame's last bit + 1, 0 = none
+    int* sfix = nullptr;                     // [nchan][rec_cap] staging: the flipped bit's index in the frame, -1 = none
 };
 
 struct HdlcScanParams {
@@ -76,6 +93,7 @@ struct HdlcGatherParams {
     const long long* rec_base; const long long* byte_base;
     int max_pdus;
     HdlcRec* out; unsigned char* out_bytes;
+    const int* sfix = nullptr; int* out_fix = nullptr; // the records' repair marks (both or neither)
 };
 
 struct alignas(16) HdB16 {
@@ -114,8 +132,8 @@ AISX_DI int hd_wave_sum(Ctx& cx, int v)
 }
 
 // the frame of `oct` octets at bit `fs` of the data-bit array: does its FCS (last two octets, low byte first)
-// match CRC-16/X.25 of the octets before it?
-AISX_HD bool hd_fcs_ok(const unsigned short* crc, const unsigned long long* arr, int fs, int oct)
+// match CRC-16/X.25 of the octets before it?  Returns the syndrome, (computed FCS) xor (sent FCS): 0 = it matches.
+AISX_HD unsigned hd_fcs_syndrome(const unsigned short* crc, const unsigned long long* arr, int fs, int oct)
 {
     const int payload = oct - 2;
     unsigned reg = 0xFFFFu;
@@ -126,10 +144,33 @@ AISX_HD bool hd_fcs_ok(const unsigned short* crc, const unsigned long long* arr,
             reg = (reg >> 8) ^ crc[(reg ^ (unsigned)(v >> (8 * j))) & 0xFFu];
     }
     const unsigned sent = (unsigned)(hd_read64(arr, fs + 8 * payload) & 0xFFFFu);
-    return (~reg & 0xFFFFu) == sent;
+    return (~reg & 0xFFFFu) ^ sent;
+}
+AISX_HD bool hd_fcs_ok(const unsigned short* crc, const unsigned long long* arr, int fs, int oct)
+{
+    return hd_fcs_syndrome(crc, arr, fs, oct) == 0;
 }
 
-template <class Ctx>
+// the frame of `oct` octets at bit `fs` failed its FCS with `syn`: the index of the one bit to flip (0 = the frame's
+// first bit), or -1 when the frame's length has no rule, no single error inside the frame gives the syndrome, or the
+// message type after the flip is not one the rule allows
+AISX_HD int hd_repair_bit(const HdlcRule* rules, int nrules, const unsigned short* syn_inv, const unsigned long long* arr, int fs,
+                          int oct, unsigned syn)
+{
+    int k = 0;
+    while (k < nrules && rules[k].payload_octets != oct - 2)
+        k++;
+    if (k == nrules)
+        return -1;
+    const int d1 = syn_inv[syn];
+    if (d1 == 0 || d1 - 1 >= 8 * oct)
+        return -1;
+    const int i = 8 * oct - d1;
+    const unsigned first = ((unsigned)hd_read64(arr, fs) & 0xFFu) ^ (i < 8 ? 1u << i : 0u);
+    return ((rules[k].type_mask >> (first >> 2)) & 1ULL) ? i : -1;
+}
+
+template <class Ctx, bool REPAIR = false>
 AISX_DI void hdlc_deframe_body(Ctx& cx, const HdlcParams& p)
 {
     const int l = cx.tid();
@@ -139,6 +180,7 @@ AISX_DI void hdlc_deframe_body(Ctx& cx, const HdlcParams& p)
     unsigned short* slots16 = (unsigned short*)(lds + HD_LDS_SLOTS);
     const unsigned long long* slots = (const unsigned long long*)(lds + HD_LDS_SLOTS);
     unsigned long long* arr = (unsigned long long*)(lds + HD_LDS_ARR);
+    HdlcRule* rules = (HdlcRule*)(lds + HD_LDS_BYTES); // (REPAIR: HD_LDS_BYTES_REPAIR bytes of LDS)
     const int n = p.nbits[c];
     if (n < 0 || n > p.max_bits) { // not advanced; reported by the next read
         if (l == 0) {
@@ -154,6 +196,10 @@ AISX_DI void hdlc_deframe_body(Ctx& cx, const HdlcParams& p)
             r = (r >> 1) ^ ((r & 1u) ? 0x8408u : 0u);
         crc[l + 64 * k] = (unsigned short)r;
     }
+    if constexpr (REPAIR)
+        if (l < p.nrules && l < HD_MAX_RULES)
+            rules[l] = p.rules[l];
+    const int nrules = p.nrules < HD_MAX_RULES ? p.nrules : HD_MAX_RULES;
     const HdlcState s0 = p.st[c];
     unsigned long long hist = s0.hist;
     int c0 = s0.open;
@@ -234,7 +280,9 @@ AISX_DI void hdlc_deframe_body(Ctx& cx, const HdlcParams& p)
         hist = cx.shfl_u64(hn, wl);
         cx.sync();
         // frames closed in this word: length and CRC
-        unsigned long long good = 0;
+        // (REPAIR: fixes holds, 16 bits per good frame of this word in order, the flipped bit's index + 1 or 0 -- a
+        // good frame is at least 16 data bits and its delimiter, so a word closes four at most)
+        unsigned long long good = 0, fixes = 0;
         int ng = 0, gb = 0;
         {
             int st = st0;
@@ -243,10 +291,19 @@ AISX_DI void hdlc_deframe_body(Ctx& cx, const HdlcParams& p)
                 const int a = base + hd_popc(data & hd_below(i));
                 const int r = (a - st) % P;
                 const int oct = r >> 3;
-                if (oct >= p.lmin && hd_fcs_ok(crc, arr, a - r, oct)) {
-                    good |= 1ULL << i;
-                    ng++;
-                    gb += oct - 2;
+                if (oct >= p.lmin) {
+                    const unsigned syn = hd_fcs_syndrome(crc, arr, a - r, oct);
+                    int fix = -1;
+                    if constexpr (REPAIR)
+                        if (syn != 0)
+                            fix = hd_repair_bit(rules, nrules, p.syn_inv, arr, a - r, oct, syn);
+                    if (syn == 0 || fix >= 0) {
+                        if constexpr (REPAIR)
+                            fixes |= (unsigned long long)(fix + 1) << (16 * (ng & 3));
+                        good |= 1ULL << i;
+                        ng++;
+                        gb += oct - 2;
+                    }
                 }
                 st = a;
             }
@@ -268,9 +325,19 @@ AISX_DI void hdlc_deframe_body(Ctx& cx, const HdlcParams& p)
                     o.chan = c;
                     o.len = len;
                     rec[ri] = o;
-                    for (int k = 0; k < len; k++)
-                        outb[bo + k] = (unsigned char)hd_read64(arr, a - r + 8 * k);
+                    const int fix = REPAIR ? (int)(fixes & 0xFFFFu) - 1 : -1;
+                    for (int k = 0; k < len; k++) {
+                        unsigned v = (unsigned)hd_read64(arr, a - r + 8 * k);
+                        if constexpr (REPAIR)
+                            if ((fix >> 3) == k) // (never for -1, nor for a wrong bit in the FCS, which is not delivered)
+                                v ^= 1u << (fix & 7);
+                        outb[bo + k] = (unsigned char)v;
+                    }
+                    if constexpr (REPAIR)
+                        p.sfix[(long)c * p.rec_cap + ri] = fix;
                 }
+                if constexpr (REPAIR)
+                    fixes >>= 16;
                 ri++;
                 bo += len;
             }
@@ -360,6 +427,8 @@ AISX_DI void hdlc_gather_body(Ctx& cx, const HdlcGatherParams& p)
         HdlcRec o = in[j];
         o.offset += bb;
         p.out[rb + j] = o;
+        if (p.out_fix)
+            p.out_fix[rb + j] = p.sfix[(long)c * p.rec_cap + j];
     }
     const int kb = nk == nr ? p.nbytes[c] : (int)in[nk].offset;
     const unsigned char* sb = p.sbytes + (long)c * p.byte_cap;

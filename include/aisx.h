@@ -551,6 +551,31 @@ int aisx_hdlc_destroy(aisx_hdlc* h);
  * *npdus = frames found (AISX_ERR_OVERFLOW if they did not all fit). */
 int aisx_hdlc_work(aisx_hdlc* h, const uint8_t* bits, int nbits, uint8_t* pdu_bytes, int pdu_cap, int* pdu_offsets,
                    int max_pdus, int* npdus);
+/* Single-bit repair by CRC syndrome: opt-in, off after create.  A rule names a payload length (octets, FCS excluded)
+ * and the message types allowed at that length: bit t of type_mask allows type t = pdu[0] >> 2 (aisx_msg_decode's
+ * convention); all ones allows any content. */
+typedef struct aisx_hdlc_rule {
+    int32_t payload_octets;
+    int32_t reserved; /* 0 */
+    uint64_t type_mask;
+} aisx_hdlc_rule;
+#define AISX_HDLC_MAX_RULES 16
+/* At most AISX_HDLC_MAX_RULES rules with distinct payload lengths in [length_min - 2, length_max - 2]; nrules == 0
+ * turns the repair off.  AISX_ERR_INVALID for anything else, and the handle keeps the rules it had.  With rules, a
+ * frame of at least length_min octets whose FCS does NOT match and whose payload length has a rule is looked up by its
+ * syndrome, (CRC of the payload) xor (sent FCS): when that is the syndrome of ONE wrong bit inside the frame, the bit
+ * is flipped, and when the message type after the flip is in the rule's mask the payload is delivered.  A wrong bit in
+ * the FCS delivers the payload as received.  Every other frame is dropped as before; which bits form a frame does not
+ * change.  Two or more wrong bits are not repaired, and about n / 65535 of such n-bit frames look like a single error
+ * and come out wrong with a matching CRC (before the type check): the marks of aisx_hdlc_work_repair tell a consumer
+ * which PDUs to trust less.  The rules apply to every frame that closes after the call, one under way included. */
+int aisx_hdlc_set_repair(aisx_hdlc* h, const aisx_hdlc_rule* rules, int nrules);
+/* aisx_hdlc_work with one more output: fix_bits [max_pdus], -1 for a frame delivered as received, else the index of
+ * the flipped bit in the frame (payload + FCS; bit 0 = the first bit received = bit 0 of octet 0; an index of
+ * 8 * payload length or more lies in the FCS).  aisx_hdlc_work on a handle with rules returns the same PDUs without
+ * the marks. */
+int aisx_hdlc_work_repair(aisx_hdlc* h, const uint8_t* bits, int nbits, uint8_t* pdu_bytes, int pdu_cap, int* pdu_offsets,
+                          int32_t* fix_bits, int max_pdus, int* npdus);
 /* ais.pdu_to_nmea(designator)::msg_to_sentence (lib/pdu_to_nmea_impl.cc:63-131):
  * writes the NUL-terminated !AIVDM sentence(s) (fragments separated by '\n');
  * returns the string length. */
@@ -589,6 +614,19 @@ int aisx_hdlc_batch_results_device(const aisx_hdlc_batch* h, const aisx_pdu** d_
  * previous read met a bad count (the flag is then cleared). */
 int aisx_hdlc_batch_read(aisx_hdlc_batch* h, aisx_pdu* pdus, int pdu_cap, uint8_t* bytes, long bytes_cap, int* npdus,
                          void* stream);
+/* aisx_hdlc_set_repair for every channel of the handle (the same rules, the same results as one host handle per
+ * channel with them, marks included).  Waits for the handle's queued work; applies from the next process call on, to
+ * every frame that closes in it, one opened before included.  Without rules the deframer launches the kernel it
+ * launches on a handle that never had any. */
+int aisx_hdlc_batch_set_repair(aisx_hdlc_batch* h, const aisx_hdlc_rule* rules, int nrules);
+/* the last call's marks in device memory: d_fix_bits [max_pdus], entry k for record k of
+ * aisx_hdlc_batch_results_device (-1: delivered as received, else the flipped bit's index as aisx_hdlc_work_repair
+ * gives it).  On a handle without rules every entry is -1. */
+int aisx_hdlc_batch_repairs_device(const aisx_hdlc_batch* h, const int32_t** d_fix_bits);
+/* copies the last call's marks to the host (synchronises `stream`): *n = PDUs found, the marks written are those of
+ * the first min(*n, max_pdus, cap) records.  AISX_ERR_OVERFLOW when not all were written.  The bad-count flag is
+ * left for aisx_hdlc_batch_read. */
+int aisx_hdlc_batch_read_repairs(aisx_hdlc_batch* h, int32_t* fix_bits, int cap, int* n, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* batched NMEA armouring on the device: for every record of a device PDU    */
@@ -835,6 +873,14 @@ int aisx_rx_enable_messages(aisx_rx* h);
  * AISX_ERR_INVALID on a handle without messages enabled. */
 int aisx_rx_pop_messages(aisx_rx* h, int wait, long long* block, char* text, long text_cap, long* text_len, aisx_pdu* recs,
                          int rec_cap, int* nrecs, int32_t* cols, long col_stride, char* strs, int* status);
+/* Opt-in: aisx_hdlc_batch_set_repair on the handle's deframer, and every result slot also carries the block's marks.
+ * Only before the first acquire, submit or push (AISX_ERR_INVALID afterwards, and for bad rules or none); a handle on
+ * which this was never called allocates, queues and copies nothing more. */
+int aisx_rx_enable_repair(aisx_rx* h, const aisx_hdlc_rule* rules, int nrules);
+/* the marks of the block popped last (by aisx_rx_pop or aisx_rx_pop_messages), one per record of that block: *n of
+ * them, the first min(*n, cap) written (AISX_ERR_OVERFLOW when cap is less).  Valid until the next pop; *n = 0 before
+ * the first.  AISX_ERR_INVALID on a handle without repair enabled. */
+int aisx_rx_popped_repairs(aisx_rx* h, int32_t* fix_bits, int cap, int* n);
 /* Opt-in, and implies aisx_rx_enable_messages: the handle also owns a vessel table of `capacity` vessels
  * (aisx_track_batch_*, max_rows = max_pdus_per_block), and from the first block on the tail stream queues its update
  * behind the field decoder, with stamp = the block's number (its low 32 bits) and the deframer's records for CHAN.

@@ -7,8 +7,9 @@ per step (about 16 400 bits per channel per step), on one MI355X:
   host               aisx_hdlc_work over the same bits, called directly: one thread, a pool of 16
 
 --hw-queues N sets GPU_MAX_HW_QUEUES for this process (read by the HIP runtime at its first call); the pipelined chain
-wants 8 or more.  Writes one JSON file (--out).
-Usage: python tools/hdlc_bench.py [--nchan 4096] [--calls 50] [--steps 20] [--hw-queues 8] --out F"""
+wants 8 or more.  --repair turns the deframer's single-bit repair on with ais_amd.AIS_REPAIR_RULES (the host
+comparison then runs the host form with the same rules).  Writes one JSON file (--out).
+Usage: python tools/hdlc_bench.py [--nchan 4096] [--calls 50] [--steps 20] [--hw-queues 8] [--repair] --out F"""
 import argparse
 import concurrent.futures as cf
 import json
@@ -55,6 +56,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--hw-queues", type=int, default=8)
+    ap.add_argument("--repair", action="store_true")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     nchan, T, sps = a.nchan, a.T, 4
@@ -64,10 +66,11 @@ def main():
     xs = [bench.make_input(nchan, T, "S", sps, dev, r, True) for r in range(2)]
     dem = ais_amd.ais_demod(opts, nchan=nchan, max_items=T, stages="stock", preamble_symbols=tmpl)
     cap = dem.clockrec.out_capacity
-    hd = ais_amd.hdlc_deframer_batch(11, 64, nchan, cap, 1 << 17)
+    hd = ais_amd.hdlc_deframer_batch(11, 64, nchan, cap, 1 << 17, repair=ais_amd.AIS_REPAIR_RULES if a.repair else None)
+    rules = ais_amd.framing.repair_rules(ais_amd.AIS_REPAIR_RULES if a.repair else None)
     s = torch.cuda.Stream()
     res = {"shape": dict(nchan=nchan, T=T, length_min=11, length_max=64, max_bits=cap), "device": torch.cuda.get_device_name(0),
-           "gpu_max_hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"])}
+           "gpu_max_hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]), "repair": bool(a.repair)}
 
     def steps(n, deframe):
         n += n % 2  # (x_next alternates between the two inputs: every run ends where the next one starts)
@@ -105,9 +108,9 @@ def main():
         e1.record(s)
     s.synchronize()
     ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
-    recs, _ = hd.pdus(stream=s)
+    recs, _, fix = hd.pdus(stream=s, with_repairs=True)
     res["deframer_alone_ms"] = dict(median=ms[len(ms) // 2], min=ms[0], max=ms[-1], calls=a.calls,
-                                    pdus_per_call=int(len(recs)))
+                                    pdus_per_call=int(len(recs)), repaired_per_call=int((fix >= 0).sum()))
     res["deframer_alone_gbit_s"] = res["bits_per_step"]["total"] / (res["deframer_alone_ms"]["median"] * 1e-3) / 1e9
 
     # the pipelined step without / with the deframer behind it (alternating runs, each after a warm-up)
@@ -138,6 +141,7 @@ def main():
         n, h, found = C.c_int(0), C.c_void_p(), 0
         for c in chans:
             check(L.aisx_hdlc_create(C.byref(h), 11, 64), "aisx_hdlc_create")
+            check(L.aisx_hdlc_set_repair(h, rules.ctypes.data_as(C.c_void_p) if rules.size else None, rules.size), "aisx_hdlc_set_repair")
             rc = L.aisx_hdlc_work(h, rows[c].ctypes.data_as(C.c_void_p), int(nb[c]), buf.ctypes.data_as(C.c_void_p),
                                   buf.size, offs.ctypes.data_as(C.c_void_p), maxp, C.byref(n))
             L.aisx_hdlc_destroy(h)
