@@ -23,6 +23,7 @@ del _t
 
 from .framing import AIS_REPAIR_RULES, MSG_COLUMNS, MSG_DTYPE, MSG_NA, hdlc_deframer_bp, msg_decode, pdu_to_nmea  # noqa: F401
 from .modulate import gmsk_mod, modulate_vector_bc  # noqa: F401
+from .transmit import BURST_DTYPE, gmsk_burst, gmsk_scene, hdlc_framer  # noqa: F401
 
 
 def __getattr__(name):
@@ -39,4 +40,8 @@ def __getattr__(name):
         from . import batch_framing
 
         return getattr(batch_framing, name)
+    if name == "ais_tx_batch":
+        from . import transmit
+
+        return transmit.ais_tx_batch
     raise AttributeError(name)

@@ -246,6 +246,14 @@ def lib(device=True):
     sig("aisx_rx_enable_tracks", i32, [vp, i32])
     sig("aisx_rx_read_tracks", i32, [vp, i32, i32, vp, lng, vp, pi32, pll])
     sig("aisx_rx_read_changed_tracks", i32, [vp, vp, vp, lng, vp, i32, pi32, pll])
+    i64 = C.c_int64
+    sig("aisx_hdlc_frame", i32, [vp, i32, i32, i32, i32, vp, i32, pi32])
+    sig("aisx_tx_render_host", i32, [f64, f64, i32, i32, i32, i32, vp, i32, vp, i64, i64, i64, vp, i64, i32])
+    sig("aisx_tx_batch_create", i32, [pvp, f64, f64, i32, i32, i32, i32, i32, i32])
+    sig("aisx_tx_batch_destroy", i32, [vp])
+    sig("aisx_tx_batch_set_bursts", i32, [vp, vp, i32, vp, i64, vp])
+    sig("aisx_tx_batch_render", i32, [vp, i64, i64, vp, i64, i32, vp])
+    sig("aisx_tx_batch_read_levels", i32, [vp, i32, vp, i32, pi32, vp])
     _lib = L
     return L
 

@@ -899,6 +899,76 @@ int aisx_rx_read_changed_tracks(aisx_rx* h, int* idx, int32_t* cols, long col_st
 int aisx_rx_set_center_freq(aisx_rx* h, int stream, int chan, double center_freq);
 /* A failed block (a HIP error, the chain refusing) makes every later call but destroy return that block's error. */
 
+/* ------------------------------------------------------------------------ */
+/* the transmit side: HDLC framing (the inverse of aisx_hdlc_work) and a      */
+/* GMSK burst modulator defined per output sample, on the host (the           */
+/* specification, in double) and batched on the device                        */
+/* ------------------------------------------------------------------------ */
+/* Payload octets -> the burst's NRZ symbol levels, one 0 / 1 per byte of `levels`:
+ *   ramp_syms alternating symbols 1, 0, 1, ... ;
+ *   training_bits symbols 1, 1, 0, 0, 1, 1, ... (the NRZI image of 0101...; 28 is what the receiver's template holds,
+ *   24 the ITU-R M.1371 value);
+ *   flag 0x7E + [payload bits, LSB first per octet, + CRC-16/X.25 FCS, low octet first; a 0 stuffed behind every five
+ *   1s] + flag 0x7E, NRZI-encoded (a 0 toggles the level, a 1 keeps it) starting from the training sequence's last level;
+ *   tail_syms repeats of the last level.
+ * 1 <= len <= 1023; 0 <= ramp_syms, tail_syms <= 64; 1 <= training_bits <= 256.  *nsyms = symbols of the burst; when
+ * cap is smaller, AISX_ERR_OVERFLOW and nothing written (levels may then be NULL). */
+int aisx_hdlc_frame(const uint8_t* payload, int len, int training_bits, int ramp_syms, int tail_syms, uint8_t* levels,
+                    int cap, int* nsyms);
+
+typedef struct aisx_burst {
+    int64_t start;   /* row sample index at which symbol 0 begins */
+    int64_t offset;  /* first payload octet in the byte buffer */
+    int32_t chan, len;
+    float frac;      /* extra delay in samples, [0, 1) */
+    float amp;
+    float cfo;       /* cycles per sample, |cfo| <= 0.5 */
+    float phase;     /* radians */
+} aisx_burst;
+
+/* The waveform.  With a_k = +-1 the burst's levels (0 outside it), L = 4, d = t - start, u = (d - frac) / sps and
+ * m = floor(u), sample t of a burst is
+ *   x(t) = amp env(u) exp(j [ (pi/2) ( S(m - L) + sum_{k = m-L+1 .. m} a_k q(u - k) ) + 2 pi cfo d + phase ])
+ * where S(i) = a_0 + ... + a_i (an integer: (pi/2) S is an exact quadrant), env(u) = min(1, u / r, (nsyms - u) / r) with
+ * r = ramp_syms / 2 symbols (1 when ramp_syms = 0), and q the phase pulse of BT = bt GMSK, truncated to L symbols:
+ *   beta = pi bt sqrt(2 / ln 2),   F(x) = x erf(beta x) + exp(-beta^2 x^2) / (beta sqrt(pi)),
+ *   G(x) = 1/2 + (F(x + 1/2) - F(x - 1/2)) / 2      (the integral of a Gaussian convolved with a one-symbol rectangle),
+ *   q(v) = (G(v - L/2) - G(-L/2)) / (G(L/2) - G(-L/2)) for 0 <= v <= L,   0 below,   1 above
+ * so that q(0) = 0 and q(L) = 1 exactly and x is continuous in u.  The burst occupies the samples with
+ * 0 <= u < nsyms; bursts that overlap in a channel add.  No sample depends on another.
+ *
+ * aisx_tx_render_host evaluates this in double for rows [nchan][n] of the sample window [t0, t0 + n), sums a sample's
+ * bursts in double and rounds once to float; accumulate != 0 adds that float to what out holds.  sps >= 2 (any real
+ * number), 0.1 <= bt <= 1, framing arguments as aisx_hdlc_frame's, descriptors as aisx_tx_batch_set_bursts checks
+ * them (length_max = 1023). */
+int aisx_tx_render_host(double sps, double bt, int training_bits, int ramp_syms, int tail_syms, int nchan,
+                        const aisx_burst* bursts, int nbursts, const uint8_t* bytes, int64_t nbytes, int64_t t0, int64_t n,
+                        aisx_cf32* out, int64_t out_stride, int accumulate);
+
+/* The same on the device, for a schedule of at most max_bursts bursts of at most length_max payload octets on nchan
+ * channels.  The handle belongs to the device that was current here. */
+typedef struct aisx_tx_batch aisx_tx_batch;
+int aisx_tx_batch_create(aisx_tx_batch** h, double sps, double bt, int training_bits, int ramp_syms, int tail_syms,
+                         int nchan, int max_bursts, int length_max);
+int aisx_tx_batch_destroy(aisx_tx_batch* h);
+/* Replaces the schedule (bursts and bytes are host memory, free again at return; n = 0 empties it).  Checked on the
+ * host: chan in [0, nchan), 1 <= len <= length_max, offset >= 0 and offset + len <= nbytes, frac in [0, 1), amp and phase
+ * finite, |cfo| <= 0.5, |start| < 2^62, n <= max_bursts -- AISX_ERR_INVALID otherwise, and the schedule stays what it
+ * was.  Waits for the handle's last render, uploads the bursts sorted by (chan, start, frac) and queues k_tx_frame on
+ * `stream`: one wave per burst frames its payload into packed levels and per-word level counts. */
+int aisx_tx_batch_set_bursts(aisx_tx_batch* h, const aisx_burst* bursts, int n, const uint8_t* bytes, int64_t nbytes,
+                             void* stream);
+/* Queues k_tx_render on `stream`: rows [nchan][n] at d_out (row stride out_stride >= n items, 8-byte aligned) for the
+ * sample window [t0, t0 + n), 1 <= n <= 2^30.  accumulate == 0: every sample is written, zeros where no burst is;
+ * accumulate != 0: out = out + (the sum of the sample's bursts), nothing written where no burst is near.  Stateless
+ * in t0: the rows of one call and of any split of its window into calls are bit-identical. */
+int aisx_tx_batch_render(aisx_tx_batch* h, int64_t t0, int64_t n, aisx_cf32* d_out, int64_t out_stride, int accumulate,
+                         void* stream);
+/* test and inspection hook: the levels k_tx_frame made for burst `index` (in the order they were given to
+ * aisx_tx_batch_set_bursts), unpacked to one 0 / 1 per byte; synchronises `stream`.  *nsyms = the device's symbol
+ * count; AISX_ERR_OVERFLOW when cap is smaller (nothing written). */
+int aisx_tx_batch_read_levels(aisx_tx_batch* h, int index, uint8_t* levels, int cap, int* nsyms, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
