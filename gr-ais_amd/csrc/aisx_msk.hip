@@ -1,18 +1,16 @@
 // aisx_msk.hip -- C ABI (include/aisx.h) for msk_timing_recovery_cc and the NRZI bit tail,
-// plus the __global__ wrappers that run the kernel bodies of k_msk.h on gfx950.
+// plus the __global__ wrappers that run the kernel bodies of k_msk.h on gfx950.  The time-parallel recovery
+// (off unless asked for) is aisx_mskp.hip: this file compiles without k_mskp.h.
 #include <math.h>
 #include <stdlib.h>
 
 #include <algorithm>
-#include <memory>
 #include <vector>
 
 #include "aisx_devctx.h"
-#include "aisx_host.h"
+#include "aisx_msk_impl.h"
 #include "aisx_plan.h"
 #include "aisx_tables.h"
-#include "k_msk.h"
-#include "k_mskp.h"
 
 using namespace aisx;
 
@@ -64,35 +62,8 @@ __global__ __launch_bounds__(256) void k_msk_tagprep(TagPrepParams p)
     tagprep_body(cx, p);
 }
 
-// ---- the time-parallel recovery (k_mskp.h): prepass, units, join, gather
-__global__ __launch_bounds__(64) void k_mskp_prep(MskpPrepParams p)
-{
-    __shared__ __attribute__((aligned(16))) char smem[MSKP_PREP_LDS_TAGS * 8];
-    DevCtx cx{ smem };
-    mskp_prep_body(cx, p);
-}
-__global__ __launch_bounds__(64) void k_mskp_units(MskpParams p)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    DevCtx cx{ smem };
-    mskp_body<DevCtx, false>(cx, p);
-}
-__global__ __launch_bounds__(64) void k_mskp_join(MskpParams p)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    DevCtx cx{ smem };
-    // one lane per channel, a recurrence: its waves go first on their SIMDs
-    __builtin_amdgcn_s_setprio(3);
-    mskp_body<DevCtx, true>(cx, p);
-}
-__global__ __launch_bounds__(256) void k_mskp_gather(MskpGatherParams p)
-{
-    DevCtx cx{ nullptr };
-    mskp_gather_body(cx, p);
-}
-
 // launch the timing-recovery build for (err/mu ports connected, osps == 2, channels per wave)
-static int msk_launch(const MskParams& p, int nwg, hipStream_t st)
+int aisx::msk_launch(const MskParams& p, int nwg, hipStream_t st)
 {
     typedef void (*kfn)(MskParams);
     static const kfn fns[20] = {
@@ -132,86 +103,6 @@ static int msk_launch(const MskParams& p, int nwg, hipStream_t st)
 // ---------------------------------------------------------------------------
 // msk_timing_recovery_cc
 // ---------------------------------------------------------------------------
-struct aisx_msk {
-    int nchan = 0, max_items = 0, out_cap = 0, osps = 1;
-    // measurement hook (aisx_msk_set_profiling): hipEvents around the recovery kernel of every stream call
-    EventRing prof;
-    int lpw = 64; // channels per wave of the timing-recovery kernel
-    int inline_tags = 1; // (AISX_MSK_INLINE_TAGS=0: every tag reset through the general steps, for A/B runs)
-    float d_sps = 0, gain = 0, gain_omega = 0, limit = 0;
-    static constexpr int carry_cap = MSK_CARRY_MAX, ctag_cap = 64;
-    DevBuf<float> d_mu, d_omega;
-    DevBuf<int> d_div;
-    DevBuf<cf> d_dly1, d_dly2, d_diff1;
-    // bit tail state (previous symbol, previous sliced bit): read from [tcur], written to [tcur ^ 1]
-    DevBuf<cf> d_tprev[2];
-    DevBuf<unsigned char> d_tbit[2];
-    int tcur = 0;
-    // symbols for the bit tail when the caller takes bits only; two, alternating, so that the
-    // bit tail of call k may still read one while call k+1 writes the other (tail stream)
-    DevBuf<cf> d_symscratch[2];
-    int callpar = 0;
-    // optional: the bit tail on a stream of its own (aisx_msk_set_tail_stream)
-    bool tail_on = false;
-    hipStream_t tail_stream = nullptr; // the caller's
-    Event ev_msk, ev_tail[2];
-    unsigned head_start_ticks = 0; // aisx_msk_set_head_start
-    Event ev_prep; // behind the tag prepass of the last aisx_msk_process_stream (aisx_msk_wait_prepass)
-    bool ev_prep_set = false;
-    bool ev_tail_set[2] = { false, false };
-    DevBuf<int> d_produced2; // second internal `produced` array (alternates with d_produced)
-    DevBuf<unsigned long long> d_nread;
-    DevBuf<cf> d_carry[2];
-    DevBuf<int> d_carry_len[2];
-    DevBuf<tag_rec> d_ctag[2];
-    DevBuf<int> d_ctag_n[2];
-    DevBuf<msk_ctag> d_ct; // this call's time_est tags, compacted (k_msk_tagprep): nchan x ct_cap()
-    DevBuf<int> d_ct_n;
-    int ct_cap() const { return (int)(d_ct.cap() / (size_t)nchan); }
-    int cur = 0;
-    DevBuf<int> d_produced, d_consumed, d_status;
-    DevBuf<float> d_mmse, d_atan;
-    // time-parallel path (k_mskp.h)
-    int tp_smax = 0;       // the time-parallel recovery (k_mskp.h): restart points per channel at most; 0 = off, the serial kernel alone
-    int tp_min_gap = 64;   // items between restart points at least
-    int tp_jw = 16;        // channels per wave of the join kernel
-    int tp_join = 1;       // the join: 1 = the serial kernel with fast-forward (k_msk.h, MskParams::ff), 0 = k_mskp_join
-    int tp_max_span = 4096; // no unit from a restart point further than this from the next one (tp_join = 1: the serial kernel is faster there)
-    int max_noutput = 0;   // set_max_noutput_items(): output items one general_work call is offered at most (0: what fits)
-    unsigned long long total_in = 0; // items handed to the block so far = absolute offset of the next row's item 0
-    // Everything the time-parallel path allocates on first use (and nothing else): set up = the struct exists;
-    // without it the handle is as if the path had never run.
-    struct Tp {
-        // the units run on a stream of their own, one call ahead of the join (which needs the previous call's
-        // state): everything the prepass and the units leave for the join exists twice, by the call's parity
-        Stream s_units;
-        Event ev_entry, ev_units[2], ev_join[2];
-        bool ev_join_set[2] = { false, false };
-        DevBuf<msk_ctag> d_ctl; // 2 x nchan x ctl_cap
-        int ctl_cap = 0;
-        DevBuf<int> d_ctl_n, d_nrst;
-        DevBuf<mskp_rst> d_rst;
-        DevBuf<mskp_res> d_res;
-        DevBuf<int> d_ct_nc;
-        DevBuf<cf> d_stage[2];
-        long stage_stride = 0;
-        DevBuf<int> d_ucount; // units per length class
-        DevBuf<int> d_ulist;  // ... and which
-        DevBuf<mskp_piece> d_pieces[2];
-        DevBuf<int> d_npieces[2];
-        long tp_calls = 0;
-    };
-    std::unique_ptr<Tp> tp;
-    // GNU Radio path staging
-    DevBuf<cf> d_st_in, d_st_blk;
-    cf* d_st_sym = nullptr; // (= d_st_blk + 2: the symbols behind their 16-byte header)
-    std::vector<cf> st_host; // where header + symbols land on the host
-    DevBuf<float> d_st_err, d_st_mu;
-    DevBuf<unsigned char> d_st_bits;
-    DevBuf<tag_rec> d_st_tags;
-    DevBuf<int> d_st_tagn;
-};
-
 // What the kernel's LDS rings and the carry buffer are sized for (k_msk.h): one general_work call
 // of a single output must fit the carry (forecast(1) + the pre-item), a pair of iterations must
 // stay well inside a 64-sample chunk, and omega must stay positive under the clip of :182
@@ -307,18 +198,7 @@ extern "C" int aisx_msk_create(aisx_msk** out, float sps, float gain, float limi
         h->lpw = 8;
         if (const char* e = exp_env("AISX_MSK_INLINE_TAGS"))
             h->inline_tags = atoi(e) != 0;
-        if (const char* e = exp_env("AISX_MSK_TIME_PARALLEL")) // (experiments; the API is aisx_msk_set_time_parallel)
-            h->tp_smax = atoi(e) != 0 ? MSKP_SMAX : 0;
-        if (const char* e = exp_env("AISX_MSK_TP_SMAX")) // restart points per channel (0: the serial kernel)
-            h->tp_smax = std::max(0, std::min(atoi(e), (int)MSKP_SMAX));
-        if (const char* e = exp_env("AISX_MSK_TP_GAP"))
-            h->tp_min_gap = std::max(0, atoi(e));
-        if (const char* e = exp_env("AISX_MSK_TP_JOIN"))
-            h->tp_join = atoi(e) != 0;
-        if (const char* e = exp_env("AISX_MSK_TP_MAXSPAN"))
-            h->tp_max_span = std::max(64, atoi(e));
-        if (const char* e = exp_env("AISX_MSK_JW"))
-            h->tp_jw = std::max(1, std::min(64, atoi(e)));
+        msk_tp_create(h.get());
         if (const char* e = exp_env("AISX_MSK_MAX_NOUTPUT")) // (experiments; the API is aisx_msk_set_max_noutput_items)
             h->max_noutput = std::max(0, atoi(e));
         if (const char* e = exp_env("AISX_MSK_LPW")) { // (experiments)
@@ -357,11 +237,7 @@ extern "C" int aisx_msk_create(aisx_msk** out, float sps, float gain, float limi
 
 extern "C" int aisx_msk_destroy(aisx_msk* h)
 {
-    if (!h)
-        return AISX_OK;
-    if (h->tp) // the units' stream comes to rest before anything it uses is released
-        (void)hipStreamSynchronize(h->tp->s_units);
-    delete h;
+    delete h; // (~MskTp lets the units' stream come to rest before anything is released)
     return AISX_OK;
 }
 
@@ -421,17 +297,6 @@ extern "C" int aisx_msk_set_max_noutput_items(aisx_msk* h, int max_noutput_items
     h->max_noutput = max_noutput_items;
     return AISX_OK;
 }
-extern "C" int aisx_msk_set_time_parallel(aisx_msk* h, int restart_points_per_channel, int join_kernel, int max_unit_items)
-{
-    if (!h || restart_points_per_channel < 0)
-        return AISX_ERR_INVALID;
-    h->tp_smax = std::min(restart_points_per_channel, (int)MSKP_SMAX);
-    if (join_kernel >= 0)
-        h->tp_join = join_kernel != 0;
-    if (max_unit_items > 0)
-        h->tp_max_span = std::max(64, max_unit_items);
-    return AISX_OK;
-}
 extern "C" int aisx_msk_get_max_noutput_items(const aisx_msk* h) { return h ? h->max_noutput : AISX_ERR_INVALID; }
 extern "C" int aisx_msk_out_capacity(const aisx_msk* h) { return h ? h->out_cap : AISX_ERR_INVALID; }
 extern "C" int aisx_msk_reset(aisx_msk* h)
@@ -445,35 +310,13 @@ extern "C" int aisx_msk_reset(aisx_msk* h)
     return AISX_OK;
 }
 
-static void msk_fill_common(aisx_msk* h, MskParams& p)
+void aisx::msk_fill_common(aisx_msk* h, MskParams& p)
 {
-    p.nchan = h->nchan;
-    p.d_sps = h->d_sps;
-    p.gain = h->gain;
-    p.gain_omega = h->gain_omega;
-    p.limit = h->limit;
+    msk_fill_state(h, p);
     p.osps = h->osps;
-    p.mu = h->d_mu;
-    p.omega = h->d_omega;
-    p.div = h->d_div;
-    p.dly1 = h->d_dly1;
-    p.dly2 = h->d_dly2;
-    p.diff1 = h->d_diff1;
-    p.nread = h->d_nread;
-    p.carry_in = h->d_carry[h->cur];
-    p.carry_out = h->d_carry[h->cur ^ 1];
-    p.carry_len_in = h->d_carry_len[h->cur];
-    p.carry_len_out = h->d_carry_len[h->cur ^ 1];
-    p.carry_cap = aisx_msk::carry_cap;
-    p.ctag_out = h->d_ctag[h->cur ^ 1];
-    p.ctag_n_out = h->d_ctag_n[h->cur ^ 1];
-    p.ctag_cap = aisx_msk::ctag_cap;
     p.ct = h->d_ct;
     p.ct_n = h->d_ct_n;
     p.ct_cap = h->ct_cap();
-    p.consumed = h->d_consumed;
-    p.status = h->d_status;
-    p.mmse = h->d_mmse;
     p.lds_tab_off = msk_lds_taboff(h->lpw);
     p.lpw = h->lpw;
     p.lds_wave_stride = msk_lds_wave(h->lpw);
@@ -481,7 +324,9 @@ static void msk_fill_common(aisx_msk* h, MskParams& p)
     p.tq_private = 0;
     p.lds_ring_off = msk_lds_ringoff(h->lpw);
     p.inline_tags = h->inline_tags;
-    p.max_noutput = h->max_noutput;
+    p.stream_mode = 1;
+    p.gr_ninput = 0;
+    p.gr_noutput = 0;
     p.ff = 0;
     p.nrst = nullptr;
     p.rst = nullptr;
@@ -505,13 +350,10 @@ static int msk_ct_reserve(aisx_msk* h, int need, hipStream_t st)
     return AISX_OK;
 }
 
-// compacts (carried tags + this call's tags [+ the prepass's list `ctl_new`, time-parallel join]) into h->d_ct for the
-// kernel launch that follows
-static int msk_launch_tagprep(aisx_msk* h, const tag_rec* d_tags, const int* d_tag_counts, int tag_cap, hipStream_t st,
-                              int* d_ct_nc = nullptr, const msk_ctag* ctl_new = nullptr, const int* ctl_new_n = nullptr,
-                              int ctl_new_cap = 0)
+int aisx::msk_launch_tagprep(aisx_msk* h, const tag_rec* d_tags, const int* d_tag_counts, int tag_cap, hipStream_t st, int* d_ct_nc,
+                             const msk_ctag* ctl_new, const int* ctl_new_n, int ctl_new_cap, int ctl_new_pre)
 {
-    const int need = aisx_msk::ctag_cap + (ctl_new ? ctl_new_cap - MSKP_TPRE : (d_tags ? tag_cap : 0));
+    const int need = aisx_msk::ctag_cap + (ctl_new ? ctl_new_cap - ctl_new_pre : (d_tags ? tag_cap : 0));
     const int rc = msk_ct_reserve(h, need, st);
     if (rc != AISX_OK)
         return rc;
@@ -531,7 +373,7 @@ static int msk_launch_tagprep(aisx_msk* h, const tag_rec* d_tags, const int* d_t
     t.ctl_new = ctl_new;
     t.ctl_new_n = ctl_new_n;
     t.ctl_new_cap = ctl_new_cap;
-    t.ctl_new_pre = ctl_new ? MSKP_TPRE : 0;
+    t.ctl_new_pre = ctl_new ? ctl_new_pre : 0;
     t.W = ctl_new ? h->total_in : 0;
     hipLaunchKernelGGL(k_msk_tagprep, dim3((h->nchan + 3) / 4), dim3(256), 0, st, t); // a wave per channel
     AISX_HIPCHK(hipGetLastError());
@@ -561,49 +403,20 @@ static int msk_launch_bittail(aisx_msk* h, const cf* syms, long sym_stride, cons
     return AISX_OK;
 }
 
-// ---- the time-parallel path -------------------------------------------------------------------
-static bool msk_tp_applies(const aisx_msk* h, const float* d_err, const float* d_mu)
+// the serial kernel over the call's items (hipEvents around it for aisx_msk_set_profiling)
+static int msk_launch_serial(aisx_msk* h, const MskCall& c, float* d_err, float* d_mu)
 {
-    // (osps = 2 and the err / mu ports stay with the serial kernel: after a restart the first err
-    // of a unit would need the previous unit's last nlin_out)
-    return h->tp_smax > 0 && h->osps == 1 && !d_err && !d_mu &&
-           mskp_geometry_ok(h->d_sps, h->gain, h->limit, h->max_items + aisx_msk::carry_cap);
-}
-
-static int msk_tp_buffers(aisx_msk* h, int tag_cap, hipStream_t st)
-{
+    MskParams p;
+    msk_fill_common(h, p);
+    msk_fill_call(c, p);
+    p.err = d_err;
+    p.mu_out = d_mu;
+    p.sym_al16 = ((uintptr_t)c.syms % 16 == 0) && (c.out_stride % 2 == 0);
     int rc;
-    const size_t nc = (size_t)h->nchan;
-    const int need = MSKP_TPRE + tag_cap + 1;
-    if (h->tp && need <= h->tp->ctl_cap)
-        return AISX_OK;
-    AISX_HIPCHK(hipStreamSynchronize(st));
-    if (!h->tp) {
-        // (all or nothing: a failed allocation half way leaves a handle on which the path never ran)
-        auto t = std::make_unique<aisx_msk::Tp>();
-        t->stage_stride = mskp_stage_stride(h->max_items + aisx_msk::carry_cap, h->d_sps, h->gain, h->limit);
-        if ((rc = t->d_ctl.alloc(2 * nc * (size_t)need)) != AISX_OK || (rc = t->d_ctl_n.alloc(2 * nc)) != AISX_OK ||
-            (rc = t->d_nrst.alloc(2 * nc)) != AISX_OK || (rc = t->d_rst.alloc(2 * nc * MSKP_SMAX)) != AISX_OK ||
-            (rc = t->d_res.alloc(2 * nc * MSKP_SMAX)) != AISX_OK || (rc = t->d_ucount.alloc(16)) != AISX_OK ||
-            (rc = t->d_ct_nc.alloc(nc)) != AISX_OK || (rc = t->d_ulist.alloc(2 * nc * MSKP_SMAX * MSKP_NCLS)) != AISX_OK ||
-            (rc = t->s_units.create_nonblocking()) != AISX_OK || (rc = t->ev_entry.create(hipEventDisableTiming)) != AISX_OK)
-            return rc;
-        for (int k = 0; k < 2; k++)
-            if ((rc = t->ev_units[k].create(hipEventDisableTiming)) != AISX_OK || (rc = t->ev_join[k].create(hipEventDisableTiming)) != AISX_OK ||
-                (rc = t->d_stage[k].alloc(nc * (size_t)t->stage_stride)) != AISX_OK ||
-                (rc = t->d_pieces[k].alloc(nc * MSKP_SMAX)) != AISX_OK || (rc = t->d_npieces[k].alloc(nc)) != AISX_OK)
-                return rc;
-        t->ctl_cap = need;
-        h->tp = std::move(t);
-    } else {
-        AISX_HIPCHK(hipStreamSynchronize(h->tp->s_units));
-        h->tp->ctl_cap = 0; // (until the new list exists)
-        if ((rc = h->tp->d_ctl.alloc(2 * nc * (size_t)need)) != AISX_OK)
-            return rc;
-        h->tp->ctl_cap = need;
-    }
-    // dev_alloc's zero fill runs on the null stream: it must not trail into the kernels on `st`
-    AISX_HIPCHK(hipDeviceSynchronize());
+    if ((rc = h->prof.begin(c.st)) != AISX_OK ||
+        (rc = msk_launch(p, (h->nchan + msk_wg_channels(h->lpw) - 1) / msk_wg_channels(h->lpw), c.st)) != AISX_OK ||
+        (rc = h->prof.end(c.st)) != AISX_OK)
+        return rc;
     return AISX_OK;
 }
 
@@ -623,95 +436,23 @@ static int msk_process_stream(aisx_msk* h, const aisx_cf32* d_in, long in_stride
         set_err("aisx_msk_process_stream: out_stride %ld too large (the 64 rows of a wave must lie within 4 GiB)", out_stride);
         return AISX_ERR_INVALID;
     }
-    hipStream_t st = (hipStream_t)stream;
+    const hipStream_t st = (hipStream_t)stream;
     const bool tp = msk_tp_applies(h, d_err, d_mu);
     const int par = h->callpar;
     h->callpar ^= 1;
-    int rc, t_smax = 0;
-    bool tp_sorted = false;
-    const size_t nc = (size_t)h->nchan;
-    // this call's copies of what the prepass and the units leave for the join
-    msk_ctag* ctl = nullptr;
-    int *ctl_n = nullptr, *nrst = nullptr, *ucount = nullptr, *ulist = nullptr;
-    mskp_rst* rst = nullptr;
-    mskp_res* res = nullptr;
-    hipStream_t su = st; // where the prepass and the units run
-    aisx_msk::Tp* T = nullptr;
-    if (tp) {
-        if ((rc = msk_tp_buffers(h, d_tags ? tag_cap : 0, st)) != AISX_OK)
-            return rc;
-        T = h->tp.get();
-        ctl = T->d_ctl + (size_t)par * nc * (size_t)T->ctl_cap;
-        ctl_n = T->d_ctl_n + par * nc;
-        nrst = T->d_nrst + par * nc;
-        rst = T->d_rst + par * nc * MSKP_SMAX;
-        res = T->d_res + par * nc * MSKP_SMAX;
-        ucount = T->d_ucount + par * 8;
-        ulist = T->d_ulist + par * nc * MSKP_SMAX * MSKP_NCLS;
-        // The units need the samples and the tags of this call, nothing of the call before: they run
-        // on their own stream, beside the join of the previous call.  They start when the caller says
-        // the inputs are there (ready_event; without one: when `stream` gets here), when the join of
-        // two calls ago has let go of this parity's records and the bit tail of its staging rows.
-        // (experiment switches, read once: units on the call's stream; unsorted unit list)
-        static const bool one_stream = exp_env("AISX_MSK_TP_ONE_STREAM") != nullptr;
-        if (!one_stream)
-            su = T->s_units;
-        if (su != st) {
-            if (ready_event) {
-                AISX_HIPCHK(hipStreamWaitEvent(su, (hipEvent_t)ready_event, 0));
-            } else {
-                AISX_HIPCHK(hipEventRecord(T->ev_entry, st));
-                AISX_HIPCHK(hipStreamWaitEvent(su, T->ev_entry, 0));
-            }
-            if (T->ev_join_set[par])
-                AISX_HIPCHK(hipStreamWaitEvent(su, T->ev_join[par], 0));
-        }
-        if (h->tail_on && h->ev_tail_set[par])
-            AISX_HIPCHK(hipStreamWaitEvent(su, h->ev_tail[par], 0));
-        MskpPrepParams t;
-        t.nchan = h->nchan;
-        t.tags = (const tag_rec*)d_tags;
-        t.tag_count = d_tag_counts;
-        t.tag_cap = tag_cap;
-        t.W = h->total_in;
-        t.n = n;
-        t.d_sps = h->d_sps;
-        t.gain = h->gain;
-        t.limit = h->limit;
-        t.ctl = ctl;
-        t.ctl_n = ctl_n;
-        t.ctl_cap = T->ctl_cap;
-        // (units run blind to the general_work calls: with a max_noutput_items the call boundaries must
-        // leave an un-blocked loop alone, which needs d_sps >= 2 -- see mskp_body's walk)
-        t.smax = (h->max_noutput > 0 && h->d_sps < 2.0f) ? 0 : h->tp_smax;
-        t_smax = t.smax;
-        t.nrst = nrst;
-        t.rst = rst;
-        t.stage_stride = T->stage_stride;
-        t.tail = mskp_tail(h->d_sps);
-        t.min_gap = h->tp_min_gap;
-        t.max_span = h->tp_join ? h->tp_max_span : 0x3fffffff;
-        // units sorted by length need every row within 4 GiB of the first (32-bit buffer offsets)
-        static const bool tp_unsorted_env = exp_env("AISX_MSK_TP_UNSORTED") != nullptr;
-        tp_sorted = (double)h->nchan * (double)in_stride * 8.0 < 4294000000.0 && !tp_unsorted_env;
-        t.ucount = tp_sorted ? ucount : nullptr;
-        t.ulist = ulist;
-        t.ucap = (long)h->nchan * MSKP_SMAX;
-        if (tp_sorted)
-            AISX_HIPCHK(hipMemsetAsync(ucount, 0, sizeof(int) * 8, su));
-        hipLaunchKernelGGL(k_mskp_prep, dim3(h->nchan), dim3(64), 0, su, t);
-        AISX_HIPCHK(hipGetLastError());
-    } else if ((rc = msk_launch_tagprep(h, (const tag_rec*)d_tags, d_tag_counts, tag_cap, st)) != AISX_OK) {
+    MskCall c = { (const cf*)d_in, in_stride, n, (const tag_rec*)d_tags, d_tag_counts, tag_cap, (cf*)d_syms, nullptr, out_stride,
+                  (int)std::min<long>(out_stride, 0x7fffffff), par, st, ready_event };
+    int rc;
+    hipStream_t su = st; // where the prepass runs: the time-parallel one may have a stream of its own
+    if ((rc = tp ? msk_tp_prepass(h, c, &su) : msk_launch_tagprep(h, c.tags, c.tag_counts, c.tag_cap, st)) != AISX_OK)
         return rc;
-    }
     if (h->ev_prep) { // (the caller's tag records have been read)
         AISX_HIPCHK(hipEventRecord(h->ev_prep, su));
         h->ev_prep_set = true;
     }
-    cf* syms = (cf*)d_syms;
     if (h->tail_on && h->ev_tail_set[par]) // the bit tail of two calls ago may still read this parity's buffers
         AISX_HIPCHK(hipStreamWaitEvent(st, h->ev_tail[par], 0));
-    if (!syms) { // the kernel always writes symbols (the bit tail reads them back): give them a home
+    if (!c.syms) { // the kernel always writes symbols (the bit tail reads them back): give them a home
         const size_t need = (size_t)h->nchan * (size_t)out_stride;
         if (need > h->d_symscratch[par].cap()) {
             AISX_HIPCHK(hipStreamSynchronize(st));
@@ -719,178 +460,36 @@ static int msk_process_stream(aisx_msk* h, const aisx_cf32* d_in, long in_stride
                 return rc;
             AISX_HIPCHK(hipDeviceSynchronize()); // (the zero fill runs on the null stream)
         }
-        syms = h->d_symscratch[par];
+        c.syms = h->d_symscratch[par];
     }
-    int* produced = d_produced ? d_produced : (par ? h->d_produced2 : h->d_produced);
-    const int out_cap = (int)std::min<long>(out_stride, 0x7fffffff);
-    if (tp) {
-        MskpParams p;
-        p.nchan = h->nchan;
-        p.d_sps = h->d_sps;
-        p.gain = h->gain;
-        p.gain_omega = h->gain_omega;
-        p.limit = h->limit;
-        p.mu = h->d_mu;
-        p.omega = h->d_omega;
-        p.div = h->d_div;
-        p.dly1 = h->d_dly1;
-        p.dly2 = h->d_dly2;
-        p.diff1 = h->d_diff1;
-        p.nread = h->d_nread;
-        p.in = (const cf*)d_in;
-        p.in_stride = in_stride;
-        p.n = n;
-        p.carry_in = h->d_carry[h->cur];
-        p.carry_out = h->d_carry[h->cur ^ 1];
-        p.carry_len_in = h->d_carry_len[h->cur];
-        p.carry_len_out = h->d_carry_len[h->cur ^ 1];
-        p.carry_cap = aisx_msk::carry_cap;
-        p.ctag_in = h->d_ctag[h->cur];
-        p.ctag_n_in = h->d_ctag_n[h->cur];
-        p.ctag_out = h->d_ctag[h->cur ^ 1];
-        p.ctag_n_out = h->d_ctag_n[h->cur ^ 1];
-        p.ctag_cap = aisx_msk::ctag_cap;
-        p.ctl = ctl;
-        p.ctl_n = ctl_n;
-        p.ctl_cap = T->ctl_cap;
-        p.smax = h->tp_smax;
-        p.nrst = nrst;
-        p.rst = rst;
-        p.res = res;
-        p.stage = T->d_stage[par];
-        p.stage_stride = T->stage_stride;
-        p.syms = syms;
-        p.out_stride = out_stride;
-        p.out_cap = out_cap;
-        p.pieces = T->d_pieces[par];
-        p.npieces = T->d_npieces[par];
-        p.produced = produced;
-        p.consumed = h->d_consumed;
-        p.status = h->d_status;
-        p.mmse = h->d_mmse;
-        p.W = h->total_in;
-        p.look = mskp_look(h->d_sps, h->limit);
-        p.padv = mskp_padv(h->d_sps, h->gain, h->limit);
-        p.padv_inv = mskp_padv_inv(h->d_sps, h->gain, h->limit);
-        p.jw = h->tp_jw;
-        p.ucount = tp_sorted ? ucount : nullptr;
-        p.ulist = ulist;
-        p.ucap = (long)h->nchan * MSKP_SMAX;
-        p.tail = mskp_tail(h->d_sps);
-        p.max_noutput = h->max_noutput;
-        if ((rc = ensure_dyn_lds((const void*)k_mskp_units, MSKP_LDS_BYTES, "msk_timing_recovery_cc: the restart units")) != AISX_OK ||
-            (rc = ensure_dyn_lds((const void*)k_mskp_join, MSKP_LDS_BYTES, "msk_timing_recovery_cc: the join")) != AISX_OK)
-            return rc;
-        if (t_smax > 0) {
-            const long units = (long)h->nchan * h->tp_smax;
-            hipLaunchKernelGGL(k_mskp_units, dim3((unsigned)((units + 63) / 64 + (tp_sorted ? MSKP_NCLS : 0))), dim3(64), MSKP_LDS_BYTES, su, p);
-            AISX_HIPCHK(hipGetLastError());
-        }
-        if (su != st) { // the join, on the caller's stream, behind the units
-            AISX_HIPCHK(hipEventRecord(T->ev_units[par], su));
-            AISX_HIPCHK(hipStreamWaitEvent(st, T->ev_units[par], 0));
-        }
-        if (h->tp_join) {
-            // the serial kernel as the join: the loop from the carried state, fast-forwarded through the units;
-            // its tag list = the tags the scheduler still held + this call's, as the prepass compacted them
-            if ((rc = msk_launch_tagprep(h, nullptr, nullptr, 0, st, T->d_ct_nc, ctl, ctl_n, T->ctl_cap)) != AISX_OK)
-                return rc;
-            MskParams m;
-            msk_fill_common(h, m);
-            m.in = (const cf*)d_in;
-            m.in_stride = in_stride;
-            m.n = n;
-            m.stream_mode = 1;
-            m.gr_ninput = 0;
-            m.gr_noutput = 0;
-            m.syms = syms;
-            m.err = nullptr;
-            m.mu_out = nullptr;
-            m.out_stride = out_stride;
-            m.sym_al16 = 0; // (behind a fast-forward a channel's symbol count may be odd)
-            m.out_cap = out_cap;
-            m.produced = produced;
-            m.inline_tags = 0; // (every tag reset through the general step, where the junctions are looked at)
-            m.ff = 1;
-            m.nrst = nrst;
-            m.rst = rst;
-            m.res = res;
-            m.pieces = T->d_pieces[par];
-            m.npieces = T->d_npieces[par];
-            m.ct_nc = T->d_ct_nc;
-            if ((rc = msk_launch(m, (h->nchan + msk_wg_channels(h->lpw) - 1) / msk_wg_channels(h->lpw), st)) != AISX_OK)
-                return rc;
-        } else {
-            hipLaunchKernelGGL(k_mskp_join, dim3((h->nchan + h->tp_jw - 1) / h->tp_jw), dim3(64), MSKP_LDS_BYTES, st, p);
-            AISX_HIPCHK(hipGetLastError());
-        }
-        if (su != st) {
-            AISX_HIPCHK(hipEventRecord(T->ev_join[par], st));
-            T->ev_join_set[par] = true;
-        }
-        T->tp_calls++;
-    } else {
-        MskParams p;
-        msk_fill_common(h, p);
-        p.in = (const cf*)d_in;
-        p.in_stride = in_stride;
-        p.n = n;
-        p.stream_mode = 1;
-        p.gr_ninput = 0;
-        p.gr_noutput = 0;
-        p.syms = syms;
-        p.err = d_err;
-        p.mu_out = d_mu;
-        p.out_stride = out_stride;
-        p.sym_al16 = ((uintptr_t)syms % 16 == 0) && (out_stride % 2 == 0);
-        p.out_cap = out_cap;
-        p.produced = produced;
-        if ((rc = h->prof.begin(st)) != AISX_OK ||
-            (rc = msk_launch(p, (h->nchan + msk_wg_channels(h->lpw) - 1) / msk_wg_channels(h->lpw), st)) != AISX_OK ||
-            (rc = h->prof.end(st)) != AISX_OK)
-            return rc;
-    }
+    c.produced = d_produced ? d_produced : (par ? h->d_produced2 : h->d_produced);
+    if ((rc = tp ? msk_tp_units_join(h, c) : msk_launch_serial(h, c, d_err, d_mu)) != AISX_OK)
+        return rc;
     h->cur ^= 1;
     h->total_in += (unsigned long long)n;
-    MskpGatherParams g;
-    if (tp) {
-        g.nchan = h->nchan;
-        g.pieces = T->d_pieces[par];
-        g.npieces = T->d_npieces[par];
-        g.stage = T->d_stage[par];
-        g.stage_stride = T->stage_stride;
-        g.syms = syms;
-        g.out_stride = out_stride;
-        if (d_syms || !d_bits || !h->tail_on) { // the caller's own symbol rows are complete when `stream` is
-            hipLaunchKernelGGL(k_mskp_gather, dim3(MSKP_GATHER_X, h->nchan), dim3(256), 0, st, g);
-            AISX_HIPCHK(hipGetLastError());
-            // this gather reads d_stage[par] / d_res[par], which the units of the call after next overwrite on
-            // their own stream: they wait for ev_join[par], so it has to stand BEHIND the gather (without a
-            // bit tail on another stream nothing else orders the two)
-            if (T->ev_join_set[par])
-                AISX_HIPCHK(hipEventRecord(T->ev_join[par], st));
-        }
-    }
-    if (d_bits) {
-        // a call produces at most forecast^-1(n + carry) symbols; out_cap bounds it too
-        const double wmin = (double)h->d_sps - fabs((double)h->limit);
-        const int max_out = std::min<long>(out_cap, (long)ceil((n + aisx_msk::carry_cap) / (2.0 * wmin)) * h->osps + 16);
-        hipStream_t ts = st;
-        if (h->tail_on) { // the bit tail has no part in the recurrence: let the next call start
-            AISX_HIPCHK(hipEventRecord(h->ev_msk, st));
-            AISX_HIPCHK(hipStreamWaitEvent(h->tail_stream, h->ev_msk, 0));
-            ts = h->tail_stream;
-            if (tp && !d_syms) { // the units' symbols join the others on the tail stream
-                hipLaunchKernelGGL(k_mskp_gather, dim3(MSKP_GATHER_X, h->nchan), dim3(256), 0, ts, g);
-                AISX_HIPCHK(hipGetLastError());
-            }
-        }
-        if ((rc = msk_launch_bittail(h, syms, out_stride, produced, d_bits, out_stride, max_out, ts)) != AISX_OK)
+    // the units' symbols: with bits only and a tail stream they are gathered there, ahead of the bit tail; the
+    // caller's own symbol rows are complete when `stream` is
+    const bool gather_on_tail = tp && !d_syms && d_bits && h->tail_on;
+    if (tp && !gather_on_tail && (rc = msk_tp_gather(h, c, false)) != AISX_OK)
+        return rc;
+    if (!d_bits)
+        return AISX_OK;
+    // a call produces at most forecast^-1(n + carry) symbols; out_cap bounds it too
+    const double wmin = (double)h->d_sps - fabs((double)h->limit);
+    const int max_out = std::min<long>(c.out_cap, (long)ceil((n + aisx_msk::carry_cap) / (2.0 * wmin)) * h->osps + 16);
+    hipStream_t ts = st;
+    if (h->tail_on) { // the bit tail has no part in the recurrence: let the next call start
+        AISX_HIPCHK(hipEventRecord(h->ev_msk, st));
+        AISX_HIPCHK(hipStreamWaitEvent(h->tail_stream, h->ev_msk, 0));
+        ts = h->tail_stream;
+        if (gather_on_tail && (rc = msk_tp_gather(h, c, true)) != AISX_OK)
             return rc;
-        if (h->tail_on) {
-            AISX_HIPCHK(hipEventRecord(h->ev_tail[par], h->tail_stream));
-            h->ev_tail_set[par] = true;
-        }
+    }
+    if ((rc = msk_launch_bittail(h, c.syms, out_stride, c.produced, d_bits, out_stride, max_out, ts)) != AISX_OK)
+        return rc;
+    if (h->tail_on) {
+        AISX_HIPCHK(hipEventRecord(h->ev_tail[par], h->tail_stream));
+        h->ev_tail_set[par] = true;
     }
     return AISX_OK;
 }
@@ -1006,53 +605,6 @@ extern "C" int aisx_msk_kernel_ms_history(aisx_msk* h, float* ms, int cap, int* 
     return h && ms && n ? h->prof.history(ms, cap, n) : AISX_ERR_INVALID;
 }
 
-// what the time-parallel path made of the last call (diagnostics; waits for `stream`)
-extern "C" int aisx_msk_restart_stats(aisx_msk* h, long long* out10, void* stream)
-{
-    if (!h || !out10)
-        return AISX_ERR_INVALID;
-    for (int i = 0; i < 10; i++) // (ten entries: include/aisx.h)
-        out10[i] = 0;
-    const aisx_msk::Tp* T = h->tp.get();
-    if (!T || T->tp_calls == 0) // (the path never ran on this handle)
-        return AISX_OK;
-    out10[5] = T->tp_calls;
-    const int par = h->callpar ^ 1; // the call before this one
-    const size_t nc = (size_t)h->nchan;
-    std::vector<int> nrst(nc), np(nc);
-    std::vector<mskp_piece> pc(nc * MSKP_SMAX);
-    std::vector<mskp_res> rs(nc * MSKP_SMAX);
-    std::vector<mskp_rst> rp(nc * MSKP_SMAX);
-    AISX_HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    // (a pipelined caller's join runs on a stream of its own: its records are complete behind ev_join)
-    if (T->ev_join_set[par])
-        AISX_HIPCHK(hipEventSynchronize(T->ev_join[par]));
-    AISX_HIPCHK(hipMemcpy(nrst.data(), T->d_nrst + par * nc, sizeof(int) * nc, hipMemcpyDeviceToHost));
-    AISX_HIPCHK(hipMemcpy(np.data(), T->d_npieces[par], sizeof(int) * nc, hipMemcpyDeviceToHost));
-    AISX_HIPCHK(hipMemcpy(pc.data(), T->d_pieces[par], sizeof(mskp_piece) * pc.size(), hipMemcpyDeviceToHost));
-    AISX_HIPCHK(hipMemcpy(rs.data(), T->d_res + par * nc * MSKP_SMAX, sizeof(mskp_res) * rs.size(), hipMemcpyDeviceToHost));
-    AISX_HIPCHK(hipMemcpy(rp.data(), T->d_rst + par * nc * MSKP_SMAX, sizeof(mskp_rst) * rp.size(), hipMemcpyDeviceToHost));
-    for (size_t c = 0; c < nc; c++) {
-        out10[0] += nrst[c];                     // restart points chosen
-        out10[1] += np[c];                       // units whose run was taken over
-        for (int i = 0; i < np[c]; i++)
-            out10[2] += pc[c * MSKP_SMAX + i].cnt; // symbols that came from units
-        for (int i = 0; i < nrst[c]; i++) {
-            out10[3] += rs[c * MSKP_SMAX + i].kind == MSKP_KIND_NEXT;    // units that ended at the next restart point
-            out10[4] += rs[c * MSKP_SMAX + i].kind == MSKP_KIND_HANDOFF; // ... somewhere else (stale tag, end of the row)
-            const long long span = rs[c * MSKP_SMAX + i].end.a - rp[c * MSKP_SMAX + i].relA;
-            out10[8] = std::max(out10[8], span); // longest unit, items
-            out10[9] += span;
-            // links: a unit that ended at the next restart point with exactly the delay registers that one assumed
-            if (i + 1 < nrst[c] && rs[c * MSKP_SMAX + i].kind == MSKP_KIND_NEXT) {
-                const mskp_res &a = rs[c * MSKP_SMAX + i], &b = rs[c * MSKP_SMAX + i + 1];
-                out10[6] += mskp_same_bits(a.end.y, b.ay) && mskp_same_bits(a.end.nl, b.anl);
-                out10[7] += 1;
-            }
-        }
-    }
-    return AISX_OK;
-}
 
 extern "C" int aisx_msk_last_status(aisx_msk* h, int* status, void* stream)
 {

@@ -30,7 +30,8 @@ def _dev(x):
     return torch.as_tensor(np.ascontiguousarray(x)).cuda()
 
 
-def _stream(ais, nchan, lens, seed, join, Q, neg_frac, pair_every, nan_at=None, every=1, sps=4.0):
+def _stream(ais, nchan, lens, seed, join, Q, neg_frac, pair_every, nan_at=None, every=1, sps=4.0, tail=False, caps=None):
+    """`tail`: the bit tail on a stream of its own; `caps`: the tag_cap of every call (default: one for all)"""
     import torch
     import synth
 
@@ -40,19 +41,22 @@ def _stream(ais, nchan, lens, seed, join, Q, neg_frac, pair_every, nan_at=None, 
     blk = ais.msk_timing_recovery_cc(sps, 0.04, 0.01, 1, nchan=nchan, max_items=max(lens))
     blk.set_time_parallel(64, join_kernel=join, max_unit_items=16384)
     blk.set_max_noutput_items(Q)
+    if tail:
+        blk.set_tail_stream(torch.cuda.Stream())
     o = {c: orc.MskStream(sps, 0.04, 0.01, 1, max_noutput=Q) for c in range(0, nchan, every)}
     bt = {c: orc.BitTail() for c in o}
     all_tags = [_tags_with_pairs(rng, total, c, sps, pair_every, neg_frac, 6, nan_at) for c in range(nchan)]
     for c in range(nchan):
         all_tags[c].dtype.names  # (TAG_DTYPE of the lane model = ais.TAG_DTYPE's layout)
     k, stats = 0, []
-    for L in lens:
-        cap = max(len(t) for t in all_tags) + 1
+    for i, L in enumerate(lens):
+        cap = caps[i] if caps else max(len(t) for t in all_tags) + 1
         tg = np.zeros((nchan, cap), dtype=ais.TAG_DTYPE)
         cnt = np.zeros(nchan, np.int32)
         new = []
         for c in range(nchan):
             sel = all_tags[c][(all_tags[c]["offset"] >= k) & (all_tags[c]["offset"] < k + L)]
+            assert len(sel) <= cap
             for f in ("offset", "value", "key", "chan"):
                 tg[f][c, : len(sel)] = sel[f]
             cnt[c] = len(sel)
@@ -60,6 +64,8 @@ def _stream(ais, nchan, lens, seed, join, Q, neg_frac, pair_every, nan_at=None, 
         d_tags = torch.as_tensor(tg.view(np.uint8).reshape(nchan, -1).copy()).cuda()
         d_cnt = torch.as_tensor(cnt).cuda()
         r = blk.work(_dev(xs[:, k:k + L]), tags_ptrs=(d_tags.data_ptr(), d_cnt.data_ptr(), cap))
+        if tail:
+            blk.wait_tail()  # (the current stream now waits for the tail)
         assert blk.last_status() == 0
         stats.append(blk.restart_stats())
         prod = r["produced"].cpu().numpy()
@@ -95,6 +101,22 @@ def test_time_parallel_with_failing_junctions(ais, join):
     assert s["restart_points"] >= 66 * 40
     assert s["units_taken"] < s["restart_points"]
     assert s["units_taken"] >= 0.3 * s["restart_points"]
+
+
+@pytest.mark.parametrize("join", [1, 0])
+def test_time_parallel_symbols_and_bits_with_a_tail_stream(ais, join):
+    """The caller takes symbols AND bits and the bit tail runs on a stream of its own: the gather of the units'
+    symbols runs on the call's stream, ahead of the tail.  9 channels = two waves of the 8-channel build, the second
+    ragged; tag pairs every 400 items give every channel several restart points in the long calls."""
+    stats = _stream(ais, 9, [3000, 37, 2500], seed=3, join=join, Q=0, neg_frac=0.3, pair_every=400, tail=True)
+    assert all(s["units_taken"] > 0 for s in (stats[0], stats[2]))
+
+
+def test_time_parallel_tag_capacity_grows_in_mid_life(ais):
+    """tag_cap 32 in the first call, 96 and 256 in the later ones, with the mode on from the start: the prepass's
+    tag lists are re-allocated on a handle whose units' stream has run."""
+    stats = _stream(ais, 9, [3000, 37, 2500], seed=4, join=1, Q=0, neg_frac=0.3, pair_every=400, caps=[32, 96, 256])
+    assert all(s["units_taken"] > 0 for s in (stats[0], stats[2]))
 
 
 @pytest.mark.parametrize("Q", [256, 2048])
