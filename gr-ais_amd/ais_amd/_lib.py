@@ -25,6 +25,8 @@ AISX_FMT_CF32, AISX_FMT_CS16, AISX_FMT_CS8, AISX_FMT_CU8 = 0, 1, 2, 3
 AISX_RX_ST_HDLC_OVERFLOW, AISX_RX_ST_NMEA_OVERFLOW, AISX_RX_ST_BAD_COUNT = 0x100, 0x200, 0x400
 AISX_MSG_NA, AISX_MSG_STR = -(1 << 31), 48
 AISX_HDLC_MAX_RULES = 16
+AISX_MLSE_ST_BAD_COUNT = 1
+MLSE_BLOCK, MLSE_OVERLAP = 64, 16  # symbols a block of the sequence detector decides, and its window's overlap
 AISX_MSG_FL_COMPLETE, AISX_MSG_FL_NO_LAYOUT, AISX_MSG_FL_BAD_RECORD = 1, 2, 4
 
 KEY_CORR_START, KEY_PHASE_EST, KEY_TIME_EST, KEY_CORR_EST, KEY_PORT1 = 0, 1, 2, 3, 0x100
@@ -254,6 +256,20 @@ def lib(device=True):
     sig("aisx_tx_batch_set_bursts", i32, [vp, vp, i32, vp, i64, vp])
     sig("aisx_tx_batch_render", i32, [vp, i64, i64, vp, i64, i32, vp])
     sig("aisx_tx_batch_read_levels", i32, [vp, i32, vp, i32, pi32, vp])
+    sig("aisx_mlse_create", i32, [pvp, f64])
+    sig("aisx_mlse_destroy", i32, [vp])
+    sig("aisx_mlse_reset", i32, [vp])
+    sig("aisx_mlse_model", i32, [vp, pf64, pf64, vp])
+    sig("aisx_mlse_work", i32, [vp, vp, i32, vp, i32, pi32])
+    sig("aisx_mlse_flush", i32, [vp, vp, i32, pi32])
+    sig("aisx_mlse_batch_create", i32, [pvp, f64, i32, i32])
+    sig("aisx_mlse_batch_destroy", i32, [vp])
+    sig("aisx_mlse_batch_reset", i32, [vp])
+    sig("aisx_mlse_batch_process", i32, [vp, vp, lng, vp, vp, lng, vp, vp])
+    sig("aisx_mlse_batch_flush", i32, [vp, vp, lng, vp, vp])
+    sig("aisx_mlse_batch_status", i32, [vp, pi32, vp])
+    sig("aisx_mlse_batch_status_device", i32, [vp, pvp])
+    sig("aisx_rx_enable_mlse", i32, [vp, f64])
     _lib = L
     return L
 

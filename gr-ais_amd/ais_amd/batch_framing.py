@@ -131,6 +131,64 @@ class hdlc_deframer_batch:
         return recs, data
 
 
+class mlse_detector_batch:
+    """ais_amd.mlse_detector for nchan channels of at most max_syms symbols per call on the device (aisx_mlse_batch_*):
+    per channel exactly the host form's bits, call by call.  Between the pipelined chain and the deframer, on a stream
+    `s` of the caller's (the deframer's max_bits = max_syms + 79: a call also decides symbols it carried):
+
+        r = dem.work_pipelined(x_k, x_next, want_syms=True)
+        dem.wait(r["step"], stream=s)
+        bits, nbits = det.process(r["syms"], r["produced"], stream=s)
+        hd.work(bits, nbits, stream=s)
+
+    process() returns the handle's own output tensors, which the next process() or flush() overwrites."""
+
+    def __init__(self, nchan, max_syms, bt=0.4):
+        h = C.c_void_p()
+        check(_lib.lib().aisx_mlse_batch_create(C.byref(h), float(bt), int(nchan), int(max_syms)), "mlse_detector_batch")
+        self._h = h
+        self.nchan, self.max_syms, self.bt = int(nchan), int(max_syms), float(bt)
+        self.max_bits = self.max_syms + _lib.MLSE_BLOCK + _lib.MLSE_OVERLAP - 1
+        self._bits = torch.zeros((self.nchan, self.max_bits), dtype=torch.uint8, device="cuda")
+        self._nbits = torch.zeros(self.nchan, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()  # (the fills ran on torch's stream; the first call may be queued on any)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            _lib.lib().aisx_mlse_batch_destroy(h)
+            self._h = None
+
+    def reset(self):
+        check(_lib.lib().aisx_mlse_batch_reset(self._h), "mlse_detector_batch.reset")
+
+    def process(self, syms, nsyms, stream=None):
+        """syms: complex64 device tensor [nchan][>= max_syms], row c holding nsyms[c] symbols (int32 device tensor
+        [nchan]).  Queued on `stream` (default: the current one); nothing waits.  Returns (bits, nbits): uint8
+        [nchan][max_syms + 79] and int32 [nchan], as hdlc_deframer_batch.work takes them."""
+        if syms.dtype != torch.complex64 or not syms.is_cuda or syms.dim() != 2 or syms.shape[0] != self.nchan or syms.stride(1) != 1:
+            raise ValueError("mlse_detector_batch.process: syms must be a complex64 device tensor [nchan][n] with unit item stride")
+        if nsyms.dtype != torch.int32 or not nsyms.is_cuda or nsyms.numel() != self.nchan or not nsyms.is_contiguous():
+            raise ValueError("mlse_detector_batch.process: nsyms must be a contiguous int32 device tensor [nchan]")
+        check(_lib.lib().aisx_mlse_batch_process(self._h, syms.data_ptr(), syms.stride(0) if self.nchan > 1 else max(syms.stride(0), self.max_syms),
+                                                 nsyms.data_ptr(), self._bits.data_ptr(), self._bits.stride(0), self._nbits.data_ptr(),
+                                                 _stream_ptr(stream)), "mlse_detector_batch.process")
+        return self._bits, self._nbits
+
+    def flush(self, stream=None):
+        """the bits of every channel's undecided symbols (at most 79 each); the channels are left as new"""
+        check(_lib.lib().aisx_mlse_batch_flush(self._h, self._bits.data_ptr(), self._bits.stride(0), self._nbits.data_ptr(),
+                                               _stream_ptr(stream)), "mlse_detector_batch.flush")
+        return self._bits, self._nbits
+
+    def status(self, stream=None):
+        """0, or AISX_MLSE_ST_BAD_COUNT when a call since the last read met a count outside [0, max_syms] (that channel
+        took no symbols); synchronises `stream`"""
+        st = C.c_int(0)
+        check(_lib.lib().aisx_mlse_batch_status(self._h, C.byref(st), _stream_ptr(stream)), "mlse_detector_batch.status")
+        return st.value
+
+
 def nmea_text_len(length, dlen):
     """what pdu_to_nmea's msg_to_sentence returns for a payload of `length` octets and a designator of dlen bytes,
     in characters (fragments of 56 payload characters, separated by '\n'); 0 for an empty payload"""

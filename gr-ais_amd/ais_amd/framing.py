@@ -87,6 +87,55 @@ class hdlc_deframer_bp:
         return [bytes(buf[offs[k]:offs[k + 1]]) for k in range(n.value)], [int(v) for v in fix[: n.value]]
 
 
+class mlse_detector:
+    """The 4-state sequence detector behind the timing recovery, on the host (aisx_mlse_*): the recovery's symbols (one
+    per symbol, complex64) to the bit stream the demod's bit tail gives (NRZI decoded, inverted; bit n belongs to symbol
+    n), the levels decided by a Viterbi search over the differential phase of BT = bt GMSK instead of one phase step
+    each.  Blocks of 64 symbols are decided once 16 more have arrived: work() returns the bits of the blocks that
+    became complete (any split of a stream into calls gives the same bits), flush() those of the rest and leaves the
+    detector as new.
+
+        bits = np.concatenate([det.work(syms), det.flush()])
+        pdus = ais_amd.hdlc_deframer_bp(11, 64).work(bits)"""
+
+    def __init__(self, bt=0.4):
+        h = C.c_void_p()
+        check(_lib.lib(device=False).aisx_mlse_create(C.byref(h), float(bt)), "mlse_detector")
+        self._h = h
+        self.bt = float(bt)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            _lib.lib(device=False).aisx_mlse_destroy(h)
+            self._h = None
+
+    def model(self):
+        """(c0, c1, rot): the phase a level adds to its own symbol and to each neighbour, in quarter turns, and the
+        float32 (cos, sin) of the eight level triples as rot[p][q][r]"""
+        c0, c1 = C.c_double(), C.c_double()
+        rot = np.zeros((2, 2, 2, 2), dtype=np.float32)
+        check(_lib.lib(device=False).aisx_mlse_model(self._h, C.byref(c0), C.byref(c1), rot.ctypes.data_as(C.c_void_p)), "mlse_detector.model")
+        return c0.value, c1.value, rot
+
+    def reset(self):
+        check(_lib.lib(device=False).aisx_mlse_reset(self._h), "mlse_detector.reset")
+
+    def work(self, syms):
+        s = np.ascontiguousarray(syms, dtype=np.complex64).ravel()
+        bits = np.zeros(s.size + _lib.MLSE_BLOCK + _lib.MLSE_OVERLAP, dtype=np.uint8)
+        n = C.c_int(0)
+        check(_lib.lib(device=False).aisx_mlse_work(self._h, s.ctypes.data_as(C.c_void_p), s.size, bits.ctypes.data_as(C.c_void_p),
+                                                    bits.size, C.byref(n)), "mlse_detector.work")
+        return bits[: n.value].copy()
+
+    def flush(self):
+        bits = np.zeros(_lib.MLSE_BLOCK + _lib.MLSE_OVERLAP, dtype=np.uint8)
+        n = C.c_int(0)
+        check(_lib.lib(device=False).aisx_mlse_flush(self._h, bits.ctypes.data_as(C.c_void_p), bits.size, C.byref(n)), "mlse_detector.flush")
+        return bits[: n.value].copy()
+
+
 class pdu_to_nmea:
     def __init__(self, designator):
         self.designator = str(designator)

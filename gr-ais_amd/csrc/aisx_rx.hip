@@ -1,22 +1,25 @@
 // aisx_rx.hip -- C ABI of the host-fed receiver (include/aisx.h, aisx_rx_*): python/radio.py's ais_rx as one handle
 // for nstreams sources, fed from pinned host memory in the source's own sample format.  Nothing here computes: the
 // handle owns the filter (aisx_xlate), the four stage handles and their chain, the deframer and the NMEA stage (and,
-// once aisx_rx_enable_messages asked for it, the field decoder behind that, and after aisx_rx_enable_tracks the vessel
-// table behind the decoder), and the rings, streams and events that
+// once aisx_rx_enable_messages asked for it, the field decoder behind that, after aisx_rx_enable_tracks the vessel
+// table behind the decoder, and after aisx_rx_enable_mlse the sequence detector between the chain step and the
+// deframer), and the rings, streams and events that
 // order them (INTEGRATION.md states the rules; this file is their one home).
 //
 //   block b, submitted:   copy stream    pinned slot b % NPIN -> raw buffer b % NRAW      (after filter b - NRAW)
 //                         filter stream  raw buffer -> row buffer b % NROW                (after wait_input(b - NROW))
 //                         chain          step b - 1 with d_in_next = row buffer b % NROW  (after tail b - 1 - DEPTH)
-//                         tail stream    wait(step b - 1), deframer, NMEA, status, results -> pinned result slot
+//                         tail stream    wait(step b - 1), [detector,] deframer, NMEA, status, results -> pinned result slot
 //
 // so the copy of block b + 1 runs beside the compute of block b, and the host never waits for the device in submit.
 #include <string.h>
 
+#include <string>
 #include <vector>
 
 #include "aisx_devctx.h"
 #include "aisx_host.h"
+#include "k_mlse.h"
 #include "k_nmea.h"
 #include "k_xlate.h"
 
@@ -58,8 +61,9 @@ std::vector<float> low_pass(double fs, double cutoff, double transition)
 
 // one workgroup: the recovery's status words or-ed over the channels, and the deframer's and the NMEA stage's counts,
 // gathered into one record for the copy back
+// (ml_flag: the detector's bad-count word or nullptr; it counts as the deframer's)
 __global__ __launch_bounds__(256) void k_rx_meta(const int* __restrict__ msk_status, int nchan, const int* __restrict__ hd_count,
-                                                 const int* __restrict__ nm_count, int* __restrict__ meta)
+                                                 const int* __restrict__ nm_count, const int* __restrict__ ml_flag, int* __restrict__ meta)
 {
     __shared__ int acc;
     if (threadIdx.x == 0)
@@ -77,6 +81,8 @@ __global__ __launch_bounds__(256) void k_rx_meta(const int* __restrict__ msk_sta
             meta[1 + i] = hd_count[i];
             meta[4 + i] = nm_count[i];
         }
+        if (ml_flag)
+            meta[3] |= *ml_flag;
         meta[7] = 0;
     }
 }
@@ -104,12 +110,19 @@ struct aisx_rx {
     const int32_t* d_fix = nullptr;    // only after aisx_rx_enable_repair: the deframer's marks,
     size_t fix_off = 0;                // and where they go in a result slot: int32 fix_bits[max_pdus]
     std::vector<int32_t> popped_fix;   // the marks of the block popped last
+    std::vector<aisx_hdlc_rule> rules; // what aisx_rx_enable_repair set (a deframer made again gets them again)
+    aisx_mlse_batch* ml = nullptr;     // only after aisx_rx_enable_mlse: the detector between the chain step and the deframer
+    const int* d_ml_flag = nullptr;
+    int mstride = 0;                   // row stride of d_mbits: cap + what the detector carries
     Stream s_copy, s_filt, s_tail;     // (before the buffers and events used on them: destroyed after those)
     PinnedBuf<char> h_in[RX_NPIN];     // pinned [ns][block_items] items
     DevBuf<char> d_raw[RX_NRAW];
     DevBuf<cf> d_row[RX_NROW];         // [ns * nch][T]
     DevBuf<uint8_t> d_bits[RX_NOUT];   // [ns * nch][cap]
     DevBuf<int> d_prod[RX_NOUT];
+    DevBuf<cf> d_syms[RX_NOUT];        // [ns * nch][cap], only with the detector
+    DevBuf<uint8_t> d_mbits;           // [ns * nch][mstride] the detector's bits (read by the deframer behind it on the tail stream)
+    DevBuf<int> d_mnb;
     DevBuf<int> d_meta;
     PinnedBuf<char> h_res[RX_NRES];    // pinned: int meta[RX_META], aisx_pdu recs[max_pdus], char text[text_cap]
     Event ev_copy[RX_NPIN];            // the slot's copy to the device has finished
@@ -158,6 +171,7 @@ extern "C" int aisx_rx_destroy(aisx_rx* h)
     (void)aisx_msg_batch_destroy(h->mg);
     (void)aisx_nmea_batch_destroy(h->nm);
     (void)aisx_hdlc_batch_destroy(h->hd);
+    (void)aisx_mlse_batch_destroy(h->ml);
     (void)aisx_msk_destroy(h->msk);
     (void)aisx_corr_destroy(h->corr);
     (void)aisx_agc_destroy(h->agc);
@@ -347,25 +361,33 @@ static int rx_issue(aisx_rx* h, long long k, const cf* next)
     if (k >= RX_NOUT) // the deframer has read this set's bits of step k - NOUT
         AISX_HIPCHK(hipStreamWaitEvent(h->s_filt, h->ev_tail[set], 0));
     long long step = -1;
-    if ((rc = aisx_chain_step(h->chain, (const aisx_cf32*)h->d_row[k % RX_NROW].get(), T, T, (const aisx_cf32*)next, T, next ? T : 0, nullptr,
-                              h->d_bits[set], h->cap, h->d_prod[set], h->s_filt, &step)) != AISX_OK)
+    if ((rc = aisx_chain_step(h->chain, (const aisx_cf32*)h->d_row[k % RX_NROW].get(), T, T, (const aisx_cf32*)next, T, next ? T : 0,
+                              h->ml ? (aisx_cf32*)h->d_syms[set].get() : nullptr, h->d_bits[set], h->cap, h->d_prod[set], h->s_filt, &step)) != AISX_OK)
         return rc;
     if (step != k) {
         set_err("aisx_rx: the chain numbered block %lld as step %lld", k, step);
         return AISX_ERR_RUNTIME;
     }
     hipStream_t st = h->s_tail;
-    if ((rc = aisx_chain_wait(h->chain, k, st, 0)) != AISX_OK ||
-        (rc = aisx_hdlc_batch_process(h->hd, h->d_bits[set], h->cap, h->d_prod[set], st)) != AISX_OK)
+    if ((rc = aisx_chain_wait(h->chain, k, st, 0)) != AISX_OK)
+        return rc;
+    if (h->ml) { // the step's symbols -> the detector's bits and counts -> the deframer
+        if ((rc = aisx_mlse_batch_process(h->ml, (const aisx_cf32*)h->d_syms[set].get(), h->cap, h->d_prod[set], h->d_mbits, h->mstride,
+                                          h->d_mnb, st)) != AISX_OK ||
+            (rc = aisx_hdlc_batch_process(h->hd, h->d_mbits, h->mstride, h->d_mnb, st)) != AISX_OK)
+            return rc;
+    } else if ((rc = aisx_hdlc_batch_process(h->hd, h->d_bits[set], h->cap, h->d_prod[set], st)) != AISX_OK)
         return rc;
     AISX_HIPCHK(hipEventRecord(h->ev_tail[set], st));
     if ((rc = aisx_nmea_batch_process(h->nm, h->d_hd_pdus, h->d_hd_bytes, h->d_hd_count + 1, h->d_hd_count, st)) != AISX_OK)
         return rc;
-    hipLaunchKernelGGL(k_rx_meta, dim3(1), dim3(256), 0, st, h->d_msk_status, rows, h->d_hd_count, h->d_nm_count, h->d_meta);
+    hipLaunchKernelGGL(k_rx_meta, dim3(1), dim3(256), 0, st, h->d_msk_status, rows, h->d_hd_count, h->d_nm_count, h->d_ml_flag, h->d_meta);
     AISX_HIPCHK(hipGetLastError());
     // (the bad-input flags are this block's: cleared behind the record that took them)
     AISX_HIPCHK(hipMemsetAsync((void*)(h->d_hd_count + 2), 0, sizeof(int), st));
     AISX_HIPCHK(hipMemsetAsync((void*)(h->d_nm_count + 2), 0, sizeof(int), st));
+    if (h->d_ml_flag)
+        AISX_HIPCHK(hipMemsetAsync((void*)h->d_ml_flag, 0, sizeof(int), st));
     char* r = h->h_res[res];
     if (h->mg) { // the rows of the records the NMEA stage kept; its bad-input flag goes into the record's spare word
         if ((rc = aisx_msg_batch_process(h->mg, h->d_hd_pdus, h->d_hd_bytes, h->d_nm_count + 1, h->d_hd_count, st)) != AISX_OK)
@@ -650,6 +672,74 @@ extern "C" int aisx_rx_enable_repair(aisx_rx* h, const aisx_hdlc_rule* rules, in
         h->res_bytes = bytes;
     }
     h->d_fix = d_fix;
+    h->rules.assign(rules, rules + nrules);
+    return AISX_OK;
+}
+
+extern "C" int aisx_rx_enable_mlse(aisx_rx* h, double bt)
+{
+    if (!h) {
+        set_err("aisx_rx_enable_mlse: need a handle");
+        return AISX_ERR_INVALID;
+    }
+    if (h->failed != AISX_OK)
+        return rx_failed(h, "aisx_rx_enable_mlse");
+    if (h->ml || h->acquired || h->submitted > 0) {
+        set_err("aisx_rx_enable_mlse: once, and only before the first acquire, submit or push");
+        return AISX_ERR_INVALID;
+    }
+    OnDevice on(h->dev);
+    AISX_HIPCHK(on.err);
+    const int rows = h->ns * h->nch, mstride = h->cap + MLSE_EXTRA;
+    // everything is made beside what the handle has, and put in its place only when all of it exists
+    aisx_mlse_batch* made_ml = nullptr;
+    int rc = aisx_mlse_batch_create(&made_ml, bt, rows, h->cap);
+    HandlePtr<aisx_mlse_batch, aisx_mlse_batch_destroy> ml(made_ml);
+    aisx_hdlc_batch* made_hd = nullptr; // a deframer for the detector's calls: a step's symbols and the carried ones
+    if (rc == AISX_OK)
+        rc = aisx_hdlc_batch_create(&made_hd, RX_LMIN, RX_LMAX, rows, mstride, h->max_pdus);
+    HandlePtr<aisx_hdlc_batch, aisx_hdlc_batch_destroy> hd(made_hd);
+    if (rc == AISX_OK && !h->rules.empty())
+        rc = aisx_hdlc_batch_set_repair(hd.get(), h->rules.data(), (int)h->rules.size());
+    DevBuf<cf> syms[RX_NOUT];
+    DevBuf<uint8_t> mbits;
+    DevBuf<int> mnb;
+    for (int i = 0; rc == AISX_OK && i < RX_NOUT; i++)
+        rc = syms[i].alloc((size_t)rows * h->cap, false);
+    if (rc == AISX_OK && (rc = mbits.alloc((size_t)rows * mstride, false)) == AISX_OK)
+        rc = mnb.alloc((size_t)rows);
+    const aisx_pdu* pdus = nullptr;
+    const uint8_t* bytes = nullptr;
+    const int *count = nullptr, *flag = nullptr;
+    const int32_t* d_fix = nullptr;
+    if (rc == AISX_OK && (rc = aisx_hdlc_batch_results_device(hd.get(), &pdus, &bytes, &count)) == AISX_OK &&
+        (rc = aisx_mlse_batch_status_device(ml.get(), &flag)) == AISX_OK && h->d_fix)
+        rc = aisx_hdlc_batch_repairs_device(hd.get(), &d_fix);
+    if (rc == AISX_OK && hipDeviceSynchronize() != hipSuccess) { // (the zero fills ran on the null stream)
+        set_err("aisx_rx_enable_mlse: hipDeviceSynchronize failed");
+        rc = AISX_ERR_HIP;
+    }
+    if (rc != AISX_OK) { // (the handle stays as it was; what is released on the way out must not replace the message)
+        const std::string msg = aisx_last_error();
+        hd.reset();
+        ml.reset();
+        set_err("%s", msg.c_str());
+        return rc;
+    }
+    (void)aisx_hdlc_batch_destroy(h->hd);
+    h->hd = hd.release();
+    h->d_hd_pdus = pdus;
+    h->d_hd_bytes = bytes;
+    h->d_hd_count = count;
+    if (h->d_fix)
+        h->d_fix = d_fix;
+    for (int i = 0; i < RX_NOUT; i++)
+        h->d_syms[i] = std::move(syms[i]);
+    h->d_mbits = std::move(mbits);
+    h->d_mnb = std::move(mnb);
+    h->mstride = mstride;
+    h->d_ml_flag = flag;
+    h->ml = ml.release();
     return AISX_OK;
 }
 

@@ -895,6 +895,17 @@ int aisx_rx_read_tracks(aisx_rx* h, int first, int n, int32_t* cols, long col_st
                         long long* block);
 int aisx_rx_read_changed_tracks(aisx_rx* h, int* idx, int32_t* cols, long col_stride, char* strs, int cap, int* nchanged,
                                 long long* block);
+/* Opt-in: the bits the deframer reads are decided by the 4-state sequence detector (aisx_mlse_batch_*, below) of BT = bt
+ * GMSK instead of the one-symbol slicer.  From the first block on every chain step also writes its symbols (one of
+ * AISX_CHAIN_DEPTH buffers of the handle's), and the tail stream queues the detector between the step and the deframer,
+ * which is made again for the detector's longer calls (max_bits + 79; rules set by aisx_rx_enable_repair are kept).
+ * Deframer, repair, NMEA, decoder and vessel table work as before behind it, and a record's end_bit counts the same
+ * bits: bit n belongs to symbol n.  The detector decides a symbol once 80 to 143 later ones have arrived, so the last
+ * 16 to 79 symbols of a channel stay undecided until more input follows; aisx_rx_flush does not flush the detector
+ * (input may follow), and a burst that ends within them appears with the next block.  Only before the first
+ * acquire, submit or push (AISX_ERR_INVALID afterwards, and for bt outside [0.1, 1]); a handle on which this was never
+ * called allocates, queues and copies nothing more. */
+int aisx_rx_enable_mlse(aisx_rx* h, double bt);
 /* from the next submitted block on (aisx_xlate_set_center_freq of the handle's filter) */
 int aisx_rx_set_center_freq(aisx_rx* h, int stream, int chan, double center_freq);
 /* A failed block (a HIP error, the chain refusing) makes every later call but destroy return that block's error. */
@@ -968,6 +979,63 @@ int aisx_tx_batch_render(aisx_tx_batch* h, int64_t t0, int64_t n, aisx_cf32* d_o
  * aisx_tx_batch_set_bursts), unpacked to one 0 / 1 per byte; synchronises `stream`.  *nsyms = the device's symbol
  * count; AISX_ERR_OVERFLOW when cap is smaller (nothing written). */
 int aisx_tx_batch_read_levels(aisx_tx_batch* h, int index, uint8_t* levels, int cap, int* nsyms, void* stream);
+
+/* ------------------------------------------------------------------------ */
+/* 4-state sequence detector behind the timing recovery: the recovery's       */
+/* symbols (one per symbol) to the bit stream the bit tail produces (NRZI     */
+/* decoded, inverted; bit n belongs to symbol n), the levels decided by a     */
+/* Viterbi search over the differential phase instead of one phase step each. */
+/* On the host (the specification) and batched on the device, bit for bit.    */
+/* ------------------------------------------------------------------------ */
+/* Per channel: symbols s[0], s[1], ... with s[-1] = 0; z[n] = s[n] conj(s[n-1]), re = fma(a.im, b.im, a.re * b.re),
+ * im = fma(a.im, b.re, -(a.re * b.im)) for a = s[n], b = s[n-1].  Levels b in {0, 1}, X = 2 x - 1 (1: a positive
+ * phase step, as the slicer's).  z[n] turns by
+ *     theta(p, q, r) = (pi/2) (c0 Q + c1 (P + R))      for (b[n-1], b[n], b[n+1]) = (p, q, r),
+ * c0 = q(2.5) - q(1.5), c1 = q(3.5) - q(2.5) of the transmitter's L = 4 phase pulse q (above) at the handle's bt, in
+ * double: 0.735928 and 0.131918 at bt = 0.4.  rot[p][q][r] = ((float)cos theta, (float)sin theta) is made once.
+ * Branch metric g(n; p, q, r) = fma(z.im, sin, z.re * cos), in float.
+ * Blocks of 64 symbols by absolute index, 16 symbols of overlap on each side: block k covers [64 k, 64 k + 64), its
+ * window is [a, e) with a = max(0, 64 k - 16) and e = 64 k + 80 (at a flush min(64 k + 80, N), N = symbols seen).  All four
+ * path metrics M[2 p + q], of (b[n-1], b[n]) = (p, q), are 0 entering step a.  Step n, for every (q, r):
+ *     cand_p = M[2 p + q] + g(n; p, q, r),   the survivor is p = 1 exactly when cand_1 > cand_0,   M'[2 q + r] = its candidate
+ * (compare and select, float, nothing renormalised).  Behind step e - 1 the best state is the lowest index whose metric
+ * is the greatest; back from it, the state (q, r) of step n gives b[n] = q and its survivor the state of step n - 1,
+ * down to b[64 k - 1] (b[-1] = 0).  bit[n] = 1 ^ b[n] ^ b[n-1] for the block's n: no block needs another's decision.
+ * Block k is emitted as soon as 64 k + 80 <= N; the undecided symbols are carried (at most 96).  The concatenated output
+ * is therefore the same for every split of a stream into calls.  A call of n symbols emits at most n + 79 bits. */
+typedef struct aisx_mlse aisx_mlse;
+int aisx_mlse_create(aisx_mlse** h, double bt); /* 0.1 <= bt <= 1 */
+int aisx_mlse_destroy(aisx_mlse* h);
+int aisx_mlse_reset(aisx_mlse* h);
+/* c0, c1 and rot[16] = {cos, sin} of the triples in the order 4 p + 2 q + r; any pointer may be NULL */
+int aisx_mlse_model(const aisx_mlse* h, double* c0, double* c1, float* rot);
+/* n >= 0 symbols in, *nbits bits (one per byte) out; AISX_ERR_OVERFLOW with *nbits = what is needed when cap is
+ * smaller: nothing was taken then */
+int aisx_mlse_work(aisx_mlse* h, const aisx_cf32* syms, int n, uint8_t* bits, int cap, int* nbits);
+/* the bits of the symbols still undecided (at most 79), their windows cut at the last symbol; leaves the handle as
+ * after reset */
+int aisx_mlse_flush(aisx_mlse* h, uint8_t* bits, int cap, int* nbits);
+
+/* The same for nchan channels of at most max_syms (<= 2^27) symbols per call on the device: per channel exactly what
+ * one aisx_mlse handle returns when fed that channel's symbols call by call.  The handle belongs to the device that was
+ * current here. */
+typedef struct aisx_mlse_batch aisx_mlse_batch;
+int aisx_mlse_batch_create(aisx_mlse_batch** h, double bt, int nchan, int max_syms);
+int aisx_mlse_batch_destroy(aisx_mlse_batch* h);
+int aisx_mlse_batch_reset(aisx_mlse_batch* h); /* back to the state after create; waits for the last call's work */
+/* d_syms [nchan][syms_stride] (syms_stride >= max_syms, 8-byte aligned), d_nsyms [nchan] on the DEVICE (the chain's
+ * d_produced); d_bits [nchan][bits_stride] with bits_stride >= max_syms + 79 and d_nbits [nchan] receive what
+ * aisx_hdlc_batch_process consumes.  Queued on `stream`, no host synchronisation; calls of one handle must be ordered.
+ * A channel whose count is outside [0, max_syms] is treated as one with no new symbols, and the status says so. */
+int aisx_mlse_batch_process(aisx_mlse_batch* h, const aisx_cf32* d_syms, long syms_stride, const int* d_nsyms,
+                            uint8_t* d_bits, long bits_stride, int* d_nbits, void* stream);
+/* aisx_mlse_flush for every channel (bits_stride >= 79), queued on `stream` */
+int aisx_mlse_batch_flush(aisx_mlse_batch* h, uint8_t* d_bits, long bits_stride, int* d_nbits, void* stream);
+enum { AISX_MLSE_ST_BAD_COUNT = 1 };
+/* *status = 0 or AISX_MLSE_ST_BAD_COUNT when a call since the previous read met a bad count (then cleared);
+ * synchronises `stream`.  _status_device: the word itself, for a consumer on the device. */
+int aisx_mlse_batch_status(aisx_mlse_batch* h, int* status, void* stream);
+int aisx_mlse_batch_status_device(const aisx_mlse_batch* h, const int** d_status);
 
 #ifdef __cplusplus
 }
