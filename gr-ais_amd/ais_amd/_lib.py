@@ -135,6 +135,9 @@ def lib(device=True):
     sig("aisx_msk_get_max_noutput_items", i32, [vp])
     sig("aisx_msk_set_tail_stream", i32, [vp, vp, i32])
     sig("aisx_msk_wait_tail", i32, [vp, vp])
+    sig("aisx_msk_set_fused_tail", i32, [vp, i32])
+    sig("aisx_msk_get_fused_tail", i32, [vp])
+    sig("aisx_msk_last_tail_fused", i32, [vp])
     sig("aisx_msk_wait_prepass", i32, [vp, vp])
     sig("aisx_msk_set_head_start", i32, [vp, i32])
     sig("aisx_msk_geometry", i32, [vp, pi32, pi32])

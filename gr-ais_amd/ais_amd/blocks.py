@@ -272,6 +272,18 @@ class msk_timing_recovery_cc:
     def wait_tail(self, stream=None):
         check(_lib.lib().aisx_msk_wait_tail(self._h, _stream_ptr(stream)), "wait_tail")
 
+    def set_fused_tail(self, on):
+        """The bit tail inside the recovery kernel's symbol flush (aisx_msk_set_fused_tail; default on).  Off: always
+        the separate bit-tail kernel.  Results are identical; the two kinds of call may alternate."""
+        check(_lib.lib().aisx_msk_set_fused_tail(self._h, 1 if on else 0), "set_fused_tail")
+
+    def get_fused_tail(self):
+        return bool(_lib.lib().aisx_msk_get_fused_tail(self._h))
+
+    def last_tail_fused(self):
+        """Whether the last work() call that took bits computed them inside the recovery kernel."""
+        return _lib.lib().aisx_msk_last_tail_fused(self._h) == 1
+
     def wait_prepass(self, stream=None):
         """`stream` waits until the last work() call's recovery kernel stands at the head of its queue
         (aisx_msk_wait_prepass): call it on the stream whose next kernels would otherwise take the

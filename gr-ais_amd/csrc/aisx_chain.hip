@@ -15,6 +15,7 @@ struct aisx_chain {
     aisx_agc* agc = nullptr;     // borrowed
     int agc_claim_prev = -1;     // the handle's LDS claim before this chain set its own (-1: the chain set none)
     int walk_claim_prev = -1;    // ... and the phase walk's (aisx_freqsync_set_walk_lds_claim)
+    int fused_tail_prev = -1;    // the recovery handle's fused-tail switch before this chain cleared it (-1: left alone)
     aisx_corr* corr = nullptr;   // borrowed
     aisx_msk* msk = nullptr;     // borrowed
     int nchan = 0, max_items = 0, fftlen = 0;
@@ -34,7 +35,7 @@ struct aisx_chain {
     Event ev_in;
     Event ev_ready[NBUF];    // s_main: the step's sample passes and tags are done (its input is free)
     Event ev_msk_done[NBUF]; // s_msk: the step's recovery has read d_yc[par] and its tags
-    Event ev_done[NBUF];     // the step's outputs are complete (bit tail included)
+    Event ev_done[NBUF];     // the step's outputs are complete (bit tail included): on s_tail, or on s_msk when the tail was fused
     long long nsteps = 0;
     int m_of[NBUF] = {}; // items the correlator wrote per row in the step that owns d_yc[k]
     int npend = 0; // items the front end holds back (n % fftlen arithmetic of stream_to_vector)
@@ -51,6 +52,8 @@ extern "C" int aisx_chain_destroy(aisx_chain* h)
         return AISX_OK;
     if (h->msk)
         (void)aisx_msk_set_tail_stream(h->msk, nullptr, 0);
+    if (h->msk && h->fused_tail_prev >= 0)
+        (void)aisx_msk_set_fused_tail(h->msk, h->fused_tail_prev);
     if (h->agc && h->agc_claim_prev >= 0) // (the placement claims are the chain's)
         (void)aisx_agc_set_lds_claim(h->agc, h->agc_claim_prev);
     if (h->fs && h->walk_claim_prev >= 0)
@@ -256,6 +259,16 @@ extern "C" int aisx_chain_create(aisx_chain** out, aisx_freqsync* fs, aisx_agc* 
         if ((rc = aisx_msk_set_tail_stream(msk, h->s_tail, 1)) != AISX_OK || (rc = aisx_msk_set_head_start(msk, us < 0 ? 0 : us)) != AISX_OK ||
             (rc = aisx_msk_wait_prepass(msk, h->s_main)) != AISX_OK)
             return rc;
+        // Where the bit tail runs.  Inside the recovery kernel it costs the recurrence about 2 % (two symbols sliced per lane
+        // and flush); as a kernel of its own it is launched the moment the next recovery and the next step's passes start.
+        // With a front end that kernel stands in their way (the phase walk and the estimates queue up behind it: the step
+        // is 6 % shorter without it, 4096 and 8192 channels).  Without one (core chain) the step IS the recovery kernel and
+        // the bit tail hides beside the next one: fused, the step is 2.5 % longer.  So the core chain keeps the kernel.
+        if (!fs) {
+            h->fused_tail_prev = aisx_msk_get_fused_tail(msk);
+            if ((rc = aisx_msk_set_fused_tail(msk, 0)) != AISX_OK)
+                return rc;
+        }
     }
     *out = h.release();
     return AISX_OK;
@@ -383,8 +396,10 @@ static int chain_step_issue(aisx_chain* h, const aisx_cf32* d_in, long in_stride
                                                 h->serial ? nullptr : (void*)h->ev_ready[par])) != AISX_OK)
             return rc;
         AISX_HIPCHK(hipEventRecord(h->ev_msk_done[par], sk));
-        // the bit tail (if any) was queued on s_tail behind the recovery
-        AISX_HIPCHK(hipEventRecord(h->ev_done[par], (d_bits && !h->serial) ? h->s_tail : sk));
+        // the bit tail (if any) was queued on s_tail behind the recovery -- unless the recovery kernel did it itself
+        // (aisx_msk_set_fused_tail): then the step's outputs are complete on the recovery's stream
+        const bool on_tail = d_bits && !h->serial && aisx_msk_last_tail_fused(h->msk) != 1;
+        AISX_HIPCHK(hipEventRecord(h->ev_done[par], on_tail ? h->s_tail : sk));
         // the next step's sample passes start behind this step's tag prepass, i.e. when the recovery
         // kernel stands at the head of its queue (aisx_msk_wait_prepass; include/aisx.h)
         if (!h->serial && (rc = aisx_msk_wait_prepass(h->msk, sm)) != AISX_OK)

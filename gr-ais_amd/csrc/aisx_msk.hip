@@ -412,12 +412,32 @@ static int msk_launch_serial(aisx_msk* h, const MskCall& c, float* d_err, float*
     p.err = d_err;
     p.mu_out = d_mu;
     p.sym_al16 = ((uintptr_t)c.syms % 16 == 0) && (c.out_stride % 2 == 0);
+    if (c.fused_bits) { // the bit tail inside the symbol flush: msk_launch_bittail's ports
+        p.bits = c.fused_bits;
+        p.bit_stride = c.out_stride;
+        p.bit_al2 = ((uintptr_t)c.fused_bits % 2 == 0) && (c.out_stride % 2 == 0);
+        p.prev_sym_in = h->d_tprev[h->tcur];
+        p.prev_bit_in = h->d_tbit[h->tcur];
+        p.prev_sym_out = h->d_tprev[h->tcur ^ 1];
+        p.prev_bit_out = h->d_tbit[h->tcur ^ 1];
+        p.atan_tab = h->d_atan;
+    }
     int rc;
     if ((rc = h->prof.begin(c.st)) != AISX_OK ||
         (rc = msk_launch(p, (h->nchan + msk_wg_channels(h->lpw) - 1) / msk_wg_channels(h->lpw), c.st)) != AISX_OK ||
         (rc = h->prof.end(c.st)) != AISX_OK)
         return rc;
+    if (c.fused_bits)
+        h->tcur ^= 1; // (as msk_launch_bittail does: fused and unfused calls may alternate)
     return AISX_OK;
+}
+
+// The kernel can do the call's bit tail itself: the serial kernel in a build with a symbol stage (k_msk.h, STG: osps 1,
+// err / mu ports open, at most 8 channels per wave).  The time-parallel recovery keeps k_bittail (its units' symbols are
+// gathered from staging rows).
+static bool msk_fused_applies(const aisx_msk* h, bool tp, const float* d_err, const float* d_mu, const uint8_t* d_bits)
+{
+    return h->fused_tail && d_bits && !tp && h->osps == 1 && !d_err && !d_mu && msk_staged(h->lpw);
 }
 
 static int msk_process_stream(aisx_msk* h, const aisx_cf32* d_in, long in_stride, int n, const aisx_tag* d_tags,
@@ -450,9 +470,21 @@ static int msk_process_stream(aisx_msk* h, const aisx_cf32* d_in, long in_stride
         AISX_HIPCHK(hipEventRecord(h->ev_prep, su));
         h->ev_prep_set = true;
     }
-    if (h->tail_on && h->ev_tail_set[par]) // the bit tail of two calls ago may still read this parity's buffers
+    const bool fused = msk_fused_applies(h, tp, d_err, d_mu, d_bits);
+    if (fused) {
+        // Nothing of this call goes to the tail stream.  Bit tails still queued there (unfused calls before this one) hold
+        // the tail state this kernel reads and writes, and the internal `produced` array of this parity: waited for once.
+        for (int k = 0; k < 2; k++)
+            if (h->tail_on && h->tail_pend[k]) {
+                AISX_HIPCHK(hipStreamWaitEvent(st, h->ev_tail[k], 0));
+                h->tail_pend[k] = false;
+            }
+        c.fused_bits = d_bits;
+    } else if (h->tail_on && h->ev_tail_set[par]) { // the bit tail of two calls ago may still read this parity's buffers
         AISX_HIPCHK(hipStreamWaitEvent(st, h->ev_tail[par], 0));
-    if (!c.syms) { // the kernel always writes symbols (the bit tail reads them back): give them a home
+        h->tail_pend[par] = false;
+    }
+    if (!c.syms && !fused) { // the kernel always writes symbols (the bit tail reads them back): give them a home
         const size_t need = (size_t)h->nchan * (size_t)out_stride;
         if (need > h->d_symscratch[par].cap()) {
             AISX_HIPCHK(hipStreamSynchronize(st));
@@ -474,6 +506,10 @@ static int msk_process_stream(aisx_msk* h, const aisx_cf32* d_in, long in_stride
         return rc;
     if (!d_bits)
         return AISX_OK;
+    h->last_fused = fused;
+    h->last_st = st;
+    if (fused) // (the kernel wrote them; complete on `stream`, whether a tail stream is set or not)
+        return AISX_OK;
     // a call produces at most forecast^-1(n + carry) symbols; out_cap bounds it too
     const double wmin = (double)h->d_sps - fabs((double)h->limit);
     const int max_out = std::min<long>(c.out_cap, (long)ceil((n + aisx_msk::carry_cap) / (2.0 * wmin)) * h->osps + 16);
@@ -490,6 +526,7 @@ static int msk_process_stream(aisx_msk* h, const aisx_cf32* d_in, long in_stride
     if (h->tail_on) {
         AISX_HIPCHK(hipEventRecord(h->ev_tail[par], h->tail_stream));
         h->ev_tail_set[par] = true;
+        h->tail_pend[par] = true;
     }
     return AISX_OK;
 }
@@ -533,12 +570,28 @@ extern "C" int aisx_msk_wait_tail(aisx_msk* h, void* stream)
 {
     if (!h)
         return AISX_ERR_INVALID;
-    if (h->tail_on)
+    if (h->tail_on) {
         for (int k = 0; k < 2; k++)
             if (h->ev_tail_set[k])
                 AISX_HIPCHK(hipStreamWaitEvent((hipStream_t)stream, h->ev_tail[k], 0));
+        // a fused call's bits are complete on the call's own stream: an event there now stands behind them
+        if (h->last_fused && h->last_st != (hipStream_t)stream) {
+            AISX_HIPCHK(hipEventRecord(h->ev_msk, h->last_st));
+            AISX_HIPCHK(hipStreamWaitEvent((hipStream_t)stream, h->ev_msk, 0));
+        }
+    }
     return AISX_OK;
 }
+
+extern "C" int aisx_msk_set_fused_tail(aisx_msk* h, int on)
+{
+    if (!h)
+        return AISX_ERR_INVALID;
+    h->fused_tail = on != 0;
+    return AISX_OK;
+}
+extern "C" int aisx_msk_get_fused_tail(const aisx_msk* h) { return h ? (h->fused_tail ? 1 : 0) : AISX_ERR_INVALID; }
+extern "C" int aisx_msk_last_tail_fused(const aisx_msk* h) { return h ? (h->last_fused ? 1 : 0) : AISX_ERR_INVALID; }
 
 extern "C" int aisx_msk_wait_prepass(aisx_msk* h, void* stream)
 {

@@ -42,6 +42,13 @@ struct aisx_msk {
     aisx::Event ev_prep; // behind the tag prepass of the last aisx_msk_process_stream (aisx_msk_wait_prepass)
     bool ev_prep_set = false;
     bool ev_tail_set[2] = { false, false };
+    // The bit tail inside the recovery kernel's symbol flush (aisx_msk_set_fused_tail; k_msk.h, MskParams::bits) where the
+    // call allows it: no second kernel, no symbol scratch, nothing on the tail stream.  last_fused / last_st: whether the
+    // last call with d_bits took that path, and its stream (where its bits are complete); tail_pend[par]: a bit tail is
+    // queued on the tail stream that no later call on the recovery's stream has waited for yet.
+    bool fused_tail = true, last_fused = false;
+    hipStream_t last_st = nullptr;
+    bool tail_pend[2] = { false, false };
     aisx::DevBuf<int> d_produced2; // second internal `produced` array (alternates with d_produced)
     aisx::DevBuf<unsigned long long> d_nread;
     aisx::DevBuf<aisx::cf> d_carry[2];
@@ -77,6 +84,7 @@ struct MskCall {
     cf* syms; int* produced; long out_stride; int out_cap;   // (syms: the caller's rows or the handle's scratch)
     int par; hipStream_t st;                                 // the call's parity and stream
     void* ready_event;
+    unsigned char* fused_bits = nullptr; // the serial kernel writes the bits itself (fused bit tail): their rows, else null
 };
 
 // the loop's state and constants, and the call's arguments, under the names MskParams (k_msk.h) and MskpParams (k_mskp.h) share

@@ -1,6 +1,7 @@
 // k_msk.h -- msk_timing_recovery_cc (reference: lib/msk_timing_recovery_cc_impl.cc
 // :107-206), and the NRZI bit tail of python/ais_demod.py:48-52 + lib/invert_impl.cc
-// :62-64 as a second, fully parallel kernel over the symbols the first one wrote.
+// :62-64: inside the first kernel's symbol flush where the build has one (MskParams::bits), else as
+// a second, fully parallel kernel over the symbols the first one wrote.
 //
 // The loop is a strict recurrence through (mu, omega, iidx): the only parallelism
 // is across channels.  A workgroup is msk_waves(LPW) waves of LPW channels each (LPW = 8
@@ -29,8 +30,8 @@
 //  * the time_est tags come compacted (tagprep_body) and are queued in LDS, so a firing
 //    tag costs an LDS read;
 //  * the bit tail (quadrature demod, slicer, differential decoder, invert) has no
-//    feedback into the loop and runs afterwards over all symbols in parallel
-//    (bittail_body).
+//    feedback into the loop: it is computed where the symbols leave the LDS stage (tail_out), outside
+//    the pair loops, or afterwards over all symbols in parallel (bittail_body).
 // All arithmetic is the reference's float/double sequence, unfused: bit-identical
 // to the CPU restatement.
 #pragma once
@@ -180,6 +181,13 @@ struct MskParams {
     const int* nrst; const mskp_rst* rst; const mskp_res* res;
     mskp_piece* pieces; int* npieces;
     const int* ct_nc;  // carried tags in front of the new ones in `ct` (-1: a new tag was dropped, no fast-forward)
+    // ---- the NRZI bit tail folded into the symbol flush (bits != nullptr; builds with a symbol stage only, not the join):
+    // the ports of BitTailParams.  `syms` may then be null: the symbols stay in the stage and never reach memory.
+    unsigned char* bits = nullptr; long bit_stride = 0;
+    int bit_al2 = 0;   // every bit row starts 2-byte aligned (bits pointer and bit_stride both even)
+    const cf* prev_sym_in = nullptr; const unsigned char* prev_bit_in = nullptr; // state before this call
+    cf* prev_sym_out = nullptr; unsigned char* prev_bit_out = nullptr;           // state after it (a different buffer)
+    const float* atan_tab = nullptr; // read from global memory, and only by the fallback of the slicer (see bittail_body)
 };
 
 // quadrature_demod_cf(pi/2) -> binary_slicer_fb -> diff_decoder_bb(2) -> invert over the
@@ -360,7 +368,7 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
     }
 
     // output rows are addressed as (wave-uniform base) + (32-bit byte offset of this lane)
-    char* const osym0 = (char*)(p.syms + (long)cbase * p.out_stride);
+    char* const osym0 = p.syms ? (char*)(p.syms + (long)cbase * p.out_stride) : nullptr; // (null: fused bit tail, bits only)
     char* const oerr0 = AUX && p.err ? (char*)(p.err + (long)cbase * p.out_stride) : nullptr;
     char* const omu0 = AUX && p.mu_out ? (char*)(p.mu_out + (long)cbase * p.out_stride) : nullptr;
     unsigned ob = (unsigned)((long)(cc - cbase) * p.out_stride) * 8u; // byte offset of the next symbol
@@ -391,12 +399,120 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
         const cf8s t = *(const cf8s*)(lds0 + ((((k & (unsigned)(MSK_STAGE - 1)) << SLOT_SH)) | stg_real));
         return mk(t.re, t.im);
     };
+    // ---- the NRZI bit tail, folded into the flush (MskParams::bits): the lanes that store two symbols of a flush have them
+    // in registers and slice them there -- bittail_body's arithmetic, one kernel and one pass over the symbols less.
+    // The slice bit of the symbol before a lane's first is the second bit of the channel's previous lane (through a
+    // ballot); in front of the flush's first symbol stand the last symbol flushed and its slice bit, carried in registers
+    // by every lane of the channel (the stage slots behind nf may have been staged again), at first the state the previous
+    // call left.
+    constexpr bool FUSE = STG && !FFT;
+    const bool fuse = FUSE && p.bits != nullptr; // (wave-uniform)
+    unsigned char* const obit0 = fuse ? p.bits + (long)cbase * p.bit_stride : nullptr;
+    const unsigned bbrow = (unsigned)((long)(cc - cbase) * p.bit_stride); // byte offset of the channel's bit row
+    cf t_sym = mk(0.f, 0.f);
+    unsigned t_bit = 0;
+    if (fuse) {
+        t_sym = p.prev_sym_in[cc];
+        t_bit = p.prev_bit_in[cc];
+    }
+    // bittail_body's slicer in two halves: the product and the test for the plain case, and the table fallback (operands
+    // not finite or vanishing: never, on symbols), which both symbols of a lane share one ballot for
+    struct slice_in { float y, x; bool tab; };
+    auto slice_pre = [&](const cf& cur, const cf& prev, bool valid) -> slice_in {
+        const cf prod = cmul_exact(cur, cconj(prev));
+        const float y = prod.im, x = prod.re;
+        const float ya = fabsf(y), xa = fabsf(x);
+        const bool plain = (ya < 1.0e30f) && (xa < 1.0e18f) && (y >= 0.0f || ya > 1.0e-18f); // (false for NaN / inf)
+        slice_in r;
+        r.y = y;
+        r.x = x;
+        r.tab = valid && !plain;
+        return r;
+    };
+    auto slice_tab = [&](const slice_in& s) -> unsigned {
+        const float fm = 1.57079632679489661923f * fast_atan2f_tab(s.y, s.x, p.atan_tab);
+        return fm >= 0 ? 1u : 0u;
+    };
+    // Symbols [nf, nf + cnt) of this lane's channel leave the stage (called by the whole wave; cnt 0: none of this channel):
+    // lane q of the channel takes symbols nf + 2q and nf + 2q + 1, writes them if there are symbol rows, and their bits.
+    // FULL: a flush, cnt is FL or 0; else the drain at the end of the call, cnt < FL.
+    struct tail_full { enum { value = 1 }; };
+    struct tail_part { enum { value = 0 }; };
+    auto tail_out = [&](auto kind, unsigned cnt) {
+        constexpr bool FULL = decltype(kind)::value != 0;
+        const unsigned qa = (unsigned)q & (FLQ - 1u); // (lanes beyond FLQ -- 4 channels per wave -- read along, store nothing)
+        const unsigned k0 = nf + 2u * qa;             // (even: nf is a multiple of FL)
+        const bool v0 = FULL ? (cnt != 0u && (unsigned)q < FLQ) : ((unsigned)q < FLQ && 2u * qa < cnt);
+        const bool v1 = FULL ? v0 : ((unsigned)q < FLQ && 2u * qa + 1u < cnt);
+        // slots k0 and k0 + 1 lie in one round of the stage, and so does k0 - 1 where it is used (qa >= 1)
+        const char* const sa = lds0 + (((k0 & (unsigned)(MSK_STAGE - 1)) << SLOT_SH) | stg_real);
+        const cf8s ra = *(const cf8s*)sa, rb = *(const cf8s*)(sa + SLOT_B);
+        const cf8s rp = *(const cf8s*)(sa - (qa != 0u ? SLOT_B : 0));
+        const cf a = mk(ra.re, ra.im), b = mk(rb.re, rb.im);
+        const cf last = stage_get(nf + (FULL ? FL : cnt) - 1u);
+        if (p.syms) {
+            cf* dst = (cf*)(osym0 + obrow) + k0;
+            if (v1 && p.sym_al16) {
+                st16(dst, a, b);
+            } else {
+                if (v0)
+                    st8(dst, a);
+                if (v1)
+                    st8(dst + 1, b);
+            }
+        }
+        const slice_in s0 = slice_pre(a, qa == 0u ? t_sym : mk(rp.re, rp.im), v0), s1 = slice_pre(b, a, v1);
+        unsigned b0 = s0.y >= 0.0f ? 1u : 0u, b1 = s1.y >= 0.0f ? 1u : 0u;
+        if (cx.ballot(s0.tab || s1.tab) != 0ull) {
+            if (s0.tab)
+                b0 = slice_tab(s0);
+            if (s1.tab)
+                b1 = slice_tab(s1);
+        }
+        // the slice bit of the symbol before this lane's first: the second bit of the channel's previous lane, or the carry
+        const u64 m1 = cx.ballot(b1 != 0u);
+        const unsigned ln = (unsigned)(cx.tid() & 63);
+        const unsigned bp = qa == 0u ? t_bit : (unsigned)(m1 >> ((ln - (unsigned)LPW) & 63u)) & 1u;
+        const unsigned char o0 = (unsigned char)(((((unsigned)(b0 - bp)) % 2u) ^ 0x01u) & 0x01u);
+        const unsigned char o1 = (unsigned char)(((((unsigned)(b1 - b0)) % 2u) ^ 0x01u) & 0x01u);
+        unsigned char* d = obit0 + bbrow + k0;
+        if (v1 && p.bit_al2) {
+            *(unsigned short*)d = (unsigned short)((unsigned)o0 | ((unsigned)o1 << 8));
+        } else {
+            if (v0)
+                d[0] = o0;
+            if (v1)
+                d[1] = o1;
+        }
+        // the carry: the last symbol that left and its slice bit
+        if constexpr (FULL) {
+            if (cnt != 0u) {
+                t_sym = last;
+                t_bit = (unsigned)(m1 >> ((FLQ - 1u) * (unsigned)LPW + (unsigned)l)) & 1u;
+            }
+        } else {
+            const u64 m0 = cx.ballot(b0 != 0u);
+            if (cnt != 0u) { // symbol nf + cnt - 1 is bit (cnt - 1) & 1 of lane (cnt - 1) / 2
+                const unsigned j = cnt - 1u;
+                t_sym = last;
+                t_bit = (unsigned)(((j & 1u) ? m1 : m0) >> ((j >> 1) * (unsigned)LPW + (unsigned)l)) & 1u;
+            }
+        }
+    };
     auto flush_syms = [&]() {
         if constexpr (STG) {
             if (cx.ballot((so >> SLOT_SH) - nf >= FL) == 0ull)
                 return;
             cx.wave_sync(); // (lane model: the symbols the channel's other lanes staged are in place)
             while (cx.ballot((so >> SLOT_SH) - nf >= FL) != 0ull) {
+                if constexpr (FUSE) {
+                    if (fuse) {
+                        const bool go = (so >> SLOT_SH) - nf >= FL;
+                        tail_out(tail_full(), go ? FL : 0u);
+                        nf += go ? FL : 0u;
+                        continue;
+                    }
+                }
                 if ((so >> SLOT_SH) - nf >= FL) {
                     const unsigned k0 = nf + 2u * (unsigned)q;
                     if ((NQ <= 8 || (unsigned)q < FLQ) && !fin_saved) {
@@ -1313,11 +1429,15 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
     if constexpr (STG) { // what is left in the stage: fewer than FL symbols per channel, 8-byte stores
         flush_syms();
         const unsigned left = fin_saved ? 0u : (so >> SLOT_SH) - nf;
+        if (fuse) {
+            tail_out(tail_part(), left);
+        } else {
 #pragma unroll
-        for (unsigned j = 0; j < 2; j++) {
-            const unsigned k = (unsigned)q + j * FLQ;
-            if ((unsigned)q < FLQ && k < left)
-                st8((cf*)(osym0 + obrow) + nf + k, stage_get(nf + k));
+            for (unsigned j = 0; j < 2; j++) {
+                const unsigned k = (unsigned)q + j * FLQ;
+                if ((unsigned)q < FLQ && k < left)
+                    st8((cf*)(osym0 + obrow) + nf + k, stage_get(nf + k));
+            }
         }
     }
     if (!live || !owner)
@@ -1343,6 +1463,10 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
     p.nread[c] = Rn;
     p.produced[c] = ototal;
     p.consumed[c] = base;
+    if (fuse) { // the bit tail's state for the next call (as it came in when nothing was produced)
+        p.prev_sym_out[c] = t_sym;
+        p.prev_bit_out[c] = (unsigned char)t_bit;
+    }
 
     cf* cout = p.carry_out + (long)c * p.carry_cap;
     if (p.stream_mode) {

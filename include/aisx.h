@@ -258,6 +258,19 @@ int aisx_msk_kernel_ms_history(aisx_msk* h, float* ms, int cap, int* n);
  * d_produced buffers from call to call.  Default: off, everything on the call's stream. */
 int aisx_msk_set_tail_stream(aisx_msk* h, void* tail_stream, int enable);
 int aisx_msk_wait_tail(aisx_msk* h, void* stream);
+/* The bit tail inside the recovery kernel (default: on).  Where a call allows it -- d_bits given, osps 1, d_err and d_mu
+ * NULL, the serial kernel (not the time-parallel recovery) -- the lanes that flush a channel's symbols to memory slice
+ * them there and write the bits: no second kernel, no pass over the symbols, and with d_syms NULL the symbols never
+ * reach memory at all.  Results are identical, bit for bit, state included: fused and unfused calls may alternate on
+ * one handle.  d_bits of a fused call is complete on the call's own `stream`, also when a tail stream is set (nothing
+ * of the call runs there); aisx_msk_wait_tail covers both cases.  aisx_msk_last_tail_fused: 1 if the last call that
+ * took d_bits was fused, 0 if its bit tail was a kernel of its own.  on = 0: always the separate kernel (twin tests,
+ * A/B runs).  The fused flush costs the recovery kernel about 2 %: it pays wherever the bit-tail kernel would delay
+ * something.  aisx_chain_create clears the switch for a chain without front end (there the step is the recovery
+ * kernel and the bit tail hides beside the next one) and gives it back at aisx_chain_destroy. */
+int aisx_msk_set_fused_tail(aisx_msk* h, int on);
+int aisx_msk_get_fused_tail(const aisx_msk* h);
+int aisx_msk_last_tail_fused(const aisx_msk* h);
 /* Makes `stream` wait until the tag prepass of the last aisx_msk_process_stream call has run, i.e.
  * until that call's recovery kernel stands at the head of its queue.  The recovery kernel is 128
  * workgroups of 90 KB of LDS each: when it becomes ready at the same moment as a kernel with
