@@ -21,7 +21,8 @@ HW_QUEUES_SET_TOO_LATE = "GPU_MAX_HW_QUEUES" not in _os.environ and _t is not No
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 del _t
 
-from .framing import AIS_REPAIR_RULES, MSG_COLUMNS, MSG_DTYPE, MSG_NA, hdlc_deframer_bp, mlse_detector, msg_decode, pdu_to_nmea  # noqa: F401
+from .framing import AIS_REPAIR_EVENTS, AIS_REPAIR_RULES, REPAIR_PAIR, REPAIR_SINGLE, REPAIR_SKIP, repair_mark  # noqa: F401
+from .framing import MSG_COLUMNS, MSG_DTYPE, MSG_NA, hdlc_deframer_bp, mlse_detector, msg_decode, pdu_to_nmea  # noqa: F401
 from .modulate import gmsk_mod, modulate_vector_bc  # noqa: F401
 from .transmit import BURST_DTYPE, gmsk_burst, gmsk_scene, hdlc_framer  # noqa: F401
 

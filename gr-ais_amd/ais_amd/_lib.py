@@ -25,6 +25,7 @@ AISX_FMT_CF32, AISX_FMT_CS16, AISX_FMT_CS8, AISX_FMT_CU8 = 0, 1, 2, 3
 AISX_RX_ST_HDLC_OVERFLOW, AISX_RX_ST_NMEA_OVERFLOW, AISX_RX_ST_BAD_COUNT = 0x100, 0x200, 0x400
 AISX_MSG_NA, AISX_MSG_STR = -(1 << 31), 48
 AISX_HDLC_MAX_RULES = 16
+AISX_HDLC_EV_SINGLE, AISX_HDLC_EV_PAIR, AISX_HDLC_EV_SKIP = 1, 2, 4  # error events of the deframers' repair
 AISX_MLSE_ST_BAD_COUNT = 1
 MLSE_BLOCK, MLSE_OVERLAP = 64, 16  # symbols a block of the sequence detector decides, and its window's overlap
 AISX_MSG_FL_COMPLETE, AISX_MSG_FL_NO_LAYOUT, AISX_MSG_FL_BAD_RECORD = 1, 2, 4
@@ -208,6 +209,8 @@ def lib(device=True):
     sig("aisx_hdlc_work", i32, [vp, vp, i32, vp, i32, vp, i32, pi32])
     sig("aisx_hdlc_set_repair", i32, [vp, vp, i32])
     sig("aisx_hdlc_work_repair", i32, [vp, vp, i32, vp, i32, vp, vp, i32, pi32])
+    sig("aisx_hdlc_set_repair_events", i32, [vp, vp, i32, i32])
+    sig("aisx_hdlc_event_table", i32, [i32, vp])
     sig("aisx_pdu_to_nmea", i32, [C.c_char_p, vp, i32, C.c_char_p, i32])
     sig("aisx_hdlc_batch_create", i32, [pvp, i32, i32, i32, i32, i32])
     sig("aisx_hdlc_batch_destroy", i32, [vp])
@@ -219,6 +222,8 @@ def lib(device=True):
     sig("aisx_hdlc_batch_repairs_device", i32, [vp, pvp])
     sig("aisx_hdlc_batch_read_repairs", i32, [vp, vp, i32, pi32, vp])
     sig("aisx_rx_enable_repair", i32, [vp, vp, i32])
+    sig("aisx_hdlc_batch_set_repair_events", i32, [vp, vp, i32, i32])
+    sig("aisx_rx_enable_repair_events", i32, [vp, vp, i32, i32])
     sig("aisx_rx_popped_repairs", i32, [vp, vp, i32, pi32])
     sig("aisx_nmea_batch_create", i32, [pvp, C.POINTER(C.c_char_p), i32, i32, i32, lng])
     sig("aisx_nmea_batch_destroy", i32, [vp])

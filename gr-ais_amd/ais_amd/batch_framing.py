@@ -39,7 +39,7 @@ class hdlc_deframer_batch:
     writes its zero counts on another of the chain's streams; aisx_chain_wait orders every path.  A step's
     outputs rotate through AISX_CHAIN_DEPTH sets, so work() must be queued before the call that reuses them."""
 
-    def __init__(self, length_min, length_max, nchan, max_bits, max_pdus, repair=None):
+    def __init__(self, length_min, length_max, nchan, max_bits, max_pdus, repair=None, events=1):
         h = C.c_void_p()
         check(_lib.lib().aisx_hdlc_batch_create(C.byref(h), int(length_min), int(length_max), int(nchan), int(max_bits),
                                                 int(max_pdus)), "hdlc_deframer_batch")
@@ -51,7 +51,7 @@ class hdlc_deframer_batch:
         self._data = np.zeros(self.max_pdus * (self.length_max - 1) + 1, dtype=np.uint8)
         self._fix = None  # read-back buffer of the repair marks, made on first use
         if repair is not None:
-            self.set_repair(repair)
+            self.set_repair(repair, events)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -59,18 +59,23 @@ class hdlc_deframer_batch:
             _lib.lib().aisx_hdlc_batch_destroy(h)
             self._h = None
 
-    def set_repair(self, rules):
-        """Single-bit repair by CRC syndrome for every channel (hdlc_deframer_bp.set_repair's rules, its results):
-        waits for the handle's queued work, applies from the next work() on.  None or empty: off."""
-        from .framing import repair_rules
+    def set_repair(self, rules, events=1):
+        """Repair by CRC syndrome for every channel (hdlc_deframer_bp.set_repair's rules and events -- by default the
+        single wrong bit --, its results): waits for the handle's queued work, applies from the next work() on.  None or
+        empty: off."""
+        from .framing import REPAIR_SINGLE, repair_rules
 
         r = repair_rules(rules)
-        check(_lib.lib().aisx_hdlc_batch_set_repair(self._h, r.ctypes.data_as(C.c_void_p) if r.size else None, r.size),
-              "hdlc_deframer_batch.set_repair")
+        if events == REPAIR_SINGLE:
+            rc = _lib.lib().aisx_hdlc_batch_set_repair(self._h, r.ctypes.data_as(C.c_void_p) if r.size else None, r.size)
+        else:
+            rc = _lib.lib().aisx_hdlc_batch_set_repair_events(self._h, r.ctypes.data_as(C.c_void_p) if r.size else None, r.size,
+                                                             int(events))
+        check(rc, "hdlc_deframer_batch.set_repair")
 
     def repairs_device(self):
         """device address of the last call's repair marks (int32 [max_pdus], entry k for record k of results_device():
-        -1 = delivered as received, else the flipped bit's index in the frame)"""
+        -1 = delivered as received, else the first flipped bit's index in the frame | event id << 16)"""
         p = C.c_void_p()
         check(_lib.lib().aisx_hdlc_batch_repairs_device(self._h, C.byref(p)), "hdlc_deframer_batch.repairs_device")
         return p.value
@@ -102,7 +107,8 @@ class hdlc_deframer_batch:
         more than max_pdus were found, OverflowError -- or with overflow_ok=True the first max_pdus (self.found
         tells how many there were).  ValueError when a call since the last read met a count outside
         [0, max_bits] (that channel was not advanced).  with_repairs=True: a third item, the records' repair marks
-        (int32 array: -1 = delivered as received, else the flipped bit's index) -- in the list form a fourth field."""
+        (int32 array: -1 = delivered as received, else the first flipped bit's index | event id << 16, which
+        ais_amd.repair_mark reads) -- in the list form a fourth field."""
         recs, data = self._recs, self._data
         n = C.c_int(0)
         rc = _lib.lib().aisx_hdlc_batch_read(self._h, recs.ctypes.data_as(C.c_void_p), self.max_pdus,

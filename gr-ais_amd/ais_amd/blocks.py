@@ -849,12 +849,14 @@ class ais_rx:
 
     repair=rules (ais_amd.AIS_REPAIR_RULES, or as ais_amd.hdlc_deframer_bp takes them) turns the deframer's single-bit
     repair on: a burst with one wrong bit still gives its sentence, and popped_repairs() tells which records of the
-    block popped last were put right.
+    block popped last were put right.  repair_events=mask (ais_amd.AIS_REPAIR_EVENTS: all) makes it the repair of one
+    error event: one wrong bit, the two adjacent wrong bits one wrong decision of the differential slicer gives, and the
+    two wrong bits two apart of the sequence detector's error event.  ais_amd.repair_mark reads a mark.
     """
 
     def __init__(self, freq, rate, designator, nstreams=1, fmt="cf32", scale=1.0, bias=0.0, block_items=None,
                  preamble_symbols=None, taps=None, max_pdus_per_block=1 << 16, decode=False, tracks=None, repair=None,
-                 detector=None, bt=0.4):
+                 detector=None, bt=0.4, repair_events=1):
         from .batch_framing import PDU_DTYPE
         from .modulate import gmsk_mod, modulate_vector_bc
 
@@ -908,7 +910,7 @@ class ais_rx:
         if detector is not None:
             self.enable_detector(detector, bt)
         if repair is not None:
-            self.enable_repair(repair)
+            self.enable_repair(repair, repair_events)
         if decode:
             self.enable_messages()
         if tracks:
@@ -998,14 +1000,19 @@ class ais_rx:
         return (b.value, self._recs[: nr.value].copy(), self._text[: tl.value].tobytes(),
                 msg_table(self._cols, self._strs, nr.value))
 
-    def enable_repair(self, rules):
-        """what repair=rules does: the deframer repairs single-bit errors by these rules from the first block on.
-        ValueError once a slot has been taken or a block pushed, and for rules the deframer (11, 64) cannot take."""
-        from .framing import repair_rules
+    def enable_repair(self, rules, events=1):
+        """what repair=rules, repair_events=events does: the deframer repairs single-bit errors (events: the error events
+        of the mask) by these rules from the first block on.  ValueError once a slot has been taken or a block pushed,
+        and for rules the deframer (11, 64) cannot take or a bad mask."""
+        from .framing import REPAIR_SINGLE, repair_rules
 
         r = repair_rules(rules)
-        check(_lib.lib().aisx_rx_enable_repair(self._h, r.ctypes.data_as(C.c_void_p) if r.size else None, r.size),
-              "ais_rx.enable_repair")
+        if events == REPAIR_SINGLE:
+            rc = _lib.lib().aisx_rx_enable_repair(self._h, r.ctypes.data_as(C.c_void_p) if r.size else None, r.size)
+        else:
+            rc = _lib.lib().aisx_rx_enable_repair_events(self._h, r.ctypes.data_as(C.c_void_p) if r.size else None, r.size,
+                                                        int(events))
+        check(rc, "ais_rx.enable_repair")
         self.repair = True
 
     def enable_detector(self, detector="mlse", bt=0.4):
@@ -1020,8 +1027,8 @@ class ais_rx:
 
     def popped_repairs(self):
         """the repair marks of the block popped last (by pop() or pop_messages()), one per record: an int32 array, -1 for
-        a frame delivered as received, else the index of the flipped bit in the frame (payload + FCS, bit 0 the first
-        received).  Needs repair= (ValueError otherwise)."""
+        a frame delivered as received, else the index of the first flipped bit in the frame (payload + FCS, bit 0 the first
+        received) | event id << 16 (ais_amd.repair_mark).  Needs repair= (ValueError otherwise)."""
         fix = np.zeros(self._recs.size, dtype=np.int32)
         n = C.c_int(0)
         check(_lib.lib().aisx_rx_popped_repairs(self._h, fix.ctypes.data_as(C.c_void_p), fix.size, C.byref(n)),

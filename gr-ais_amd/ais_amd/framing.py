@@ -16,6 +16,32 @@ ANY_TYPE = (1 << 64) - 1
 # Single-bit repair rules for the ITU-R M.1371 messages of fixed length: {payload octets: the message types sent at that
 # length}.  168 bits: 1-3 and 4 / 11, 9, 18, 24 part B; 424: 5; 312: 19; 160: 24 part A; 96: 27.
 AIS_REPAIR_RULES = {21: (1, 2, 3, 4, 9, 11, 18, 24), 53: (5,), 39: (19,), 20: (24,), 12: (27,)}
+# The error events a repair can look for (a mask; include/aisx.h, AISX_HDLC_EV_*): one wrong bit, two adjacent wrong bits
+# (one wrong decision of the differential slicer) and two wrong bits two apart (the sequence detector's error event).
+# events= everywhere defaults to REPAIR_SINGLE, the single-bit repair; AIS_REPAIR_EVENTS holds all three.
+REPAIR_SINGLE, REPAIR_PAIR, REPAIR_SKIP = _lib.AISX_HDLC_EV_SINGLE, _lib.AISX_HDLC_EV_PAIR, _lib.AISX_HDLC_EV_SKIP
+AIS_REPAIR_EVENTS = REPAIR_SINGLE | REPAIR_PAIR | REPAIR_SKIP
+_PATTERNS = ((1,), (1, 1), (1, 0, 1))  # by event id, the first flipped bit first
+
+
+def repair_mark(mark):
+    """a repair mark (work(with_repairs=True), pdus(with_repairs=True), popped_repairs()) -> (first_bit, pattern_bits):
+    the index in the frame (payload + FCS, bit 0 the first received) of the first flipped bit, and the pattern that was
+    flipped from there on as a tuple of 0 / 1 -- (1,), (1, 1) or (1, 0, 1); (-1, ()) for a frame delivered as received"""
+    mark = int(mark)
+    if mark < 0:
+        return -1, ()
+    if (mark >> 16) >= len(_PATTERNS):
+        raise ValueError("repair_mark: %d is not a repair mark" % mark)
+    return mark & 0xFFFF, _PATTERNS[mark >> 16]
+
+
+def event_table(events):
+    """aisx_hdlc_event_table: uint16 [65536], for every FCS syndrome the enabled event nearest the frame's end as
+    id << 14 | distance of its last flipped bit + 1, 0 for none"""
+    t = np.zeros(65536, dtype=np.uint16)
+    check(_lib.lib(device=False).aisx_hdlc_event_table(int(events), t.ctypes.data_as(C.c_void_p)), "event_table")
+    return t
 
 
 def repair_rules(rules):
@@ -42,24 +68,30 @@ def repair_rules(rules):
 
 
 class hdlc_deframer_bp:
-    """digital.hdlc_deframer_bp(length_min, length_max).  repair: single-bit repair rules (repair_rules() says how
-    they are written, AIS_REPAIR_RULES is a ready set): a frame whose CRC fails by one wrong bit, of a length and
-    message type the rules allow, is put right and delivered; work(bits, with_repairs=True) marks those."""
+    """digital.hdlc_deframer_bp(length_min, length_max).  repair: repair rules (repair_rules() says how they are
+    written, AIS_REPAIR_RULES is a ready set): a frame whose CRC fails by one wrong bit -- with events=, by one of the
+    error events of that mask (AIS_REPAIR_EVENTS: all) -- of a length and message type the rules allow, is put right
+    and delivered; work(bits, with_repairs=True) marks those."""
 
-    def __init__(self, length_min, length_max, repair=None):
+    def __init__(self, length_min, length_max, repair=None, events=REPAIR_SINGLE):
         h = C.c_void_p()
         check(_lib.lib(device=False).aisx_hdlc_create(C.byref(h), int(length_min), int(length_max)), "hdlc_deframer_bp")
         self._h = h
         self._max = int(length_max)
         if repair is not None:
-            self.set_repair(repair)
+            self.set_repair(repair, events)
 
-    def set_repair(self, rules):
+    def set_repair(self, rules, events=REPAIR_SINGLE):
         """from the next frame that closes on; None or empty: off.  ValueError for rules the handle cannot take (more
-        than 16, a length outside [length_min - 2, length_max - 2] or given twice): it keeps the ones it had."""
+        than 16, a length outside [length_min - 2, length_max - 2] or given twice) or a mask that is 0 or has unknown
+        bits: it keeps what it had."""
         r = repair_rules(rules)
-        check(_lib.lib(device=False).aisx_hdlc_set_repair(self._h, r.ctypes.data_as(C.c_void_p) if r.size else None, r.size),
-              "hdlc_deframer_bp.set_repair")
+        L = _lib.lib(device=False)
+        if events == REPAIR_SINGLE:
+            rc = L.aisx_hdlc_set_repair(self._h, r.ctypes.data_as(C.c_void_p) if r.size else None, r.size)
+        else:
+            rc = L.aisx_hdlc_set_repair_events(self._h, r.ctypes.data_as(C.c_void_p) if r.size else None, r.size, int(events))
+        check(rc, "hdlc_deframer_bp.set_repair")
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -69,8 +101,9 @@ class hdlc_deframer_bp:
 
     def work(self, bits, with_repairs=False):
         """bits: unpacked bits (one per item).  Returns the list of PDUs (bytes) whose CRC checked -- or, with repair
-        rules, was made to by flipping one bit.  with_repairs=True: (PDUs, marks), a mark -1 for a frame delivered as
-        received, else the index of the flipped bit in the frame (payload + FCS, bit 0 the first received)."""
+        rules, was made to by flipping one bit or one error event.  with_repairs=True: (PDUs, marks), a mark -1 for a
+        frame delivered as received, else the index of the first flipped bit in the frame (payload + FCS, bit 0 the
+        first received) | event id << 16: for a single bit its index, and repair_mark() reads any."""
         b = np.ascontiguousarray(bits, dtype=np.uint8)
         maxp = b.size // 16 + 2
         buf = np.zeros(maxp * (self._max + 2), dtype=np.uint8)

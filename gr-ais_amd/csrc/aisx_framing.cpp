@@ -14,6 +14,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <mutex>
 #include <vector>
 
 #include "../../include/aisx.h"
@@ -78,6 +79,23 @@ const X25Syndromes& syndromes()
     return s;
 }
 
+// the event tables of aisx::hdlc_event_table, one per mask, built on first use
+class X25EventTables {
+public:
+    const uint16_t* get(int events)
+    {
+        std::call_once(once_[events], [&] {
+            tab_[events].resize(65536);
+            aisx::hdlc_event_table(events, tab_[events].data());
+        });
+        return tab_[events].data();
+    }
+
+private:
+    std::once_flag once_[AISX_HDLC_EV_ALL + 1];
+    std::vector<uint16_t> tab_[AISX_HDLC_EV_ALL + 1];
+};
+
 } // namespace
 
 // Receiver state: the run of ones seen so far (the de-stuffer), the octet being filled and the
@@ -88,8 +106,10 @@ struct aisx_hdlc {
     unsigned shift = 0;   // octet under construction, filled from the top and shifted down
     int nshift = 0;       // bits in it
     std::vector<uint8_t> frame;
-    int nrules = 0;       // single-bit repair (aisx_hdlc_set_repair): off without rules
+    int nrules = 0;       // repair by CRC syndrome (aisx_hdlc_set_repair, _set_repair_events): off without rules
     aisx_hdlc_rule rules[AISX_HDLC_MAX_RULES] = {};
+    int events = AISX_HDLC_EV_SINGLE;
+    const uint16_t* event_tab = nullptr; // aisx::hdlc_event_table(events); not used for the single event alone
 
     void drop_frame()
     {
@@ -115,9 +135,10 @@ struct aisx_hdlc {
     }
     // six ones in a row: end of frame (or an abort / idle flags when nothing was collected).
     // Whole octets only; the flag's own leading bits sit in the partial octet and go with it.
-    // the FCS of the frame does not match: one wrong bit at a place the syndrome names, in a frame whose length has a
-    // rule and whose message type after the flip the rule allows, is put right and the frame delivered with the
-    // bit's index (bit 0 = the first bit received); everything else is dropped
+    // the FCS of the frame does not match: one error event (one wrong bit, or with aisx_hdlc_set_repair_events one of
+    // the enabled patterns) at the place the syndrome names, in a frame whose length has a rule and whose message type
+    // after the flips the rule allows, is put right and the frame delivered with the mark first flipped bit's index
+    // (bit 0 = the first bit received) | event id << 16; everything else is dropped
     template <class Sink>
     void repair(unsigned syndrome, Sink&& deliver)
     {
@@ -126,13 +147,17 @@ struct aisx_hdlc {
         for (int k = 0; k < nrules && !rule; k++)
             if (rules[k].payload_octets == got - 2)
                 rule = &rules[k];
-        const int d1 = syndromes().inverse()[syndrome];
-        if (!rule || !d1 || d1 - 1 >= 8 * got)
+        // (the single event alone keeps the table it always had, which reaches further than any frame can be long)
+        const unsigned v = event_tab ? event_tab[syndrome] : syndromes().inverse()[syndrome];
+        const int id = event_tab ? (int)(v >> 14) : 0, d1 = event_tab ? (int)(v & 0x3FFFu) : (int)v;
+        if (!rule || !d1 || d1 - 1 + id >= 8 * got) // (an event's span is its id)
             return;
-        const int i = 8 * got - d1;
-        frame[(size_t)(i >> 3)] ^= (uint8_t)(1u << (i & 7)); // (in the FCS: the payload goes out as received)
+        const int last = 8 * got - d1, i = last - id;
+        frame[(size_t)(last >> 3)] ^= (uint8_t)(1u << (last & 7)); // (in the FCS: the payload goes out as received)
+        if (id)
+            frame[(size_t)(i >> 3)] ^= (uint8_t)(1u << (i & 7));
         if ((rule->type_mask >> (frame[0] >> 2)) & 1u)
-            deliver(frame.data(), got - 2, i);
+            deliver(frame.data(), got - 2, i | (id << 16));
     }
     template <class Sink>
     void delimiter(Sink&& deliver)
@@ -234,13 +259,53 @@ int aisx::hdlc_rules_check(const aisx_hdlc_rule* rules, int nrules, int length_m
 
 const uint16_t* aisx::hdlc_syndrome_table() { return syndromes().inverse(); }
 
-extern "C" int aisx_hdlc_set_repair(aisx_hdlc* h, const aisx_hdlc_rule* rules, int nrules)
+void aisx::hdlc_event_table(int events, uint16_t* out)
 {
-    if (!h || aisx::hdlc_rules_check(rules, nrules, h->min_octets, h->max_octets) != AISX_OK)
+    memset(out, 0, sizeof(uint16_t) * 65536);
+    unsigned s[3] = { 0x8000u, 0, 0 }; // s(d), s(d + 1), s(d + 2)
+    auto step = [](unsigned v) { return (v >> 1) ^ ((v & 1u) ? 0x8408u : 0u); };
+    s[1] = step(s[0]);
+    s[2] = step(s[1]);
+    for (int d = 0; d < AISX_HDLC_EV_REACH; d++) { // ascending: the first event to claim a syndrome is the nearest
+        for (int id = 0; id < 3; id++) {
+            const unsigned syn = id ? s[0] ^ s[id] : s[0];
+            if (((events >> id) & 1) && !out[syn])
+                out[syn] = (uint16_t)((id << 14) | (d + 1));
+        }
+        s[0] = s[1];
+        s[1] = s[2];
+        s[2] = step(s[2]);
+    }
+}
+
+const uint16_t* aisx::hdlc_event_table(int events)
+{
+    static X25EventTables tables;
+    return tables.get(events & AISX_HDLC_EV_ALL);
+}
+
+extern "C" int aisx_hdlc_set_repair_events(aisx_hdlc* h, const aisx_hdlc_rule* rules, int nrules, int events)
+{
+    if (!h || !aisx::hdlc_events_ok(events) || aisx::hdlc_rules_check(rules, nrules, h->min_octets, h->max_octets) != AISX_OK)
         return AISX_ERR_INVALID;
     h->nrules = nrules;
     for (int k = 0; k < nrules; k++)
         h->rules[k] = rules[k];
+    h->events = events;
+    h->event_tab = events == AISX_HDLC_EV_SINGLE ? nullptr : aisx::hdlc_event_table(events);
+    return AISX_OK;
+}
+
+extern "C" int aisx_hdlc_set_repair(aisx_hdlc* h, const aisx_hdlc_rule* rules, int nrules)
+{
+    return aisx_hdlc_set_repair_events(h, rules, nrules, AISX_HDLC_EV_SINGLE);
+}
+
+extern "C" int aisx_hdlc_event_table(int events, uint16_t* table)
+{
+    if (!table || !aisx::hdlc_events_ok(events))
+        return AISX_ERR_INVALID;
+    aisx::hdlc_event_table(events, table);
     return AISX_OK;
 }
 

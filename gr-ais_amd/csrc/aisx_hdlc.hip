@@ -30,6 +30,14 @@ __global__ __launch_bounds__(HD_T) void k_hdlc_deframe_repair(HdlcParams p)
     hdlc_deframe_body<DevCtx, true>(cx, p);
 }
 
+// the deframer of a handle with repair rules and an event mask that is not the single event alone
+__global__ __launch_bounds__(HD_T) void k_hdlc_deframe_events(HdlcParams p)
+{
+    __shared__ __attribute__((aligned(16))) char smem[HD_LDS_BYTES_REPAIR];
+    DevCtx cx{ smem };
+    hdlc_deframe_body<DevCtx, true, true>(cx, p);
+}
+
 __global__ __launch_bounds__(HD_SCAN_T) void k_hdlc_scan(HdlcScanParams p)
 {
     __shared__ __attribute__((aligned(16))) char smem[2 * HD_SCAN_T * 8];
@@ -64,6 +72,10 @@ struct aisx_hdlc_batch {
     DevBuf<HdlcRule> d_rules;
     DevBuf<unsigned short> d_syn_inv;
     DevBuf<int> d_sfix;        // [nchan][rec_cap]
+    // error events (aisx_hdlc_batch_set_repair_events): the mask, and for one that is not the single event alone its table
+    int events = AISX_HDLC_EV_SINGLE;
+    int ev_tab_events = 0;     // the mask d_ev_tab holds the table of, 0 = none yet
+    DevBuf<unsigned short> d_ev_tab;
 };
 
 extern "C" int aisx_hdlc_batch_destroy(aisx_hdlc_batch* h)
@@ -133,15 +145,28 @@ extern "C" int aisx_hdlc_batch_reset(aisx_hdlc_batch* h)
 
 extern "C" int aisx_hdlc_batch_set_repair(aisx_hdlc_batch* h, const aisx_hdlc_rule* rules, int nrules)
 {
-    if (!h || hdlc_rules_check(rules, nrules, h->lmin, h->lmax) != AISX_OK) {
-        set_err("aisx_hdlc_batch_set_repair: need a handle and at most %d rules with distinct payload lengths in "
-                "[length_min - 2, length_max - 2] and reserved = 0", AISX_HDLC_MAX_RULES);
+    return aisx_hdlc_batch_set_repair_events(h, rules, nrules, AISX_HDLC_EV_SINGLE);
+}
+
+extern "C" int aisx_hdlc_batch_set_repair_events(aisx_hdlc_batch* h, const aisx_hdlc_rule* rules, int nrules, int events)
+{
+    if (!h || !hdlc_events_ok(events) || hdlc_rules_check(rules, nrules, h->lmin, h->lmax) != AISX_OK) {
+        set_err("aisx_hdlc_batch_set_repair: need a handle, at most %d rules with distinct payload lengths in "
+                "[length_min - 2, length_max - 2] and reserved = 0, and a mask of AISX_HDLC_EV_* events",
+                AISX_HDLC_MAX_RULES);
         return AISX_ERR_INVALID;
     }
     OnDevice on(h->dev);
     AISX_HIPCHK(on.err);
-    AISX_HIPCHK(hipEventSynchronize(h->done)); // (the last call's kernels read the rules in place)
+    AISX_HIPCHK(hipEventSynchronize(h->done)); // (the last call's kernels read the rules and the table in place)
     int rc;
+    DevBuf<unsigned short> ev_tab; // (a mask's table is made beside the one in use, which stays if anything below fails)
+    const bool new_tab = nrules > 0 && events != AISX_HDLC_EV_SINGLE && h->ev_tab_events != events;
+    if (new_tab) {
+        if ((rc = ev_tab.alloc(65536, false)) != AISX_OK)
+            return rc;
+        AISX_HIPCHK(hipMemcpy(ev_tab, hdlc_event_table(events), sizeof(unsigned short) * 65536, hipMemcpyHostToDevice));
+    }
     if (nrules > 0) {
         if (!h->d_syn_inv) {
             DevBuf<HdlcRule> r;
@@ -160,7 +185,12 @@ extern "C" int aisx_hdlc_batch_set_repair(aisx_hdlc_batch* h, const aisx_hdlc_ru
         AISX_HIPCHK(hipMemset(h->d_fix, 0xFF, sizeof(int) * (size_t)h->max_pdus)); // (nothing writes the marks without rules)
         AISX_HIPCHK(hipStreamSynchronize(nullptr));
     }
+    if (new_tab) {
+        h->d_ev_tab = std::move(ev_tab);
+        h->ev_tab_events = events;
+    }
     h->nrules = nrules;
+    h->events = events;
     return AISX_OK;
 }
 
@@ -195,9 +225,14 @@ extern "C" int aisx_hdlc_batch_process(aisx_hdlc_batch* h, const uint8_t* d_bits
     if (h->nrules > 0) {
         p.rules = h->d_rules;
         p.nrules = h->nrules;
-        p.syn_inv = h->d_syn_inv;
         p.sfix = h->d_sfix;
-        hipLaunchKernelGGL(k_hdlc_deframe_repair, dim3(h->nchan), dim3(HD_T), 0, st, p);
+        if (h->events == AISX_HDLC_EV_SINGLE) {
+            p.syn_inv = h->d_syn_inv;
+            hipLaunchKernelGGL(k_hdlc_deframe_repair, dim3(h->nchan), dim3(HD_T), 0, st, p);
+        } else {
+            p.syn_inv = h->d_ev_tab;
+            hipLaunchKernelGGL(k_hdlc_deframe_events, dim3(h->nchan), dim3(HD_T), 0, st, p);
+        }
     } else {
         hipLaunchKernelGGL(k_hdlc_deframe, dim3(h->nchan), dim3(HD_T), 0, st, p);
     }

@@ -110,7 +110,8 @@ struct aisx_rx {
     const int32_t* d_fix = nullptr;    // only after aisx_rx_enable_repair: the deframer's marks,
     size_t fix_off = 0;                // and where they go in a result slot: int32 fix_bits[max_pdus]
     std::vector<int32_t> popped_fix;   // the marks of the block popped last
-    std::vector<aisx_hdlc_rule> rules; // what aisx_rx_enable_repair set (a deframer made again gets them again)
+    std::vector<aisx_hdlc_rule> rules; // what aisx_rx_enable_repair set (a deframer made again gets them again),
+    int events = AISX_HDLC_EV_SINGLE;  // and the error events to look for
     aisx_mlse_batch* ml = nullptr;     // only after aisx_rx_enable_mlse: the detector between the chain step and the deframer
     const int* d_ml_flag = nullptr;
     int mstride = 0;                   // row stride of d_mbits: cap + what the detector carries
@@ -640,6 +641,11 @@ extern "C" int aisx_rx_pop_messages(aisx_rx* h, int wait, long long* block, char
 
 extern "C" int aisx_rx_enable_repair(aisx_rx* h, const aisx_hdlc_rule* rules, int nrules)
 {
+    return aisx_rx_enable_repair_events(h, rules, nrules, AISX_HDLC_EV_SINGLE);
+}
+
+extern "C" int aisx_rx_enable_repair_events(aisx_rx* h, const aisx_hdlc_rule* rules, int nrules, int events)
+{
     if (!h) {
         set_err("aisx_rx_enable_repair: need a handle");
         return AISX_ERR_INVALID;
@@ -662,7 +668,7 @@ extern "C" int aisx_rx_enable_repair(aisx_rx* h, const aisx_hdlc_rule* rules, in
         if ((rc = slots[i].alloc(bytes)) != AISX_OK)
             set_err("aisx_rx_enable_repair: %zu bytes of pinned memory for result slot %d could not be had", bytes, i);
     const int32_t* d_fix = nullptr;
-    if (rc != AISX_OK || (rc = aisx_hdlc_batch_set_repair(h->hd, rules, nrules)) != AISX_OK ||
+    if (rc != AISX_OK || (rc = aisx_hdlc_batch_set_repair_events(h->hd, rules, nrules, events)) != AISX_OK ||
         (rc = aisx_hdlc_batch_repairs_device(h->hd, &d_fix)) != AISX_OK)
         return rc; // (the handle stays as it was)
     if (first) {
@@ -673,6 +679,7 @@ extern "C" int aisx_rx_enable_repair(aisx_rx* h, const aisx_hdlc_rule* rules, in
     }
     h->d_fix = d_fix;
     h->rules.assign(rules, rules + nrules);
+    h->events = events;
     return AISX_OK;
 }
 
@@ -700,7 +707,7 @@ extern "C" int aisx_rx_enable_mlse(aisx_rx* h, double bt)
         rc = aisx_hdlc_batch_create(&made_hd, RX_LMIN, RX_LMAX, rows, mstride, h->max_pdus);
     HandlePtr<aisx_hdlc_batch, aisx_hdlc_batch_destroy> hd(made_hd);
     if (rc == AISX_OK && !h->rules.empty())
-        rc = aisx_hdlc_batch_set_repair(hd.get(), h->rules.data(), (int)h->rules.size());
+        rc = aisx_hdlc_batch_set_repair_events(hd.get(), h->rules.data(), (int)h->rules.size(), h->events);
     DevBuf<cf> syms[RX_NOUT];
     DevBuf<uint8_t> mbits;
     DevBuf<int> mnb;

@@ -22,6 +22,10 @@
 // error inside the frame whose message type the rule allows makes the frame a good one, its bit flipped in the byte on
 // the way to staging (never in the LDS array: frames sharing a delimiter read it too) and its index kept beside the
 // record.
+// Error-event repair (hdlc_deframe_body<Ctx, true, true>, launched only for a handle whose event mask is not the
+// single event alone): the table is the mask's (aisx_hdlc_event_table: event id and distance of its last flipped bit),
+// the lookup gives id and the first flipped bit's index in the same 16 bits per good frame, the bytes on the way to
+// staging take up to two flips, which may sit in two octets, and the mark beside the record is index | id << 16.
 // hdlc_scan_body then places every channel's records behind those of the channels before it (one workgroup,
 // a scan of the counts) and hdlc_gather_body copies them there: records ordered by channel and end bit, no
 // atomic decides where one goes.
@@ -76,7 +80,9 @@ struct HdlcParams {
     // single-bit repair (read by hdlc_deframe_body<Ctx, true> alone)
     const HdlcRule* rules = nullptr; int nrules = 0;
     const unsigned short* syn_inv = nullptr; // [65536] syndrome -> distance from the frame's last bit + 1, 0 = none
+                                             // (EVENTS: event id << 14 | distance of its last flipped bit + 1)
     int* sfix = nullptr;                     // [nchan][rec_cap] staging: the flipped bit's index in the frame, -1 = none
+                                             // (EVENTS: the first flipped bit's index | event id << 16)
 };
 
 struct HdlcScanParams {
@@ -170,9 +176,31 @@ AISX_HD int hd_repair_bit(const HdlcRule* rules, int nrules, const unsigned shor
     return ((rules[k].type_mask >> (first >> 2)) & 1ULL) ? i : -1;
 }
 
-template <class Ctx, bool REPAIR = false>
+// hd_repair_bit for the error events of a mask's table: event id << 14 | (index of the event's FIRST flipped bit + 1),
+// or 0 under hd_repair_bit's conditions, all of the event's bits inside the frame (an event's span is its id) and the
+// type read with every flip below bit 8 applied
+AISX_HD unsigned hd_repair_event(const HdlcRule* rules, int nrules, const unsigned short* ev_tab, const unsigned long long* arr,
+                                 int fs, int oct, unsigned syn)
+{
+    int k = 0;
+    while (k < nrules && rules[k].payload_octets != oct - 2)
+        k++;
+    if (k == nrules)
+        return 0u;
+    const unsigned v = ev_tab[syn];
+    const int id = (int)(v >> 14), d1 = (int)(v & 0x3FFFu);
+    if (d1 == 0 || d1 - 1 + id >= 8 * oct)
+        return 0u;
+    const int last = 8 * oct - d1, i = last - id;
+    const unsigned flips = ((i < 8 ? 1u << i : 0u) | (last < 8 ? 1u << last : 0u)) & 0xFFu;
+    const unsigned first = ((unsigned)hd_read64(arr, fs) & 0xFFu) ^ flips;
+    return ((rules[k].type_mask >> (first >> 2)) & 1ULL) ? ((unsigned)id << 14) | (unsigned)(i + 1) : 0u;
+}
+
+template <class Ctx, bool REPAIR = false, bool EVENTS = false>
 AISX_DI void hdlc_deframe_body(Ctx& cx, const HdlcParams& p)
 {
+    static_assert(REPAIR || !EVENTS, "the error events are a form of the repair");
     const int l = cx.tid();
     const int c = cx.bx();
     char* lds = cx.lds();
@@ -281,7 +309,8 @@ AISX_DI void hdlc_deframe_body(Ctx& cx, const HdlcParams& p)
         cx.sync();
         // frames closed in this word: length and CRC
         // (REPAIR: fixes holds, 16 bits per good frame of this word in order, the flipped bit's index + 1 or 0 -- a
-        // good frame is at least 16 data bits and its delimiter, so a word closes four at most)
+        // good frame is at least 16 data bits and its delimiter, so a word closes four at most; EVENTS: the index is
+        // the first flipped bit's, 14 bits of it, and the event's id sits in the two bits above)
         unsigned long long good = 0, fixes = 0;
         int ng = 0, gb = 0;
         {
@@ -294,9 +323,13 @@ AISX_DI void hdlc_deframe_body(Ctx& cx, const HdlcParams& p)
                 if (oct >= p.lmin) {
                     const unsigned syn = hd_fcs_syndrome(crc, arr, a - r, oct);
                     int fix = -1;
-                    if constexpr (REPAIR)
+                    if constexpr (EVENTS) {
+                        if (syn != 0)
+                            fix = (int)hd_repair_event(rules, nrules, p.syn_inv, arr, a - r, oct, syn) - 1;
+                    } else if constexpr (REPAIR) {
                         if (syn != 0)
                             fix = hd_repair_bit(rules, nrules, p.syn_inv, arr, a - r, oct, syn);
+                    }
                     if (syn == 0 || fix >= 0) {
                         if constexpr (REPAIR)
                             fixes |= (unsigned long long)(fix + 1) << (16 * (ng & 3));
@@ -325,16 +358,22 @@ AISX_DI void hdlc_deframe_body(Ctx& cx, const HdlcParams& p)
                     o.chan = c;
                     o.len = len;
                     rec[ri] = o;
-                    const int fix = REPAIR ? (int)(fixes & 0xFFFFu) - 1 : -1;
+                    const int code = REPAIR ? (int)(fixes & 0xFFFFu) : 0;
+                    // the first flipped bit and the event's other one (REPAIR alone: the one bit, twice)
+                    const int fix = (EVENTS ? code & 0x3FFF : code) - 1;
+                    const int id = EVENTS ? code >> 14 : 0, fix2 = fix + id;
                     for (int k = 0; k < len; k++) {
                         unsigned v = (unsigned)hd_read64(arr, a - r + 8 * k);
                         if constexpr (REPAIR)
                             if ((fix >> 3) == k) // (never for -1, nor for a wrong bit in the FCS, which is not delivered)
                                 v ^= 1u << (fix & 7);
+                        if constexpr (EVENTS)
+                            if (id && (fix2 >> 3) == k)
+                                v ^= 1u << (fix2 & 7);
                         outb[bo + k] = (unsigned char)v;
                     }
                     if constexpr (REPAIR)
-                        p.sfix[(long)c * p.rec_cap + ri] = fix;
+                        p.sfix[(long)c * p.rec_cap + ri] = EVENTS && fix >= 0 ? fix | (id << 16) : fix;
                 }
                 if constexpr (REPAIR)
                     fixes >>= 16;

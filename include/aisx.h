@@ -581,12 +581,36 @@ typedef struct aisx_hdlc_rule {
  * the FCS delivers the payload as received.  Every other frame is dropped as before; which bits form a frame does not
  * change.  Two or more wrong bits are not repaired, and about n / 65535 of such n-bit frames look like a single error
  * and come out wrong with a matching CRC (before the type check): the marks of aisx_hdlc_work_repair tell a consumer
- * which PDUs to trust less.  The rules apply to every frame that closes after the call, one under way included. */
+ * which PDUs to trust less.  The rules apply to every frame that closes after the call, one under way included.
+ * The same as aisx_hdlc_set_repair_events with AISX_HDLC_EV_SINGLE. */
 int aisx_hdlc_set_repair(aisx_hdlc* h, const aisx_hdlc_rule* rules, int nrules);
-/* aisx_hdlc_work with one more output: fix_bits [max_pdus], -1 for a frame delivered as received, else the index of
- * the flipped bit in the frame (payload + FCS; bit 0 = the first bit received = bit 0 of octet 0; an index of
- * 8 * payload length or more lies in the FCS).  aisx_hdlc_work on a handle with rules returns the same PDUs without
- * the marks. */
+/* Repair of one error EVENT: a short fixed pattern of wrong bits anywhere in the destuffed frame.  Both bit sources of
+ * the receiver decode differentially, so one wrong decision never gives one wrong bit: a wrong symbol decision of the
+ * slicer gives two adjacent wrong bits (PAIR), the sequence detector's typical error two wrong bits two apart (SKIP).
+ * An event's id is its span: the distance between its first and last flipped bit. */
+#define AISX_HDLC_EV_SINGLE 1 /* pattern 1,   id 0 */
+#define AISX_HDLC_EV_PAIR 2   /* pattern 11,  id 1 */
+#define AISX_HDLC_EV_SKIP 4   /* pattern 101, id 2 */
+#define AISX_HDLC_EV_ALL 7
+#define AISX_HDLC_EV_REACH 16383 /* an event is looked for with its last flipped bit less than this far from the frame's last bit */
+/* aisx_hdlc_set_repair with a mask of the events to look for (rules: as there; when they apply: as there).
+ * AISX_ERR_INVALID also for a mask of 0 or with unknown bits, and the handle keeps the rules and mask it had.  The
+ * syndrome of an event whose LAST flipped bit is d bits before the frame's last bit is s(d) ^ s(d + span) (s(d) for
+ * SINGLE), s(0) = 0x8000 and one step of the CRC's shift register per bit.  Of the enabled events that give a failed
+ * frame's syndrome the one with the smallest d is taken (aisx_hdlc_event_table); when all its flipped bits lie inside
+ * the frame (d + span < 8 * octets) they are flipped, and when the message type after the flips is in the length's
+ * rule the payload is delivered.  Bits flipped in the FCS change nothing that is delivered.  SINGLE syndromes never
+ * equal PAIR or SKIP ones; PAIR at d and SKIP at d + 7140 share theirs, so in frames below 893 octets the choice is
+ * the only candidate, and in longer ones the nearer event wins. */
+int aisx_hdlc_set_repair_events(aisx_hdlc* h, const aisx_hdlc_rule* rules, int nrules, int events);
+/* table [65536]: for every syndrome the enabled event with the smallest d < AISX_HDLC_EV_REACH, as id << 14 | d + 1,
+ * or 0 for none: what the deframers look a failed frame up in.  AISX_ERR_INVALID for a bad mask. */
+int aisx_hdlc_event_table(int events, uint16_t* table);
+/* aisx_hdlc_work with one more output: fix_bits [max_pdus], the frames' repair MARKS: -1 for a frame delivered as
+ * received, else (index of the first flipped bit in the frame) | (event id << 16) -- payload + FCS; bit 0 = the first
+ * bit received = bit 0 of octet 0; an index of 8 * payload length or more lies in the FCS; the event's other flipped
+ * bit, if any, is id bits behind the first.  A single-bit repair's mark is the flipped bit's index.  aisx_hdlc_work on
+ * a handle with rules returns the same PDUs without the marks. */
 int aisx_hdlc_work_repair(aisx_hdlc* h, const uint8_t* bits, int nbits, uint8_t* pdu_bytes, int pdu_cap, int* pdu_offsets,
                           int32_t* fix_bits, int max_pdus, int* npdus);
 /* ais.pdu_to_nmea(designator)::msg_to_sentence (lib/pdu_to_nmea_impl.cc:63-131):
@@ -630,11 +654,16 @@ int aisx_hdlc_batch_read(aisx_hdlc_batch* h, aisx_pdu* pdus, int pdu_cap, uint8_
 /* aisx_hdlc_set_repair for every channel of the handle (the same rules, the same results as one host handle per
  * channel with them, marks included).  Waits for the handle's queued work; applies from the next process call on, to
  * every frame that closes in it, one opened before included.  Without rules the deframer launches the kernel it
- * launches on a handle that never had any. */
+ * launches on a handle that never had any.  The same as aisx_hdlc_batch_set_repair_events with AISX_HDLC_EV_SINGLE. */
 int aisx_hdlc_batch_set_repair(aisx_hdlc_batch* h, const aisx_hdlc_rule* rules, int nrules);
+/* aisx_hdlc_set_repair_events for every channel of the handle (the same results as one host handle per channel, marks
+ * included); waits and applies as aisx_hdlc_batch_set_repair does.  AISX_ERR_INVALID for bad rules or a bad mask, and
+ * the handle keeps what it had.  A mask of exactly AISX_HDLC_EV_SINGLE launches the single-bit kernel; any other mask
+ * its own kernel, with the mask's table (aisx_hdlc_event_table) uploaded here. */
+int aisx_hdlc_batch_set_repair_events(aisx_hdlc_batch* h, const aisx_hdlc_rule* rules, int nrules, int events);
 /* the last call's marks in device memory: d_fix_bits [max_pdus], entry k for record k of
- * aisx_hdlc_batch_results_device (-1: delivered as received, else the flipped bit's index as aisx_hdlc_work_repair
- * gives it).  On a handle without rules every entry is -1. */
+ * aisx_hdlc_batch_results_device (-1: delivered as received, else first flipped bit's index | event id << 16 as
+ * aisx_hdlc_work_repair gives it).  On a handle without rules every entry is -1. */
 int aisx_hdlc_batch_repairs_device(const aisx_hdlc_batch* h, const int32_t** d_fix_bits);
 /* copies the last call's marks to the host (synchronises `stream`): *n = PDUs found, the marks written are those of
  * the first min(*n, max_pdus, cap) records.  AISX_ERR_OVERFLOW when not all were written.  The bad-count flag is
@@ -888,11 +917,16 @@ int aisx_rx_pop_messages(aisx_rx* h, int wait, long long* block, char* text, lon
                          int rec_cap, int* nrecs, int32_t* cols, long col_stride, char* strs, int* status);
 /* Opt-in: aisx_hdlc_batch_set_repair on the handle's deframer, and every result slot also carries the block's marks.
  * Only before the first acquire, submit or push (AISX_ERR_INVALID afterwards, and for bad rules or none); a handle on
- * which this was never called allocates, queues and copies nothing more. */
+ * which this was never called allocates, queues and copies nothing more.  The same as aisx_rx_enable_repair_events
+ * with AISX_HDLC_EV_SINGLE. */
 int aisx_rx_enable_repair(aisx_rx* h, const aisx_hdlc_rule* rules, int nrules);
+/* aisx_rx_enable_repair with aisx_hdlc_batch_set_repair_events' mask of error events, under the same
+ * before-the-first-block rule (AISX_ERR_INVALID also for a bad mask; the handle stays as it was). */
+int aisx_rx_enable_repair_events(aisx_rx* h, const aisx_hdlc_rule* rules, int nrules, int events);
 /* the marks of the block popped last (by aisx_rx_pop or aisx_rx_pop_messages), one per record of that block: *n of
- * them, the first min(*n, cap) written (AISX_ERR_OVERFLOW when cap is less).  Valid until the next pop; *n = 0 before
- * the first.  AISX_ERR_INVALID on a handle without repair enabled. */
+ * them, the first min(*n, cap) written (AISX_ERR_OVERFLOW when cap is less): -1, or first flipped bit's index |
+ * event id << 16 (aisx_hdlc_work_repair).  Valid until the next pop; *n = 0 before the first.  AISX_ERR_INVALID on a
+ * handle without repair enabled. */
 int aisx_rx_popped_repairs(aisx_rx* h, int32_t* fix_bits, int cap, int* n);
 /* Opt-in, and implies aisx_rx_enable_messages: the handle also owns a vessel table of `capacity` vessels
  * (aisx_track_batch_*, max_rows = max_pdus_per_block), and from the first block on the tail stream queues its update
@@ -911,7 +945,7 @@ int aisx_rx_read_changed_tracks(aisx_rx* h, int* idx, int32_t* cols, long col_st
 /* Opt-in: the bits the deframer reads are decided by the 4-state sequence detector (aisx_mlse_batch_*, below) of BT = bt
  * GMSK instead of the one-symbol slicer.  From the first block on every chain step also writes its symbols (one of
  * AISX_CHAIN_DEPTH buffers of the handle's), and the tail stream queues the detector between the step and the deframer,
- * which is made again for the detector's longer calls (max_bits + 79; rules set by aisx_rx_enable_repair are kept).
+ * which is made again for the detector's longer calls (max_bits + 79; rules and events set by aisx_rx_enable_repair / _events are kept).
  * Deframer, repair, NMEA, decoder and vessel table work as before behind it, and a record's end_bit counts the same
  * bits: bit n belongs to symbol n.  The detector decides a symbol once 80 to 143 later ones have arrived, so the last
  * 16 to 79 symbols of a channel stay undecided until more input follows; aisx_rx_flush does not flush the detector

@@ -8,8 +8,10 @@ per step (about 16 400 bits per channel per step), on one MI355X:
 
 --hw-queues N sets GPU_MAX_HW_QUEUES for this process (read by the HIP runtime at its first call); the pipelined chain
 wants 8 or more.  --repair turns the deframer's single-bit repair on with ais_amd.AIS_REPAIR_RULES (the host
-comparison then runs the host form with the same rules).  Writes one JSON file (--out).
-Usage: python tools/hdlc_bench.py [--nchan 4096] [--calls 50] [--steps 20] [--hw-queues 8] [--repair] --out F"""
+comparison then runs the host form with the same rules); --events MASK makes it the repair of the error events of that
+mask (ais_amd.AIS_REPAIR_EVENTS = 7: all; 1, the default, is the single-bit repair and its kernel).  Writes one JSON file
+(--out).
+Usage: python tools/hdlc_bench.py [--nchan 4096] [--calls 50] [--steps 20] [--hw-queues 8] [--repair [--events 7]] --out F"""
 import argparse
 import concurrent.futures as cf
 import json
@@ -57,8 +59,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--hw-queues", type=int, default=8)
     ap.add_argument("--repair", action="store_true")
+    ap.add_argument("--events", type=int, default=1)
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
+    if a.events != 1 and not a.repair:
+        sys.exit("hdlc_bench: --events needs --repair")
     nchan, T, sps = a.nchan, a.T, 4
     dev = torch.device("cuda", 0)
     opts = dict(samples_per_symbol=sps, bits_per_sec=9600.0, clockrec_gain=0.04, omega_relative_limit=0.01, fftlen=1024)
@@ -66,11 +71,13 @@ def main():
     xs = [bench.make_input(nchan, T, "S", sps, dev, r, True) for r in range(2)]
     dem = ais_amd.ais_demod(opts, nchan=nchan, max_items=T, stages="stock", preamble_symbols=tmpl)
     cap = dem.clockrec.out_capacity
-    hd = ais_amd.hdlc_deframer_batch(11, 64, nchan, cap, 1 << 17, repair=ais_amd.AIS_REPAIR_RULES if a.repair else None)
+    hd = ais_amd.hdlc_deframer_batch(11, 64, nchan, cap, 1 << 17)
+    if a.repair:
+        hd.set_repair(ais_amd.AIS_REPAIR_RULES, *([a.events] if a.events != 1 else []))
     rules = ais_amd.framing.repair_rules(ais_amd.AIS_REPAIR_RULES if a.repair else None)
     s = torch.cuda.Stream()
     res = {"shape": dict(nchan=nchan, T=T, length_min=11, length_max=64, max_bits=cap), "device": torch.cuda.get_device_name(0),
-           "gpu_max_hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]), "repair": bool(a.repair)}
+           "gpu_max_hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]), "repair": bool(a.repair), "events": a.events}
 
     def steps(n, deframe):
         n += n % 2  # (x_next alternates between the two inputs: every run ends where the next one starts)
@@ -110,7 +117,8 @@ def main():
     ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
     recs, _, fix = hd.pdus(stream=s, with_repairs=True)
     res["deframer_alone_ms"] = dict(median=ms[len(ms) // 2], min=ms[0], max=ms[-1], calls=a.calls,
-                                    pdus_per_call=int(len(recs)), repaired_per_call=int((fix >= 0).sum()))
+                                    pdus_per_call=int(len(recs)), repaired_per_call=int((fix >= 0).sum()),
+                                    repaired_by_event=[int(((fix >= 0) & (fix >> 16 == e)).sum()) for e in range(3)])
     res["deframer_alone_gbit_s"] = res["bits_per_step"]["total"] / (res["deframer_alone_ms"]["median"] * 1e-3) / 1e9
 
     # the pipelined step without / with the deframer behind it (alternating runs, each after a warm-up)
@@ -141,7 +149,10 @@ def main():
         n, h, found = C.c_int(0), C.c_void_p(), 0
         for c in chans:
             check(L.aisx_hdlc_create(C.byref(h), 11, 64), "aisx_hdlc_create")
-            check(L.aisx_hdlc_set_repair(h, rules.ctypes.data_as(C.c_void_p) if rules.size else None, rules.size), "aisx_hdlc_set_repair")
+            if a.events != 1:
+                check(L.aisx_hdlc_set_repair_events(h, rules.ctypes.data_as(C.c_void_p), rules.size, a.events), "aisx_hdlc_set_repair_events")
+            else:
+                check(L.aisx_hdlc_set_repair(h, rules.ctypes.data_as(C.c_void_p) if rules.size else None, rules.size), "aisx_hdlc_set_repair")
             rc = L.aisx_hdlc_work(h, rows[c].ctypes.data_as(C.c_void_p), int(nb[c]), buf.ctypes.data_as(C.c_void_p),
                                   buf.size, offs.ctypes.data_as(C.c_void_p), maxp, C.byref(n))
             L.aisx_hdlc_destroy(h)
