@@ -29,6 +29,11 @@ AISX_HDLC_EV_SINGLE, AISX_HDLC_EV_PAIR, AISX_HDLC_EV_SKIP = 1, 2, 4  # error eve
 AISX_MLSE_ST_BAD_COUNT = 1
 MLSE_BLOCK, MLSE_OVERLAP = 64, 16  # symbols a block of the sequence detector decides, and its window's overlap
 AISX_MSG_FL_COMPLETE, AISX_MSG_FL_NO_LAYOUT, AISX_MSG_FL_BAD_RECORD = 1, 2, 4
+AISX_NMEA_PARSE_REF_TAIL = 1
+# what a call of the NMEA parsers reports (include/aisx.h, AISX_NMEAP_*), in order
+AISX_NMEAP_NAMES = ("FOUND", "KEPT", "BAD_INPUT", "LINES", "SENTENCES", "REJ_FORMAT", "REJ_CHECKSUM", "REJ_CHANNEL",
+                    "REJ_ARMOUR", "REJ_FRAGMENT", "REJ_LENGTH", "CARRIED")
+AISX_NMEAP_NCNT = len(AISX_NMEAP_NAMES)
 
 KEY_CORR_START, KEY_PHASE_EST, KEY_TIME_EST, KEY_CORR_EST, KEY_PORT1 = 0, 1, 2, 3, 0x100
 KEY_NAMES = {0: "corr_start", 1: "phase_est", 2: "time_est", 3: "corr_est"}
@@ -230,6 +235,17 @@ def lib(device=True):
     sig("aisx_nmea_batch_process", i32, [vp, vp, vp, vp, vp, vp])
     sig("aisx_nmea_batch_results_device", i32, [vp, pvp, pvp, pvp])
     sig("aisx_nmea_batch_read", i32, [vp, vp, i32, vp, lng, pi32, pi32, vp])
+    ppc = C.POINTER(C.c_char_p)
+    sig("aisx_nmea_parse_create", i32, [pvp, ppc, i32, i32, i32, i32])
+    sig("aisx_nmea_parse_destroy", i32, [vp])
+    sig("aisx_nmea_parse_reset", i32, [vp])
+    sig("aisx_nmea_parse_work", i32, [vp, vp, lng, vp, i32, vp, lng, vp, vp])
+    sig("aisx_nmea_parse_batch_create", i32, [pvp, ppc, i32, i32, i32, i32, lng, i32, i32])
+    sig("aisx_nmea_parse_batch_destroy", i32, [vp])
+    sig("aisx_nmea_parse_batch_reset", i32, [vp])
+    sig("aisx_nmea_parse_batch_process", i32, [vp, vp, vp, vp])
+    sig("aisx_nmea_parse_batch_results_device", i32, [vp, pvp, pvp, pvp, pvp])
+    sig("aisx_nmea_parse_batch_read", i32, [vp, vp, i32, vp, lng, vp, vp, vp])
     sig("aisx_msg_decode", i32, [vp, i32, vp, vp])
     sig("aisx_msg_batch_create", i32, [pvp, i32, i32, i32])
     sig("aisx_msg_batch_destroy", i32, [vp])

@@ -205,6 +205,18 @@ def nmea_text_len(length, dlen):
     return F * (18 + (2 if F >= 10 else 1) + dlen) + max(F - 9, 0) + P - 1
 
 
+def _text_end(offset, length):
+    """where a pdu_to_nmea_batch record's text ends in the text buffer: behind its newline, which an empty text lacks
+    (integers, numpy or torch values alike)"""
+    return offset + length + (length > 0)
+
+
+class _DevMem:  # device memory a handle owns, for torch.as_tensor: a view keeps the handle alive through `owner`
+    def __init__(self, owner, ptr, shape, typestr):
+        self.owner = owner
+        self.__cuda_array_interface__ = dict(shape=shape, typestr=typestr, data=(ptr, False), version=3)
+
+
 class pdu_to_nmea_batch:
     """`pdu_to_nmea(designator)` for every PDU of a device list at once: per record, byte for byte what
     ais_amd.pdu_to_nmea(designator of its channel).msg_to_sentence(payload) returns, followed by one '\n'; the
@@ -288,12 +300,155 @@ class pdu_to_nmea_batch:
         if not (rc == _lib.AISX_ERR_OVERFLOW and overflow_ok):
             check(rc, "pdu_to_nmea_batch.sentences")
         recs = recs[: n.value].copy()
-        nt = int(recs["offset"][-1] + recs["len"][-1] + (recs["len"][-1] > 0)) if len(recs) else 0
+        nt = int(_text_end(recs["offset"][-1], recs["len"][-1])) if len(recs) else 0
         text = text[:nt].tobytes()
         if as_list:
             return [(int(r["chan"]), int(r["end_bit"]), text[r["offset"]:r["offset"] + r["len"]].decode("latin-1"))
                     for r in recs]
         return recs, text
+
+
+class nmea_to_pdu_batch:
+    """ais_amd.nmea_to_pdu on the device (aisx_nmea_parse_batch_*): per call at most max_bytes bytes of text holding at
+    most max_lines line ends, at most max_pdus records; records, bytes, times and counts are the host form's with
+    pdu_cap = max_pdus, bit for bit and call by call, however the text is cut into calls.  results_device() gives
+    (pdus, bytes, count) as hdlc_deframer_batch's does, so every stage behind the deframer takes this handle in its
+    place.  Replaying recorded text into the vessel table, chunk by chunk on a stream `s`:
+
+        ps = ais_amd.nmea_to_pdu_batch(["A", "B"], 64, max_bytes, max_lines, max_pdus)
+        md = ais_amd.pdu_decode_batch(2, max_pdus, 64)
+        vt = ais_amd.vessel_table_batch(capacity, max_pdus)
+        for stamp, chunk in enumerate(chunks):           # bytes cut anywhere; the last one ends in a newline
+            ps.work(chunk, stream=s)                     # text -> PDUs
+            md.work(ps, stream=s)                        # PDUs -> fields
+            vt.work(md, stamp, stream=s, deframer=ps)    # fields -> vessels; nothing waits
+        vessels = vt.vessels(stream=s)
+
+    A call whose text breaks a bound (more than max_bytes bytes or max_lines line ends) is refused on the device and
+    advances nothing; messages() then raises ValueError."""
+
+    def __init__(self, designators, length_max, max_bytes, max_lines, max_pdus, max_line=512, ref_tail=False):
+        from .framing import _designators
+
+        d = _designators(designators)
+        arr = (C.c_char_p * len(d))(*d)
+        h = C.c_void_p()
+        check(_lib.lib().aisx_nmea_parse_batch_create(C.byref(h), arr, len(d), int(length_max), int(max_line),
+                                                      _lib.AISX_NMEA_PARSE_REF_TAIL if ref_tail else 0, int(max_bytes),
+                                                      int(max_lines), int(max_pdus)), "nmea_to_pdu_batch")
+        self._h = h
+        self.nchan, self.length_max, self.max_line = len(d), int(length_max), int(max_line)
+        self.max_bytes, self.max_lines, self.max_pdus = int(max_bytes), int(max_lines), int(max_pdus)
+        self.found = 0
+        self._text = self._n = self._src = None  # the device copy of host text, made on first use
+        self._recs = np.zeros(self.max_pdus, dtype=PDU_DTYPE)
+        self._data = np.zeros(self.max_pdus * (self.length_max - 1) + 1, dtype=np.uint8)
+        self._times = np.zeros(self.max_pdus, dtype=np.int64)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            _lib.lib().aisx_nmea_parse_batch_destroy(h)
+            self._h = None
+
+    def reset(self):
+        check(_lib.lib().aisx_nmea_parse_batch_reset(self._h), "nmea_to_pdu_batch.reset")
+
+    def work(self, text, nbytes=None, stream=None):
+        """text: a contiguous uint8 device tensor, or host bytes (copied into a buffer of the handle's, at most
+        max_bytes of them).  nbytes: optionally a one-element int64 device tensor holding the byte count (read when the
+        work runs); by default the text's size.  Queued on `stream` (default: the current one); nothing waits.  Host
+        bytes go through ONE staging tensor of the handle's: such calls stay on one stream, or are separated by a
+        read (a handle's calls are ordered by its state anyway: the carry of one call is the next one's input)."""
+        s = stream if stream is not None else torch.cuda.current_stream()
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            t = bytes(text)
+            if len(t) > self.max_bytes:
+                raise ValueError("nmea_to_pdu_batch.work: %d bytes of text, max_bytes is %d" % (len(t), self.max_bytes))
+            if self._text is None:
+                self._text = torch.zeros(self.max_bytes, dtype=torch.uint8, device="cuda")
+                torch.cuda.synchronize()
+            with torch.cuda.stream(s):
+                if t:
+                    self._text[: len(t)].copy_(torch.frombuffer(bytearray(t), dtype=torch.uint8))
+                n = torch.tensor([len(t)], dtype=torch.int64).to("cuda")
+            text, nbytes = self._text, n
+        if text.dtype != torch.uint8 or not text.is_cuda or not text.is_contiguous():
+            raise ValueError("nmea_to_pdu_batch.work: text must be a contiguous uint8 device tensor or bytes")
+        if nbytes is None:
+            with torch.cuda.stream(s):
+                nbytes = torch.tensor([text.numel()], dtype=torch.int64).to("cuda")
+        if nbytes.dtype != torch.int64 or not nbytes.is_cuda or nbytes.numel() != 1:
+            raise ValueError("nmea_to_pdu_batch.work: nbytes must be a one-element int64 device tensor")
+        self._n, self._src = nbytes, text  # (kept alive until the next call)
+        self.work_device(text.data_ptr() if text.numel() else self._dummy().data_ptr(), nbytes.data_ptr(), s)
+
+    def work_nmea(self, armourer, stream=None):
+        """Parses the text of a pdu_to_nmea_batch's last call where it is (create the parser with ref_tail=True, and with
+        max_bytes >= the armourer's text_cap).  The armourer keeps no text length on the device, so it is worked out
+        there from its last written record (_text_end, the rule its own sentences() reads the text by) with a few
+        tensor operations on `stream`: nothing waits."""
+        s = stream if stream is not None else torch.cuda.current_stream()
+        p, t, n = armourer.results_device()
+        dev = torch.device("cuda", torch.cuda.current_device())
+        raw = torch.as_tensor(_DevMem(armourer, p, (armourer.max_pdus, PDU_DTYPE.itemsize), "|u1"), device=dev)
+        cnt = torch.as_tensor(_DevMem(armourer, n, (3,), "<i4"), device=dev)
+
+        def field(row, name):  # one field of a record, by PDU_DTYPE's own offsets
+            dt, off = PDU_DTYPE.fields[name][:2]
+            return row[off:off + dt.itemsize].view(torch.int64 if dt.itemsize == 8 else torch.int32).to(torch.int64)
+
+        with torch.cuda.stream(s):
+            k = cnt[1:2].to(torch.int64)
+            last = raw.index_select(0, (k - 1).clamp(min=0))[0]
+            nbytes = torch.where(k > 0, _text_end(field(last, "offset"), field(last, "len")), torch.zeros_like(k))
+        self._n, self._src = nbytes, armourer
+        self.work_device(t, nbytes.data_ptr(), s)
+
+    def _dummy(self):
+        if self._text is None:
+            self._text = torch.zeros(self.max_bytes, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+        return self._text
+
+    def work_device(self, text_ptr, nbytes_ptr, stream=None):
+        """Device addresses: the text and ONE int64 = its byte count.  Queued on `stream`; the count is read on the
+        device, and no byte at or beyond it is."""
+        check(_lib.lib().aisx_nmea_parse_batch_process(self._h, C.c_void_p(text_ptr), C.c_void_p(nbytes_ptr), _stream_ptr(stream)),
+              "nmea_to_pdu_batch.work")
+
+    def _results(self):
+        p, b, n, t = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(_lib.lib().aisx_nmea_parse_batch_results_device(self._h, C.byref(p), C.byref(b), C.byref(n), C.byref(t)),
+              "nmea_to_pdu_batch.results_device")
+        return p.value, b.value, n.value, t.value
+
+    def results_device(self):
+        """device addresses of the last call's records (aisx_pdu [max_pdus]), bytes and counts (int
+        [AISX_NMEAP_NCNT], beginning found, kept, bad-input flag), as hdlc_deframer_batch.results_device()"""
+        return self._results()[:3]
+
+    def times_device(self):
+        """device address of the last call's times (int64 [max_pdus], entry k for record k)"""
+        return self._results()[3]
+
+    def messages(self, stream=None, overflow_ok=False):
+        """The last call's results on the host (synchronises `stream`): (records, bytes, times, counts) as
+        nmea_to_pdu.work gives them.  OverflowError when more than max_pdus messages were found -- or with
+        overflow_ok=True the first max_pdus (self.found tells how many there were); ValueError when a call since the
+        last read was refused."""
+        cnt = np.zeros(_lib.AISX_NMEAP_NCNT, dtype=np.int32)
+        rc = _lib.lib().aisx_nmea_parse_batch_read(self._h, self._recs.ctypes.data_as(C.c_void_p), self.max_pdus,
+                                                   self._data.ctypes.data_as(C.c_void_p), self._data.size,
+                                                   self._times.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p),
+                                                   _stream_ptr(stream))
+        self.found = int(cnt[0])
+        if not (rc == _lib.AISX_ERR_OVERFLOW and overflow_ok):
+            check(rc, "nmea_to_pdu_batch.messages")
+        k = int(cnt[1])
+        recs = self._recs[:k].copy()
+        nb = int(recs["offset"][-1] + recs["len"][-1]) if k else 0
+        return recs, self._data[:nb].copy(), self._times[:k].copy(), {n: int(v) for n, v in zip(_lib.AISX_NMEAP_NAMES, cnt)}
 
 
 class pdu_decode_batch:

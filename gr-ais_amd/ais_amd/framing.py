@@ -181,6 +181,72 @@ class pdu_to_nmea:
         return out.raw[:n].decode("latin-1")
 
 
+def _designators(designators):
+    if isinstance(designators, (str, bytes)):
+        designators = [designators]
+    return [d.encode() if isinstance(d, str) else bytes(d) for d in designators]
+
+
+_PDU_DTYPE = np.dtype([("end_bit", "<u8"), ("offset", "<i8"), ("chan", "<i4"), ("len", "<i4")])  # aisx_pdu
+
+
+class nmea_to_pdu:
+    """!AIVDM text back into PDUs on the host (aisx_nmea_parse_*, whose grammar include/aisx.h states): the inverse of
+    pdu_to_nmea for text from anywhere -- archives, other receivers, ais_rx's own output.  designators: the channel
+    field's text per channel index (a sentence whose field equals none is rejected); messages of at most
+    length_max - 1 octets; lines of at most max_line bytes.  The text is a byte stream: work() takes it in pieces cut
+    anywhere, an open multi-sentence group and a partial line wait for the next call.  ref_tail=True reads this
+    project's own armouring, whose last payload character is not standard when fill > 0: that character then counts
+    as six zero bits.
+
+        recs, data, times, counts = ais_amd.nmea_to_pdu(["A", "B"], 64).work(text)
+
+    recs: a PDU_DTYPE array (chan, len, offset into data, end_bit = line index of the message's last sentence);
+    times: the tag block's c: value of each message's first sentence, -1 without one; counts: a dict by the names of
+    _lib.AISX_NMEAP_NAMES.  The last line must end in a newline to be seen: there is no flush."""
+
+    def __init__(self, designators, length_max, max_line=512, ref_tail=False):
+        d = _designators(designators)
+        arr = (C.c_char_p * len(d))(*d)
+        h = C.c_void_p()
+        check(_lib.lib(device=False).aisx_nmea_parse_create(C.byref(h), arr, len(d), int(length_max), int(max_line),
+                                                            _lib.AISX_NMEA_PARSE_REF_TAIL if ref_tail else 0), "nmea_to_pdu")
+        self._h = h
+        self.length_max, self.max_line = int(length_max), int(max_line)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            _lib.lib(device=False).aisx_nmea_parse_destroy(h)
+            self._h = None
+
+    def reset(self):
+        check(_lib.lib(device=False).aisx_nmea_parse_reset(self._h), "nmea_to_pdu.reset")
+
+    def work(self, text, pdu_cap=None, bytes_cap=None, overflow_ok=False):
+        """text: bytes.  pdu_cap / bytes_cap: by default what the text can hold at most, so nothing overflows; with
+        smaller ones OverflowError when not every message was kept -- or with overflow_ok=True the prefix that was
+        (counts tells FOUND and KEPT).  The state advances either way."""
+        t = bytes(text)
+        if pdu_cap is None:
+            pdu_cap = t.count(b"\n") + 1
+        if bytes_cap is None:
+            bytes_cap = pdu_cap * (self.length_max - 1)
+        recs = np.zeros(max(pdu_cap, 1), dtype=_PDU_DTYPE)
+        data = np.zeros(max(bytes_cap, 1), dtype=np.uint8)
+        times = np.zeros(max(pdu_cap, 1), dtype=np.int64)
+        cnt = np.zeros(_lib.AISX_NMEAP_NCNT, dtype=np.int32)
+        rc = _lib.lib(device=False).aisx_nmea_parse_work(self._h, t, len(t), recs.ctypes.data_as(C.c_void_p), int(pdu_cap),
+                                                         data.ctypes.data_as(C.c_void_p), int(bytes_cap),
+                                                         times.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p))
+        if not (rc == _lib.AISX_ERR_OVERFLOW and overflow_ok):
+            check(rc, "nmea_to_pdu.work")
+        k = int(cnt[1])
+        recs = recs[:k].copy()
+        nb = int(recs["offset"][-1] + recs["len"][-1]) if k else 0
+        return recs, data[:nb].copy(), times[:k].copy(), {n: int(v) for n, v in zip(_lib.AISX_NMEAP_NAMES, cnt)}
+
+
 # the columns of a decoded message, in the order of include/aisx.h's AISX_MSG_COL_*
 MSG_COLUMNS = ("TYPE", "REPEAT", "MMSI", "FLAGS", "NAV_STATUS", "ROT", "SOG", "ACCURACY", "LON", "LAT", "COG", "HEADING",
                "SECOND", "MANEUVER", "RAIM", "RADIO", "IMO", "AIS_VERSION", "SHIPTYPE", "TO_BOW", "TO_STERN", "TO_PORT",

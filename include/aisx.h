@@ -704,6 +704,83 @@ int aisx_nmea_batch_read(aisx_nmea_batch* h, aisx_pdu* recs, int rec_cap, char* 
                          int* nfound, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* !AIVDM text back into PDUs: on the host (the specification), and batched   */
+/* on the device, where the record list feeds the stages behind the deframer  */
+/* ------------------------------------------------------------------------ */
+/* The text is a byte stream cut into calls anywhere; every result is the same for every way of cutting it.  A line
+ * ends at '\n' (one '\r' directly before it is dropped); line indices count line ends from create / reset.  A line of
+ * more than max_line bytes ('\r' included) is rejected once (REJ_FORMAT), where its '\n' arrives.  A sentence is a
+ * line of exactly the form
+ *     [\tagblock\]!TTVDM,F,f,[s],chan,payload,fill*HH
+ * TT two of A-Z / 0-9; F, f one digit 1..9 each, f <= F; s empty or one digit; chan 0..16 bytes without ',' or '*';
+ * payload any bytes without ','; fill one digit 0..5; HH two hex digits (either case), the line's last bytes.  A tag
+ * block runs from a leading '\' to the next one (none: REJ_FORMAT); its time is the first ','-separated field, of
+ * what precedes its last '*', that is "c:" and 1..18 digits, else -1 (as for a sentence without a block); the block's
+ * own checksum is not looked at.  Then, the first failure naming the reject: HH is the XOR of the bytes between '!'
+ * and '*' (REJ_CHECKSUM); chan equals one of the designators byte for byte, the smallest such index being the
+ * record's chan (REJ_CHANNEL); every payload byte is in '0'..'W' or '`'..'w' (REJ_ARMOUR).  With
+ * AISX_NMEA_PARSE_REF_TAIL the last payload character of a sentence with f == F and fill > 0 is not checked and
+ * counts as six zero bits (aisx_pdu_to_nmea keeps the reference's defect in that character).
+ * Messages form from accepted sentences in line order: F == 1 is a message; f == 1 with F > 1 opens a group, which
+ * completes when the next F - 1 accepted sentences carry f = 2..F in order with the same F, s and chan; anything
+ * else closes it (a sentence with f == 1 opens the next).  Every accepted sentence that ends up in no completed
+ * message counts in REJ_FRAGMENT, in the call that decides it.  An open group and a partial line survive calls.
+ * A message of P payload characters (its sentences' one behind the other) and the LAST sentence's fill has
+ * nbits = 6 P - fill and len = ceil(nbits / 8) octets; nbits <= 0 or len > length_max - 1 counts REJ_LENGTH and
+ * gives no record.  Character c is v = c - 48, less 8 more if that is above 40, six bits, most significant first;
+ * message bit i is bit 7 - i % 8 of octet i / 8 (what aisx_msg_decode reads); bits from nbits on are zero.
+ * The record: chan, len, offset (records' bytes one behind the other), end_bit = the line index of the message's
+ * last sentence; times[k] = the FIRST sentence's time. */
+enum { AISX_NMEA_PARSE_REF_TAIL = 1 };
+/* what a call reports: int counts[AISX_NMEAP_NCNT] */
+enum {
+    AISX_NMEAP_FOUND = 0,    /* messages that give a record */
+    AISX_NMEAP_KEPT,         /* records written: the first that fit the capacities (a prefix) */
+    AISX_NMEAP_BAD_INPUT,    /* device form only: a call since the last read was refused */
+    AISX_NMEAP_LINES,        /* line ends */
+    AISX_NMEAP_SENTENCES,    /* lines accepted as sentences */
+    AISX_NMEAP_REJ_FORMAT, AISX_NMEAP_REJ_CHECKSUM, AISX_NMEAP_REJ_CHANNEL, AISX_NMEAP_REJ_ARMOUR, /* lines rejected */
+    AISX_NMEAP_REJ_FRAGMENT, /* accepted sentences that ended up in no completed message */
+    AISX_NMEAP_REJ_LENGTH,   /* completed messages without a record */
+    AISX_NMEAP_CARRIED,      /* bytes of text held for the next call: the partial line and the open group's lines */
+    AISX_NMEAP_NCNT
+};
+typedef struct aisx_nmea_parse aisx_nmea_parse;
+/* nchan designators of 0..16 bytes, 2 <= length_max <= 1024, 64 <= max_line <= 4096, flags 0 or
+ * AISX_NMEA_PARSE_REF_TAIL.  Plain C++, no device. */
+int aisx_nmea_parse_create(aisx_nmea_parse** h, const char* const* designators, int nchan, int length_max, int max_line,
+                           int flags);
+int aisx_nmea_parse_destroy(aisx_nmea_parse* h);
+int aisx_nmea_parse_reset(aisx_nmea_parse* h); /* drops the open group and the partial line; line indices start at 0 */
+/* times may be NULL.  AISX_ERR_OVERFLOW when KEPT < FOUND (pdu_cap or bytes_cap); the state advances all the same. */
+int aisx_nmea_parse_work(aisx_nmea_parse* h, const char* text, long nbytes, aisx_pdu* pdus, int pdu_cap, uint8_t* bytes,
+                         long bytes_cap, int64_t* times, int* counts);
+
+typedef struct aisx_nmea_parse_batch aisx_nmea_parse_batch;
+/* The device form: per call at most max_bytes (<= 2^30) bytes of text holding at most max_lines (<= 2^26) line ends,
+ * at most max_pdus records (the byte buffer holds max_pdus * (length_max - 1), so only max_pdus can truncate).
+ * Records, bytes, times and counts equal the host form's with pdu_cap = max_pdus, bit for bit, call by call.  The
+ * handle belongs to the device that was current here. */
+int aisx_nmea_parse_batch_create(aisx_nmea_parse_batch** h, const char* const* designators, int nchan, int length_max,
+                                 int max_line, int flags, long max_bytes, int max_lines, int max_pdus);
+int aisx_nmea_parse_batch_destroy(aisx_nmea_parse_batch* h);
+int aisx_nmea_parse_batch_reset(aisx_nmea_parse_batch* h); /* waits for the handle's queued work */
+/* d_text: the call's bytes in device memory; d_nbytes: ONE value on the device, read when the work runs (the armouring
+ * stage's text length can be handed over as it is).  Queued on `stream`, no host synchronisation.  A call whose
+ * count lies outside [0, max_bytes], or whose text holds more than max_lines line ends, advances nothing and makes
+ * the next read say so.  No byte at or beyond *d_nbytes is read. */
+int aisx_nmea_parse_batch_process(aisx_nmea_parse_batch* h, const char* d_text, const long long* d_nbytes, void* stream);
+/* the last call's results in device memory: d_pdus [max_pdus], d_bytes, d_count [AISX_NMEAP_NCNT] (its first three
+ * entries as every producer's here: found, kept, bad-input flag), d_times [max_pdus] */
+int aisx_nmea_parse_batch_results_device(const aisx_nmea_parse_batch* h, const aisx_pdu** d_pdus, const uint8_t** d_bytes,
+                                         const int** d_count, const int64_t** d_times);
+/* copies the last call's results to the host (synchronises `stream`): the first records kept that fit pdu_cap and
+ * bytes_cap (counts[AISX_NMEAP_KEPT] says how many), times may be NULL.  AISX_ERR_INVALID when a call since the
+ * previous read was refused (the flag is then cleared), AISX_ERR_OVERFLOW when fewer records were copied than found. */
+int aisx_nmea_parse_batch_read(aisx_nmea_parse_batch* h, aisx_pdu* pdus, int pdu_cap, uint8_t* bytes, long bytes_cap,
+                               int64_t* times, int* counts, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* ITU-R M.1371 message fields: one PDU on the host (the specification), and  */
 /* every record of a device PDU list at once, queued behind the deframer      */
 /* ------------------------------------------------------------------------ */
