@@ -143,6 +143,8 @@ def lib(device=True):
     sig("aisx_msk_wait_tail", i32, [vp, vp])
     sig("aisx_msk_set_fused_tail", i32, [vp, i32])
     sig("aisx_msk_get_fused_tail", i32, [vp])
+    sig("aisx_msk_set_pair_core", i32, [vp, i32])
+    sig("aisx_msk_get_pair_core", i32, [vp])
     sig("aisx_msk_last_tail_fused", i32, [vp])
     sig("aisx_msk_wait_prepass", i32, [vp, vp])
     sig("aisx_msk_set_head_start", i32, [vp, i32])

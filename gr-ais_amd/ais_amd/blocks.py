@@ -280,6 +280,14 @@ class msk_timing_recovery_cc:
     def get_fused_tail(self):
         return bool(_lib.lib().aisx_msk_get_fused_tail(self._h))
 
+    def set_pair_core(self, mode):
+        """Schedule of the kernel's lock-step iteration pair (aisx_msk_set_pair_core): 1 (default) the hand-scheduled
+        sequence, 0 the compiler's.  Results are identical; calls of either mode may alternate."""
+        check(_lib.lib().aisx_msk_set_pair_core(self._h, int(mode)), "set_pair_core")
+
+    def get_pair_core(self):
+        return int(_lib.lib().aisx_msk_get_pair_core(self._h))
+
     def last_tail_fused(self):
         """Whether the last work() call that took bits computed them inside the recovery kernel."""
         return _lib.lib().aisx_msk_last_tail_fused(self._h) == 1

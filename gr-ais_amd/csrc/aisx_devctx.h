@@ -129,6 +129,116 @@ struct DevCtx {
             hi = mk(__uint_as_float(ra[1]), __uint_as_float(rb[1]));
         }
     }
+    // ---- The lock-step pair of the timing recovery (k_msk.h, 8 channels per wave) as one hand-scheduled stretch: from the
+    // state (mu, omega, sb) and the odd lane's previous square s1 to the new state, with the symbol of the PREVIOUS
+    // pair (`acc` on entry) staged at `waddr` while the reads are in flight.  Every float operation, its operands and
+    // its rounding are those of the C++ statements the other builds and the CPU lane model execute (k_msk.h, the plain
+    // pair loop): packed forms are two independent IEEE operations, nothing is fused, x - c is formed as x + (-c)
+    // only where c is a constant.  What the schedule does that the compiler's does not:
+    //  * taps and samples are multiplied where the reads left them (op_sel picks the tap's half of its register pair);
+    //    the second half of the table row, which holds the tap of the first product, is read first;
+    //  * three waits, none of which stalls behind the first: the first product's operands, the next read pair, then
+    //    everything but the staged symbol's write (LDS operations of a wave complete in the order issued, a read every
+    //    8 cycles; with ONE wait for all reads behind the first the kernel alone was 0.5 % slower than the compiler's, with three 2.9 % faster);
+    //  * the square comes out twice as (re, im) pairs, so the row swap needs no copies and the two products of
+    //    nlE / nlO are one packed instruction each;
+    //  * what is not on the dependent chain -- the stage write, its next address, the stage counter, sb + adv1, the
+    //    copy of the previous square -- stands behind the reads or where the hardware wants an independent instruction
+    //    anyway (2 wait states between a VALU write and v_permlane16_swap reading it: `s_nop 1`).
+    // v[0:23] take the reads and temporaries (clobbered), v[16:17] return sE, v[24:25] carry s1.
+    static constexpr bool has_pair_core = true;
+    struct PairK {                      // what a run keeps constant
+        unsigned long long roleM;       // lanes that run the odd iteration of their channel's pair
+        unsigned rbase;                 // mmse_row_base(): LDS byte address of tap row 0, biased
+        float gain_omega, d_sps, limit, gain;
+        unsigned rstep;                 // ring_read_off()'s step: the slot row bytes for the odd lanes, 0 for the even ones
+        unsigned ring;                  // LDS byte address of this lane's ring column
+        unsigned pmask, pbase;          // stage slot address = (so & pmask) + pbase (LDS byte address)
+        float rnd;                      // 1.5 * 2^23 (mmse_row_bits)
+    };
+    __device__ __forceinline__ void pair_core(const PairK& k, float& mu, float& omega, int& sb, unsigned& so, unsigned& waddr, v2f& acc,
+                                              v2f& sE, v2f& s1, float& nlO) const
+    {
+        float t1, t3, t4;
+        int t2;
+        asm volatile(
+            "v_add_f32 %[t3], %[mu], %[om]\n\t"                 // m1 = mu + omega
+            "v_cvt_i32_f32 %[t2], %[t3]\n\t"                    // adv1
+            "v_fract_f32 %[t1], %[t3]\n\t"                      // muO
+            "v_mad_u32_u24 %[t4], %[t2], %[rstep], %[sb]\n\t"   // ring_read_off
+            "v_cndmask_b32_e64 %[t3], %[mu], %[t1], %[roleM]\n\t"
+            "v_and_b32 %[t4], 0x3fc0, %[t4]\n\t"
+            "v_fmamk_f32 %[t3], %[t3], 0x43000000, %[rnd]\n\t"  // mmse_row_off
+            "v_add_u32 %[t4], %[ring], %[t4]\n\t"
+            "v_mad_u32_u24 %[t3], %[t3], 48, %[rbase]\n\t"
+            "ds_read_b128 v[4:7], %[t3] offset:16\n\t"          // taps 4..7
+            "ds_read2_b64 v[8:11], %[t4] offset1:8\n\t"         // samples 0, 1
+            "ds_read_b128 v[0:3], %[t3]\n\t"                    // taps 0..3
+            "ds_read2_b64 v[12:15], %[t4] offset0:16 offset1:24\n\t"
+            "ds_read2_b64 v[16:19], %[t4] offset0:32 offset1:40\n\t"
+            "ds_read2_b64 v[20:23], %[t4] offset0:48 offset1:56\n\t"
+            "ds_write_b64 %[waddr], %[acc]\n\t"                 // the previous pair's symbol
+            "v_lshl_add_u32 %[sb], %[t2], 6, %[sb]\n\t"         // sb1 = sb + adv1 * 64
+            "v_and_b32 %[waddr], %[so], %[pmask]\n\t"
+            "s_waitcnt lgkmcnt(5)\n\t"                          // taps 4..7, samples 0, 1
+            "v_pk_mul_f32 %[acc], v[8:9], v[6:7] op_sel:[0,1] op_sel_hi:[1,1]\n\t" // sample 0 * tap 7
+            "v_pk_mul_f32 v[8:9], v[10:11], v[6:7] op_sel_hi:[1,0]\n\t"           // sample 1 * tap 6
+            "v_pk_add_f32 %[acc], %[acc], 0 op_sel_hi:[1,0]\n\t"                  // 0 + p0
+            "s_waitcnt lgkmcnt(3)\n\t"                          // taps 0..3, samples 2, 3
+            "v_pk_mul_f32 v[10:11], v[12:13], v[4:5] op_sel:[0,1] op_sel_hi:[1,1]\n\t"
+            "v_pk_add_f32 %[acc], %[acc], v[8:9]\n\t"
+            "v_pk_mul_f32 v[8:9], v[14:15], v[4:5] op_sel_hi:[1,0]\n\t"
+            "v_pk_add_f32 %[acc], %[acc], v[10:11]\n\t"
+            "s_waitcnt lgkmcnt(1)\n\t"                          // every read (they return in order, 8 cycles apart)
+            "v_pk_mul_f32 v[10:11], v[16:17], v[2:3] op_sel:[0,1] op_sel_hi:[1,1]\n\t"
+            "v_pk_add_f32 %[acc], %[acc], v[8:9]\n\t"
+            "v_pk_mul_f32 v[8:9], v[18:19], v[2:3] op_sel_hi:[1,0]\n\t"
+            "v_pk_add_f32 %[acc], %[acc], v[10:11]\n\t"
+            "v_pk_mul_f32 v[10:11], v[20:21], v[0:1] op_sel:[0,1] op_sel_hi:[1,1]\n\t"
+            "v_pk_add_f32 %[acc], %[acc], v[8:9]\n\t"
+            "v_pk_mul_f32 v[8:9], v[22:23], v[0:1] op_sel_hi:[1,0]\n\t"
+            "v_pk_add_f32 %[acc], %[acc], v[10:11]\n\t"
+            "v_add_u32 %[waddr], %[pbase], %[waddr]\n\t"        // where this pair's symbol will go
+            "v_pk_add_f32 %[acc], %[acc], v[8:9]\n\t"
+            "v_add_u32 %[so], 64, %[so]\n\t"
+            "v_pk_mul_f32 v[18:19], %[acc], %[acc] op_sel:[0,0] op_sel_hi:[0,1]\n\t" // (re re, re im)
+            "v_pk_mul_f32 v[20:21], %[acc], %[acc] op_sel:[1,1] op_sel_hi:[1,0]\n\t" // (im im, im re)
+            "v_mov_b64 v[14:15], v[24:25]\n\t"                                       // sqO = the previous s1
+            "v_pk_add_f32 v[16:17], v[18:19], v[20:21] neg_lo:[0,1]\n\t"             // sq, twice
+            "v_pk_add_f32 v[24:25], v[18:19], v[20:21] neg_lo:[0,1]\n\t"
+            "s_nop 1\n\t"
+            "v_permlane16_swap_b32 v16, v24\n\t"                // v[16:17] = sE (the even lane's), v[24:25] = s1
+            "v_permlane16_swap_b32 v17, v25\n\t"
+            "v_pk_mul_f32 v[8:9], v[16:17], v[14:15]\n\t"       // sE * sqO by components
+            "v_pk_mul_f32 v[10:11], v[24:25], v[16:17]\n\t"     // s1 * sE
+            "v_add_f32 v0, v8, v9\n\t"                          // nlE
+            "v_add_f32 %[nlO], v10, v11\n\t"
+            "v_sub_f32 v0, %[nlO], v0\n\t"
+            "v_add_f32 v1, 0x40400000, v0\n\t"                  // branchless_clip(.., 3)
+            "v_add_f32 v2, 0xc0400000, v0\n\t"
+            "v_sub_f32_e64 v0, |v1|, |v2|\n\t"
+            "v_mul_f32 v0, 0.5, v0\n\t"                         // err
+            "v_mul_f32 v1, %[go], v0\n\t"
+            "v_mul_f32 v2, %[gain], v0\n\t"
+            "v_add_f32 v1, %[om], v1\n\t"                       // omega + gain_omega err
+            "v_add_f32 v2, %[t1], v2\n\t"                       // mu2 = muO + gain err
+            "v_subrev_f32 v1, %[dsps], v1\n\t"
+            "v_add_f32 v0, %[lim], v1\n\t"                      // branchless_clip(.., limit)
+            "v_subrev_f32 v1, %[lim], v1\n\t"
+            "v_sub_f32_e64 v0, |v0|, |v1|\n\t"
+            "v_mul_f32 v0, 0.5, v0\n\t"
+            "v_add_f32 %[om], %[dsps], v0\n\t"
+            "v_add_f32 v2, v2, %[om]\n\t"                       // m2
+            "v_cvt_i32_f32 v3, v2\n\t"
+            "v_fract_f32 %[mu], v2\n\t"
+            "v_lshl_add_u32 %[sb], v3, 6, %[sb]"
+            : [mu] "+v"(mu), [om] "+v"(omega), [sb] "+v"(sb), [so] "+v"(so), [waddr] "+v"(waddr), [acc] "+v"(acc), "={v[16:17]}"(sE),
+              "+{v[24:25]}"(s1), [nlO] "=&v"(nlO), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4)
+            : [roleM] "s"(k.roleM), [rbase] "s"(k.rbase), [go] "s"(k.gain_omega), [dsps] "s"(k.d_sps), [lim] "s"(k.limit), [gain] "s"(k.gain),
+              [rstep] "v"(k.rstep), [ring] "v"(k.ring), [pmask] "v"(k.pmask), [pbase] "v"(k.pbase), [rnd] "v"(k.rnd)
+            : "memory", "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v18", "v19",
+              "v20", "v21", "v22", "v23");
+    }
     // Transpose of eight complex registers against lane bits 3 .. 5: x[j] of lane (h, e) <- x[h] of lane (j, e), h / j = bits
     // 5:3 of the lane, e = bits 2:0.  Three stages of pairwise half exchanges: lane bit 5 against register bit 2 by
     // v_permlane32_swap (lanes 32-63 of the first operand with lanes 0-31 of the second), lane bit 4 against register bit 1

@@ -38,6 +38,15 @@ __global__ __launch_bounds__(64 * msk_waves(LPW)) void k_msk_ff(MskParams p)
     msk_body<DevCtx, false, false, LPW, true>(cx, p);
 }
 
+// the build the chain launches (no err / mu ports, osps 1, 8 channels per wave) with the hand-scheduled pair (MskParams::pair_core)
+__global__ __launch_bounds__(64 * msk_waves(8)) void k_msk_core(MskParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    DevCtx cx{ smem };
+    __builtin_amdgcn_s_setprio(MSK_PRIO);
+    msk_body<DevCtx, false, false, 8, false, true>(cx, p);
+}
+
 __global__ __launch_bounds__(BT_T) void k_bittail(BitTailParams p)
 {
     __shared__ __attribute__((aligned(16))) char smem[260 * 4];
@@ -90,6 +99,8 @@ int aisx::msk_launch(const MskParams& p, int nwg, hipStream_t st)
             return AISX_ERR_INVALID;
         }
         fn = ffs[li];
+    } else if (p.pair_core && v == 3 * 4) { // (the other builds keep the compiler's schedule)
+        fn = k_msk_core;
     }
     int rc = ensure_dyn_lds((const void*)fn, lds, "msk_timing_recovery_cc");
     if (rc != AISX_OK)
@@ -324,6 +335,7 @@ void aisx::msk_fill_common(aisx_msk* h, MskParams& p)
     p.tq_private = 0;
     p.lds_ring_off = msk_lds_ringoff(h->lpw);
     p.inline_tags = h->inline_tags;
+    p.pair_core = h->pair_core;
     p.stream_mode = 1;
     p.gr_ninput = 0;
     p.gr_noutput = 0;
@@ -592,6 +604,15 @@ extern "C" int aisx_msk_set_fused_tail(aisx_msk* h, int on)
 }
 extern "C" int aisx_msk_get_fused_tail(const aisx_msk* h) { return h ? (h->fused_tail ? 1 : 0) : AISX_ERR_INVALID; }
 extern "C" int aisx_msk_last_tail_fused(const aisx_msk* h) { return h ? (h->last_fused ? 1 : 0) : AISX_ERR_INVALID; }
+
+extern "C" int aisx_msk_set_pair_core(aisx_msk* h, int mode)
+{
+    if (!h || (mode != 0 && mode != 1))
+        return AISX_ERR_INVALID;
+    h->pair_core = mode;
+    return AISX_OK;
+}
+extern "C" int aisx_msk_get_pair_core(const aisx_msk* h) { return h ? h->pair_core : AISX_ERR_INVALID; }
 
 extern "C" int aisx_msk_wait_prepass(aisx_msk* h, void* stream)
 {

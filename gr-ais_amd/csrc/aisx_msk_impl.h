@@ -47,6 +47,7 @@ struct aisx_msk {
     // last call with d_bits took that path, and its stream (where its bits are complete); tail_pend[par]: a bit tail is
     // queued on the tail stream that no later call on the recovery's stream has waited for yet.
     bool fused_tail = true, last_fused = false;
+    int pair_core = 1; // aisx_msk_set_pair_core: 1 = the hand-scheduled lock-step pair where a build has it, 0 = the compiler's
     hipStream_t last_st = nullptr;
     bool tail_pend[2] = { false, false };
     aisx::DevBuf<int> d_produced2; // second internal `produced` array (alternates with d_produced)

@@ -178,6 +178,7 @@ struct MskParams {
     // equal what unit k assumed, unit k's run IS this loop's: the lane takes its symbol count and end
     // state, and the following units' too while each ended on the next one's assumption (k_mskp.h).
     int ff;
+    int pair_core = 0; // the build whose plain pair loop is the scheduled stretch (aisx_msk_set_pair_core; picked by the launcher)
     const int* nrst; const mskp_rst* rst; const mskp_res* res;
     mskp_piece* pieces; int* npieces;
     const int* ct_nc;  // carried tags in front of the new ones in `ct` (-1: a new tag was dropped, no fast-forward)
@@ -210,14 +211,22 @@ AISX_HD int msk_forecast(float d_sps, int noutput_items)
 #ifdef MSK_EMU_STATS
 extern long msk_stats[8];
 #endif
+// whether a context brings the hand-scheduled pair (Ctx::pair_core): the device's does, the CPU lane model's does not
+template <class Ctx, class = void>
+struct msk_has_pair_core { static constexpr bool value = false; };
+template <class Ctx>
+struct msk_has_pair_core<Ctx, decltype((void)Ctx::has_pair_core)> { static constexpr bool value = Ctx::has_pair_core; };
 // AUX: the err / mu output ports are connected (:187-189).  OSPS2: osps == 2 (:186).
 // LPW: channels (active lanes) per wave; the LDS layouts are [.][LPW], so a build with few
 // channels per wave leaves most of the CU's LDS to whatever else runs there.
 // FFT: the build that can run as the join of the time-parallel recovery (MskParams::ff; AUX and OSPS2 off).
-template <class Ctx, bool AUX, bool OSPS2, int LPW, bool FFT = false>
+// CORE: the plain lock-step pair runs the context's hand-scheduled stretch (Ctx::pair_core: the device's, aisx_devctx.h)
+// instead of the C++ statements; the launcher picks the build by MskParams::pair_core (8 channels per wave, AUX, OSPS2, FFT off).
+template <class Ctx, bool AUX, bool OSPS2, int LPW, bool FFT = false, bool CORE = false>
 AISX_DI void msk_body(Ctx& cx, const MskParams& p)
 {
     static_assert(!FFT || (!AUX && !OSPS2), "the join build has no err / mu ports and osps == 1");
+    static_assert(!CORE || (msk_has_pair_core<Ctx>::value && !AUX && !OSPS2 && !FFT && LPW == 8), "the scheduled pair is written for this build");
     constexpr int SLOT_B = LPW * 8;                                   // bytes per ring slot row
     constexpr int SLOT_SH = LPW == 64 ? 9 : (LPW == 32 ? 8 : (LPW == 16 ? 7 : (LPW == 8 ? 6 : 5))); // log2(SLOT_B)
     static_assert(LPW == 4 || LPW == 8 || LPW == 16 || LPW == 32 || LPW == 64, "channels per wave");
@@ -394,6 +403,13 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
         t.im = v.im;
         *(cf8s*)(lds0 + ((so & mask) | base)) = t;
         so += (unsigned)SLOT_B;
+    };
+    // (the plain pair loop stages the symbol of a pair while the NEXT pair waits for its reads: address kept from pair to pair)
+    auto stage_at = [&](unsigned at, cf v) {
+        cf8s t;
+        t.re = v.re;
+        t.im = v.im;
+        *(cf8s*)(lds0 + at) = t;
     };
     auto stage_get = [&](unsigned k) -> cf {
         const cf8s t = *(const cf8s*)(lds0 + ((((k & (unsigned)(MSK_STAGE - 1)) << SLOT_SH)) | stg_real));
@@ -1232,6 +1248,34 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
                 cf sqO = prev_sq, sqE = mk(0.f, 0.f), acc = last_interp;
                 float nl_prev = d_dly_diff_1.re;
                 const int sb_entry = sb;
+                // Builds with a symbol stage: the symbol of pair k is staged while pair k + 1 waits for its reads, where
+                // issue slots are free (the first pair of a run "stages" the entry value of acc in the spare row, the last
+                // symbol is staged at the run's exit).  `wat`: where the pair in progress will have its symbol staged.
+                // (the device's compiler-scheduled builds keep the write at the end of the pair: there it costs them no more)
+                constexpr bool ROT = STG && (CORE || !Ctx::wave_lds_coherent);
+                unsigned wat = stg_spare;
+              if constexpr (CORE) {
+                typename Ctx::PairK kk;
+                kk.roleM = cx.ballot(roleO);
+                kk.rbase = mm_rbase + cx.lds_addr(lds0);
+                kk.gain_omega = p.gain_omega;
+                kk.d_sps = d_sps;
+                kk.limit = p.limit;
+                kk.gain = p.gain;
+                kk.rstep = rstep;
+                kk.ring = cx.lds_addr(lds_l);
+                kk.pmask = pmask;
+                kk.pbase = pbase + cx.lds_addr(lds0);
+                kk.rnd = 12582912.0f;
+                typename Ctx::v2f a2 = Ctx::tov(acc), e2 = Ctx::tov(sqE), o2 = Ctx::tov(sqO);
+                wat += cx.lds_addr(lds0);
+                for (int k = 0; k < npairs; k++)
+                    cx.pair_core(kk, d_mu, d_omega, sb, so, wat, a2, e2, o2, nl_prev);
+                wat -= cx.lds_addr(lds0);
+                acc = Ctx::tocf(a2);
+                sqE = Ctx::tocf(e2);
+                sqO = Ctx::tocf(o2);
+              } else {
                 for (int k = 0; k < npairs; k++) {
 #ifdef MSK_EMU_STATS
                     if (l == 0 && q == 0) msk_stats[0]++;
@@ -1243,6 +1287,11 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
                     cf sv[8];
                     float tv[8];
                     fir_load_pair(roleO ? muO : d_mu, ring_read_off(sb, adv1, rstep, RING_M), sv, tv);
+                    if constexpr (ROT) {                                           // :186-191, the previous pair's
+                        stage_at(wat, acc);
+                        wat = (so & pmask) | pbase;
+                        so += (unsigned)SLOT_B;
+                    }
                     acc = fir_sum(sv, tv);
                     const cf sq = cmul_exact(acc, acc);                            // :171
                     cf sE, s1;
@@ -1264,7 +1313,8 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
                         }
                         ob += 16u;
                     } else if constexpr (STG) {
-                        stage_put(pmask, pbase, acc);
+                        if constexpr (!ROT)
+                            stage_put(pmask, pbase, acc);
                     } else {
                         if (!roleO) {
                             *(cf*)(osym0 + ob) = acc;
@@ -1284,6 +1334,9 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
                     sqO = s1;
                     nl_prev = nlO;
                 }
+              }
+                if constexpr (ROT)
+                    stage_at(wat, acc); // the run's last symbol
                 // the state every lane of the channel carries on with
                 cf accE, accO;
                 cx.template pair_rows<ROW>(acc, accE, accO);

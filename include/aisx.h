@@ -271,6 +271,15 @@ int aisx_msk_wait_tail(aisx_msk* h, void* stream);
 int aisx_msk_set_fused_tail(aisx_msk* h, int on);
 int aisx_msk_get_fused_tail(const aisx_msk* h);
 int aisx_msk_last_tail_fused(const aisx_msk* h);
+/* The schedule of the recovery kernel's lock-step iteration pair.  mode 1 (default): the build that the stream contract
+ * launches with osps 1 and d_err / d_mu NULL runs its plain pair loop as a hand-scheduled instruction sequence (operands
+ * used where the LDS reads leave them, two waits, the symbol staged while the next pair's reads are in flight).  mode 0:
+ * the same statements as the compiler schedules them.  The builds with err / mu ports, osps 2, the GNU Radio path and the
+ * join of the time-parallel recovery have the compiler's schedule in either mode.  Every float operation, its operands and
+ * its rounding are the same: results are identical bit for bit, state included, and calls of either mode may alternate on
+ * one handle.  The switch exists for twin tests and for A/B runs inside one library; it is not a tuning knob. */
+int aisx_msk_set_pair_core(aisx_msk* h, int mode);
+int aisx_msk_get_pair_core(const aisx_msk* h);
 /* Makes `stream` wait until the tag prepass of the last aisx_msk_process_stream call has run, i.e.
  * until that call's recovery kernel stands at the head of its queue.  The recovery kernel is 128
  * workgroups of 90 KB of LDS each: when it becomes ready at the same moment as a kernel with

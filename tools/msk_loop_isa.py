@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Instruction mix of the timing recovery's pair loops in the gfx950 code of k_msk<false, false, LPW>:
 
-    python tools/msk_loop_isa.py [--asm FILE.s] [--lpw 8] [--json OUT]
+    python tools/msk_loop_isa.py [--asm FILE.s] [--lpw 8] [--core] [--json OUT]
 
 Without --asm, compiles gr-ais_amd/csrc/aisx_msk.hip to assembly with the Makefile's flags (-S --cuda-device-only).
 The loops are found by the compiler's loop comments: every innermost loop of the kernel that swaps rows
 (v_permlane16/32_swap) is a pair loop; the one of a single basic block is the plain lock-step loop, the one of several
 blocks (the tag tests branch) the tagged-run loop.  Reported per loop: VALU (packed counted apart), LDS, SALU, s_nop,
 v_mov, s_waitcnt, the total, and for the plain loop the longest chain of register dependences within one trip (each
-instruction one step; s_nop and s_waitcnt not counted)."""
+instruction one step; s_nop and s_waitcnt not counted).  --core: the build with the hand-scheduled pair, k_msk_core (its
+inline assembly is part of the loop's block like any other instruction)."""
 import argparse
 import collections
 import json
@@ -28,8 +29,8 @@ def compile_asm(out):
     subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
 
 
-def kernel_body(txt, lpw):
-    name = "_Z5k_mskILb0ELb0ELi%dEEvN4aisx9MskParamsE" % lpw
+def kernel_body(txt, lpw, core=False):
+    name = "_Z10k_msk_coreN4aisx9MskParamsE" if core else "_Z5k_mskILb0ELb0ELi%dEEvN4aisx9MskParamsE" % lpw
     m = re.search(r"^%s:[^\n]*\n(.*?)^\.Lfunc_end\d+:" % name, txt, flags=re.S | re.M)
     if not m:
         sys.exit("no %s in the assembly" % name)
@@ -149,6 +150,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--asm", help="an assembly file of aisx_msk.hip (default: compile one)")
     ap.add_argument("--lpw", type=int, default=8)
+    ap.add_argument("--core", action="store_true", help="k_msk_core instead of k_msk<false, false, LPW>")
     ap.add_argument("--json", help="write the result here as well")
     a = ap.parse_args()
     path = a.asm
@@ -156,7 +158,7 @@ def main():
         fd, path = tempfile.mkstemp(suffix=".s")
         os.close(fd)
         compile_asm(path)
-    lines = kernel_body(open(path).read(), a.lpw)
+    lines = kernel_body(open(path).read(), a.lpw, a.core)
     bl = blocks(lines)
     loops = collections.OrderedDict()
     for b in bl:
@@ -170,7 +172,7 @@ def main():
             found.append((hdr, bs, ins))
     plain = [f for f in found if len(f[1]) == 1]
     tagged = [f for f in found if len(f[1]) > 1]
-    res = {"kernel": "k_msk<false,false,%d>" % a.lpw}
+    res = {"kernel": "k_msk_core" if a.core else "k_msk<false,false,%d>" % a.lpw}
     if plain:
         hdr, bs, ins = min(plain, key=lambda f: len(f[2]))
         res["plain_pair_loop"] = dict(mix(ins), label=hdr, chain=chain(ins))
