@@ -258,4 +258,18 @@ struct tag_rec {
 };
 enum { KEY_CORR_START = 0, KEY_PHASE_EST = 1, KEY_TIME_EST = 2, KEY_CORR_EST = 3 };
 
+// ------------------------------------------------------------------
+// Pieces of a batched stage's launch plan (the *Plan struct at the end of its k_*.h): host arithmetic the C ABI
+// and the CPU model of the stage both run, so that the model is driven by the product's plan and not a copy of it.
+// ------------------------------------------------------------------
+struct PlanBuf { // a buffer of a handle: its elements, and whether the device form allocates it zeroed
+    size_t n;
+    bool zeroed;
+};
+struct PlanLaunch { // one kernel launch; `kernel` is the stage's own id, `lds` what the kernel's wrapper declares
+    int kernel, gx, gy, threads, lds;
+};
+// A plan's per-call sequence issues its launches through a callable `bool launch(const PlanLaunch&, const Params&)`
+// and stops at the first that returns false.
+
 } // namespace aisx

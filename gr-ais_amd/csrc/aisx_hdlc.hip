@@ -52,10 +52,9 @@ __global__ __launch_bounds__(HD_T) void k_hdlc_gather(HdlcGatherParams p)
 }
 
 struct aisx_hdlc_batch {
+    explicit aisx_hdlc_batch(const HdlcPlan& plan) : pl(plan) {}
     int dev = 0;
-    int lmin = 0, lmax = 0, nchan = 0, max_bits = 0, max_pdus = 0;
-    int carry_words = 0, rec_cap = 0, byte_cap = 0;
-    long long out_bytes_cap = 0;
+    const HdlcPlan pl;         // the arguments, the sizes derived from them and the per-call sequence (k_hdlc.h)
     DevBuf<HdlcState> d_st;
     DevBuf<unsigned long long> d_carry;
     DevBuf<HdlcRec> d_srec;
@@ -93,37 +92,24 @@ extern "C" int aisx_hdlc_batch_create(aisx_hdlc_batch** out, int length_min, int
     if (!out)
         return AISX_ERR_INVALID;
     *out = nullptr;
-    if (length_min < 2 || length_max < length_min || length_max > HD_MAX_OCTETS || nchan < 1 || max_bits < 1 ||
-        max_bits > (1 << 28) || max_pdus < 1) {
-        set_err("aisx_hdlc_batch_create: need 2 <= length_min <= length_max <= %d, nchan >= 1, 1 <= max_bits <= 2^28, "
-                "max_pdus >= 1", HD_MAX_OCTETS);
+    if (const char* why = HdlcPlan::check(length_min, length_max, nchan, max_bits, max_pdus)) {
+        set_err("aisx_hdlc_batch_create: %s", why);
         return AISX_ERR_INVALID;
     }
     int rc = require_device();
     if (rc != AISX_OK)
         return rc;
-    HandlePtr<aisx_hdlc_batch, aisx_hdlc_batch_destroy> h(new aisx_hdlc_batch());
+    HandlePtr<aisx_hdlc_batch, aisx_hdlc_batch_destroy> h(new aisx_hdlc_batch(HdlcPlan(length_min, length_max, nchan, max_bits, max_pdus)));
     AISX_HIPCHK(hipGetDevice(&h->dev));
-    h->lmin = length_min;
-    h->lmax = length_max;
-    h->nchan = nchan;
-    h->max_bits = max_bits;
-    h->max_pdus = max_pdus;
-    // a call's good frames per channel: disjoint runs of >= 8 length_min data bits, each closed by a bit of its
-    // own, all but the first inside the call's bits; their payload comes from the open frame and the call's bits
-    const long long span = 8LL * (length_max + 1) + max_bits;
-    h->carry_words = (8 * (length_max + 1) + 63) / 64;
-    h->rec_cap = (int)(span / (8LL * length_min + 1) + 2);
-    h->byte_cap = (int)(span / 8 + 8);
-    h->out_bytes_cap = (long long)max_pdus * (length_max - 1); // (a payload is at most length_max - 1 octets)
-    if ((rc = h->d_st.alloc((size_t)nchan)) != AISX_OK || (rc = h->d_carry.alloc((size_t)nchan * h->carry_words)) != AISX_OK ||
-        (rc = h->d_srec.alloc((size_t)nchan * h->rec_cap, false)) != AISX_OK ||
-        (rc = h->d_sbytes.alloc((size_t)nchan * h->byte_cap, false)) != AISX_OK || (rc = h->d_cnt.alloc(2 * (size_t)nchan)) != AISX_OK ||
-        (rc = h->d_base.alloc(2 * (size_t)nchan)) != AISX_OK || (rc = h->d_count.alloc(4)) != AISX_OK ||
-        (rc = h->d_out.alloc((size_t)max_pdus)) != AISX_OK || (rc = h->d_out_bytes.alloc((size_t)h->out_bytes_cap)) != AISX_OK ||
-        (rc = h->d_fix.alloc((size_t)max_pdus, false)) != AISX_OK || (rc = h->done.create(hipEventDisableTiming)) != AISX_OK)
+    const HdlcPlan& pl = h->pl;
+    if ((rc = h->d_st.alloc(pl.st)) != AISX_OK || (rc = h->d_carry.alloc(pl.carry)) != AISX_OK ||
+        (rc = h->d_srec.alloc(pl.srec)) != AISX_OK || (rc = h->d_sbytes.alloc(pl.sbytes)) != AISX_OK ||
+        (rc = h->d_cnt.alloc(pl.cnt)) != AISX_OK || (rc = h->d_base.alloc(pl.base)) != AISX_OK ||
+        (rc = h->d_count.alloc(pl.count)) != AISX_OK || (rc = h->d_out.alloc(pl.out)) != AISX_OK ||
+        (rc = h->d_out_bytes.alloc(pl.out_bytes)) != AISX_OK || (rc = h->d_fix.alloc(pl.fix)) != AISX_OK ||
+        (rc = h->done.create(hipEventDisableTiming)) != AISX_OK)
         return rc;
-    AISX_HIPCHK(hipMemset(h->d_fix, 0xFF, sizeof(int) * (size_t)max_pdus));
+    AISX_HIPCHK(hipMemset(h->d_fix, 0xFF, sizeof(int) * pl.fix.n));
     *out = h.release();
     return AISX_OK;
 }
@@ -135,10 +121,10 @@ extern "C" int aisx_hdlc_batch_reset(aisx_hdlc_batch* h)
     OnDevice on(h->dev);
     AISX_HIPCHK(on.err);
     AISX_HIPCHK(hipEventSynchronize(h->done)); // (the last call's kernels; nothing else on the device)
-    AISX_HIPCHK(hipMemsetAsync(h->d_st, 0, sizeof(HdlcState) * h->nchan, nullptr));
-    AISX_HIPCHK(hipMemsetAsync(h->d_carry, 0, sizeof(unsigned long long) * h->nchan * h->carry_words, nullptr));
-    AISX_HIPCHK(hipMemsetAsync(h->d_cnt, 0, sizeof(int) * 2 * h->nchan, nullptr));
-    AISX_HIPCHK(hipMemsetAsync(h->d_count, 0, sizeof(int) * 4, nullptr));
+    AISX_HIPCHK(hipMemsetAsync(h->d_st, 0, sizeof(HdlcState) * h->pl.st.n, nullptr));
+    AISX_HIPCHK(hipMemsetAsync(h->d_carry, 0, sizeof(unsigned long long) * h->pl.carry.n, nullptr));
+    AISX_HIPCHK(hipMemsetAsync(h->d_cnt, 0, sizeof(int) * h->pl.cnt.n, nullptr));
+    AISX_HIPCHK(hipMemsetAsync(h->d_count, 0, sizeof(int) * h->pl.count.n, nullptr));
     AISX_HIPCHK(hipStreamSynchronize(nullptr)); // (done before the next call, whatever stream that is queued on)
     return AISX_OK;
 }
@@ -150,7 +136,7 @@ extern "C" int aisx_hdlc_batch_set_repair(aisx_hdlc_batch* h, const aisx_hdlc_ru
 
 extern "C" int aisx_hdlc_batch_set_repair_events(aisx_hdlc_batch* h, const aisx_hdlc_rule* rules, int nrules, int events)
 {
-    if (!h || !hdlc_events_ok(events) || hdlc_rules_check(rules, nrules, h->lmin, h->lmax) != AISX_OK) {
+    if (!h || !hdlc_events_ok(events) || hdlc_rules_check(rules, nrules, h->pl.lmin, h->pl.lmax) != AISX_OK) {
         set_err("aisx_hdlc_batch_set_repair: need a handle, at most %d rules with distinct payload lengths in "
                 "[length_min - 2, length_max - 2] and reserved = 0, and a mask of AISX_HDLC_EV_* events",
                 AISX_HDLC_MAX_RULES);
@@ -163,7 +149,7 @@ extern "C" int aisx_hdlc_batch_set_repair_events(aisx_hdlc_batch* h, const aisx_
     DevBuf<unsigned short> ev_tab; // (a mask's table is made beside the one in use, which stays if anything below fails)
     const bool new_tab = nrules > 0 && events != AISX_HDLC_EV_SINGLE && h->ev_tab_events != events;
     if (new_tab) {
-        if ((rc = ev_tab.alloc(65536, false)) != AISX_OK)
+        if ((rc = ev_tab.alloc(h->pl.syn)) != AISX_OK)
             return rc;
         AISX_HIPCHK(hipMemcpy(ev_tab, hdlc_event_table(events), sizeof(unsigned short) * 65536, hipMemcpyHostToDevice));
     }
@@ -172,8 +158,7 @@ extern "C" int aisx_hdlc_batch_set_repair_events(aisx_hdlc_batch* h, const aisx_
             DevBuf<HdlcRule> r;
             DevBuf<unsigned short> t;
             DevBuf<int> f;
-            if ((rc = r.alloc(HD_MAX_RULES)) != AISX_OK || (rc = t.alloc(65536, false)) != AISX_OK ||
-                (rc = f.alloc((size_t)h->nchan * h->rec_cap, false)) != AISX_OK)
+            if ((rc = r.alloc(h->pl.rules)) != AISX_OK || (rc = t.alloc(h->pl.syn)) != AISX_OK || (rc = f.alloc(h->pl.sfix)) != AISX_OK)
                 return rc;
             AISX_HIPCHK(hipMemcpy(t, hdlc_syndrome_table(), sizeof(unsigned short) * 65536, hipMemcpyHostToDevice));
             h->d_rules = std::move(r);
@@ -182,7 +167,7 @@ extern "C" int aisx_hdlc_batch_set_repair_events(aisx_hdlc_batch* h, const aisx_
         }
         AISX_HIPCHK(hipMemcpy(h->d_rules, rules, sizeof(HdlcRule) * nrules, hipMemcpyHostToDevice));
     } else if (h->nrules > 0) {
-        AISX_HIPCHK(hipMemset(h->d_fix, 0xFF, sizeof(int) * (size_t)h->max_pdus)); // (nothing writes the marks without rules)
+        AISX_HIPCHK(hipMemset(h->d_fix, 0xFF, sizeof(int) * h->pl.fix.n)); // (nothing writes the marks without rules)
         AISX_HIPCHK(hipStreamSynchronize(nullptr));
     }
     if (new_tab) {
@@ -197,74 +182,30 @@ extern "C" int aisx_hdlc_batch_set_repair_events(aisx_hdlc_batch* h, const aisx_
 extern "C" int aisx_hdlc_batch_process(aisx_hdlc_batch* h, const uint8_t* d_bits, long bits_stride, const int* d_nbits,
                                        void* stream)
 {
-    if (!h || !d_bits || !d_nbits || bits_stride < h->max_bits) {
+    if (!h || !d_bits || !d_nbits || bits_stride < h->pl.max_bits) {
         set_err("aisx_hdlc_batch_process: bits, counts and a row stride of at least max_bits (%d) are needed",
-                h ? h->max_bits : 0);
+                h ? h->pl.max_bits : 0);
         return AISX_ERR_INVALID;
     }
     OnDevice on(h->dev);
     AISX_HIPCHK(on.err);
     const hipStream_t st = (hipStream_t)stream;
-    HdlcParams p;
-    p.bits = d_bits;
-    p.stride = bits_stride;
-    p.nbits = d_nbits;
-    p.max_bits = h->max_bits;
-    p.lmin = h->lmin;
-    p.lmax = h->lmax;
-    p.st = h->d_st;
-    p.carry = h->d_carry;
-    p.carry_words = h->carry_words;
-    p.srec = h->d_srec;
-    p.rec_cap = h->rec_cap;
-    p.sbytes = h->d_sbytes;
-    p.byte_cap = h->byte_cap;
-    p.cnt = h->d_cnt;
-    p.nbytes = h->d_cnt + h->nchan;
-    p.flags = h->d_count + 2;
-    if (h->nrules > 0) {
-        p.rules = h->d_rules;
-        p.nrules = h->nrules;
-        p.sfix = h->d_sfix;
-        if (h->events == AISX_HDLC_EV_SINGLE) {
-            p.syn_inv = h->d_syn_inv;
-            hipLaunchKernelGGL(k_hdlc_deframe_repair, dim3(h->nchan), dim3(HD_T), 0, st, p);
-        } else {
-            p.syn_inv = h->d_ev_tab;
-            hipLaunchKernelGGL(k_hdlc_deframe_events, dim3(h->nchan), dim3(HD_T), 0, st, p);
+    const bool single = h->events == AISX_HDLC_EV_SINGLE;
+    const HdlcBufs b = { h->d_st,  h->d_carry,     h->d_srec, h->d_sbytes, h->d_cnt,  h->d_base, h->d_count,
+                         h->d_out, h->d_out_bytes, h->d_fix,  h->d_rules,  h->d_sfix, single ? h->d_syn_inv : h->d_ev_tab };
+    hipError_t err = hipSuccess;
+    h->pl.process(b, d_bits, bits_stride, d_nbits, h->nrules, !single, [&](const PlanLaunch& l, const HdlcCall& c) {
+        const dim3 grid(l.gx, l.gy), threads(l.threads);
+        switch (l.kernel) {
+        case HD_K_DEFRAME: hipLaunchKernelGGL(k_hdlc_deframe, grid, threads, 0, st, c.p); break;
+        case HD_K_DEFRAME_REPAIR: hipLaunchKernelGGL(k_hdlc_deframe_repair, grid, threads, 0, st, c.p); break;
+        case HD_K_DEFRAME_EVENTS: hipLaunchKernelGGL(k_hdlc_deframe_events, grid, threads, 0, st, c.p); break;
+        case HD_K_SCAN: hipLaunchKernelGGL(k_hdlc_scan, grid, threads, 0, st, c.s); break;
+        case HD_K_GATHER: hipLaunchKernelGGL(k_hdlc_gather, grid, threads, 0, st, c.g); break;
         }
-    } else {
-        hipLaunchKernelGGL(k_hdlc_deframe, dim3(h->nchan), dim3(HD_T), 0, st, p);
-    }
-    AISX_HIPCHK(hipGetLastError());
-    HdlcScanParams s;
-    s.cnt = p.cnt;
-    s.nbytes = p.nbytes;
-    s.rec_base = h->d_base;
-    s.byte_base = h->d_base + h->nchan;
-    s.nchan = h->nchan;
-    s.max_pdus = h->max_pdus;
-    s.count = h->d_count;
-    hipLaunchKernelGGL(k_hdlc_scan, dim3(1), dim3(HD_SCAN_T), 0, st, s);
-    AISX_HIPCHK(hipGetLastError());
-    HdlcGatherParams g;
-    g.srec = h->d_srec;
-    g.rec_cap = h->rec_cap;
-    g.sbytes = h->d_sbytes;
-    g.byte_cap = h->byte_cap;
-    g.cnt = p.cnt;
-    g.nbytes = p.nbytes;
-    g.rec_base = s.rec_base;
-    g.byte_base = s.byte_base;
-    g.max_pdus = h->max_pdus;
-    g.out = h->d_out;
-    g.out_bytes = h->d_out_bytes;
-    if (h->nrules > 0) {
-        g.sfix = h->d_sfix;
-        g.out_fix = h->d_fix;
-    }
-    hipLaunchKernelGGL(k_hdlc_gather, dim3(h->nchan), dim3(HD_T), 0, st, g);
-    AISX_HIPCHK(hipGetLastError());
+        return (err = hipGetLastError()) == hipSuccess;
+    });
+    AISX_LAUNCHCHK(err);
     AISX_HIPCHK(hipEventRecord(h->done, st));
     return AISX_OK;
 }
@@ -309,7 +250,7 @@ extern "C" int aisx_hdlc_batch_read(aisx_hdlc_batch* h, aisx_pdu* pdus, int pdu_
     *npdus = cnt[0];
     if (cnt[2]) {
         set_err("aisx_hdlc_batch_read: a channel's bit count was outside [0, %d]: that channel was not advanced",
-                h->max_bits);
+                h->pl.max_bits);
         return AISX_ERR_INVALID;
     }
     if (k < cnt[0]) {

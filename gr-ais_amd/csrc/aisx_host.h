@@ -39,6 +39,15 @@ inline void set_err(const char* fmt, ...)
         }                                                                                      \
     } while (0)
 
+// The same for what a launch plan's callable kept of hipGetLastError() behind the launch its sequence stopped at.
+#define AISX_LAUNCHCHK(err)                                                                    \
+    do {                                                                                       \
+        if ((err) != hipSuccess) {                                                             \
+            ::aisx::set_err("hipGetLastError() failed: %s (%s:%d)", hipGetErrorString(err), __FILE__, __LINE__); \
+            return AISX_ERR_HIP;                                                               \
+        }                                                                                      \
+    } while (0)
+
 // Experiment knobs.  The product library reads NO environment variable: its behaviour is what the API was told.
 // A build made with -DAISX_EXPERIMENTS (lib/libaisx_exp.so: tools/ab_*, the profiling scripts, the tests of the
 // alternative kernels) answers these look-ups from the environment; in the product build they fold to "unset".
@@ -147,6 +156,7 @@ public:
             cap_ = count;
         return rc;
     }
+    int alloc(const PlanBuf& b) { return alloc(b.n, b.zeroed); } // a buffer of a stage's launch plan
     // grow-only: nothing while `count` fits, else free and allocate ({nullptr, 0} is left behind on failure).  An empty
     // buffer allocates even for count == 0 (one element, as dev_alloc).  *fresh is set once it HAS allocated: the zero
     // fill runs on the null stream, the caller synchronises as it needs to

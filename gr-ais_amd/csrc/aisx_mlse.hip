@@ -25,10 +25,9 @@ __global__ __launch_bounds__(MLSE_T) void k_mlse_flush(MlseParams p)
 }
 
 struct aisx_mlse_batch {
+    explicit aisx_mlse_batch(const MlsePlan& plan) : pl(plan) {}
     int dev = 0;
-    int nchan = 0, max_syms = 0, groups = 0;
-    int cur = 0;              // which state / carry buffer the calls queued so far leave the channels in
-    MlseRot rot = {};
+    MlsePlan pl;              // the arguments, the sizes derived from them and the per-call sequence (k_mlse.h)
     DevBuf<MlseState> d_st[2];
     DevBuf<cf> d_carry[2];    // [nchan][MLSE_CARRY]
     DevBuf<int> d_flag;
@@ -50,25 +49,19 @@ extern "C" int aisx_mlse_batch_create(aisx_mlse_batch** out, double bt, int ncha
         return AISX_ERR_INVALID;
     *out = nullptr;
     MlseRot rot;
-    if (nchan < 1 || nchan > (1 << 20) || max_syms < 1 || max_syms > (1 << 27) || mlse_model(bt, nullptr, nullptr, &rot) != AISX_OK) {
-        set_err("aisx_mlse_batch_create: need 0.1 <= bt <= 1, 1 <= nchan <= 2^20 and 1 <= max_syms <= 2^27");
+    if (const char* why = MlsePlan::check(nchan, max_syms, mlse_model(bt, nullptr, nullptr, &rot) == AISX_OK)) {
+        set_err("aisx_mlse_batch_create: %s", why);
         return AISX_ERR_INVALID;
     }
     int rc = require_device();
     if (rc != AISX_OK)
         return rc;
-    HandlePtr<aisx_mlse_batch, aisx_mlse_batch_destroy> h(new aisx_mlse_batch());
+    HandlePtr<aisx_mlse_batch, aisx_mlse_batch_destroy> h(new aisx_mlse_batch(MlsePlan(rot, nchan, max_syms)));
     AISX_HIPCHK(hipGetDevice(&h->dev));
-    h->nchan = nchan;
-    h->max_syms = max_syms;
-    h->rot = rot;
-    // a call decides at most (max_syms + MLSE_B - 1) / MLSE_B blocks of a channel
-    const int blocks = (max_syms + MLSE_B - 1) / MLSE_B;
-    h->groups = std::max(1, (blocks + MLSE_T - 1) / MLSE_T);
     for (int k = 0; k < 2; k++)
-        if ((rc = h->d_st[k].alloc((size_t)nchan)) != AISX_OK || (rc = h->d_carry[k].alloc((size_t)nchan * MLSE_CARRY)) != AISX_OK)
+        if ((rc = h->d_st[k].alloc(h->pl.st)) != AISX_OK || (rc = h->d_carry[k].alloc(h->pl.carry)) != AISX_OK)
             return rc;
-    if ((rc = h->d_flag.alloc(1)) != AISX_OK || (rc = h->done.create(hipEventDisableTiming)) != AISX_OK)
+    if ((rc = h->d_flag.alloc(h->pl.flag)) != AISX_OK || (rc = h->done.create(hipEventDisableTiming)) != AISX_OK)
         return rc;
     AISX_HIPCHK(hipDeviceSynchronize()); // (the zero fill ran on the null stream)
     *out = h.release();
@@ -83,50 +76,43 @@ extern "C" int aisx_mlse_batch_reset(aisx_mlse_batch* h)
     AISX_HIPCHK(on.err);
     AISX_HIPCHK(hipEventSynchronize(h->done)); // (the last call's kernel; nothing else on the device)
     for (int k = 0; k < 2; k++)
-        AISX_HIPCHK(hipMemsetAsync(h->d_st[k], 0, sizeof(MlseState) * h->nchan, nullptr));
+        AISX_HIPCHK(hipMemsetAsync(h->d_st[k], 0, sizeof(MlseState) * h->pl.st.n, nullptr));
     AISX_HIPCHK(hipMemsetAsync(h->d_flag, 0, sizeof(int), nullptr));
     AISX_HIPCHK(hipStreamSynchronize(nullptr)); // (done before the next call, whatever stream that is queued on)
-    h->cur = 0;
+    h->pl.reset();
     return AISX_OK;
 }
 
-static MlseParams mlse_params(aisx_mlse_batch* h, uint8_t* d_bits, long bits_stride, int* d_nbits)
+// a call (d_syms == nullptr: the flush) queued on `st` by the handle's plan
+static int mlse_run(aisx_mlse_batch* h, const cf* d_syms, long syms_stride, const int* d_nsyms, uint8_t* d_bits, long bits_stride,
+                    int* d_nbits, hipStream_t st)
 {
-    MlseParams p = {};
-    p.max_syms = h->max_syms;
-    p.bits = d_bits;
-    p.bit_stride = bits_stride;
-    p.nbits = d_nbits;
-    p.st_in = h->d_st[h->cur];
-    p.st_out = h->d_st[h->cur ^ 1];
-    p.carry_in = h->d_carry[h->cur];
-    p.carry_out = h->d_carry[h->cur ^ 1];
-    p.flag = h->d_flag;
-    p.rot = h->rot;
-    return p;
+    const MlseBufs b = { { h->d_st[0], h->d_st[1] }, { h->d_carry[0], h->d_carry[1] }, h->d_flag };
+    hipError_t err = hipSuccess;
+    h->pl.process(b, d_syms, syms_stride, d_nsyms, d_bits, bits_stride, d_nbits, [&](const PlanLaunch& l, const MlseParams& p) {
+        if (l.kernel == MLSE_K_PROCESS)
+            hipLaunchKernelGGL(k_mlse, dim3(l.gx, l.gy), dim3(l.threads), 0, st, p);
+        else
+            hipLaunchKernelGGL(k_mlse_flush, dim3(l.gx, l.gy), dim3(l.threads), 0, st, p);
+        return (err = hipGetLastError()) == hipSuccess;
+    });
+    AISX_LAUNCHCHK(err);
+    AISX_HIPCHK(hipEventRecord(h->done, st));
+    return AISX_OK;
 }
 
 extern "C" int aisx_mlse_batch_process(aisx_mlse_batch* h, const aisx_cf32* d_syms, long syms_stride, const int* d_nsyms,
                                        uint8_t* d_bits, long bits_stride, int* d_nbits, void* stream)
 {
-    if (!h || !d_syms || !d_nsyms || !d_bits || !d_nbits || syms_stride < h->max_syms || bits_stride < (long)h->max_syms + MLSE_EXTRA ||
+    if (!h || !d_syms || !d_nsyms || !d_bits || !d_nbits || syms_stride < h->pl.max_syms || bits_stride < (long)h->pl.max_syms + MLSE_EXTRA ||
         ((size_t)d_syms & 7)) {
         set_err("aisx_mlse_batch_process: symbols (8-byte aligned) with a row stride of at least max_syms (%d), counts, and bits with a "
-                "row stride of at least max_syms + %d are needed", h ? h->max_syms : 0, MLSE_EXTRA);
+                "row stride of at least max_syms + %d are needed", h ? h->pl.max_syms : 0, MLSE_EXTRA);
         return AISX_ERR_INVALID;
     }
     OnDevice on(h->dev);
     AISX_HIPCHK(on.err);
-    const hipStream_t st = (hipStream_t)stream;
-    MlseParams p = mlse_params(h, d_bits, bits_stride, d_nbits);
-    p.syms = (const cf*)d_syms;
-    p.sym_stride = syms_stride;
-    p.nsyms = d_nsyms;
-    hipLaunchKernelGGL(k_mlse, dim3(h->nchan, h->groups), dim3(MLSE_T), 0, st, p);
-    AISX_HIPCHK(hipGetLastError());
-    AISX_HIPCHK(hipEventRecord(h->done, st));
-    h->cur ^= 1;
-    return AISX_OK;
+    return mlse_run(h, (const cf*)d_syms, syms_stride, d_nsyms, d_bits, bits_stride, d_nbits, (hipStream_t)stream);
 }
 
 extern "C" int aisx_mlse_batch_flush(aisx_mlse_batch* h, uint8_t* d_bits, long bits_stride, int* d_nbits, void* stream)
@@ -137,13 +123,7 @@ extern "C" int aisx_mlse_batch_flush(aisx_mlse_batch* h, uint8_t* d_bits, long b
     }
     OnDevice on(h->dev);
     AISX_HIPCHK(on.err);
-    const hipStream_t st = (hipStream_t)stream;
-    const MlseParams p = mlse_params(h, d_bits, bits_stride, d_nbits);
-    hipLaunchKernelGGL(k_mlse_flush, dim3(h->nchan, 1), dim3(MLSE_T), 0, st, p); // (at most two blocks of a channel are left)
-    AISX_HIPCHK(hipGetLastError());
-    AISX_HIPCHK(hipEventRecord(h->done, st));
-    h->cur ^= 1;
-    return AISX_OK;
+    return mlse_run(h, nullptr, 0, nullptr, d_bits, bits_stride, d_nbits, (hipStream_t)stream);
 }
 
 extern "C" int aisx_mlse_batch_status_device(const aisx_mlse_batch* h, const int** d_status)

@@ -22,8 +22,9 @@ __global__ __launch_bounds__(MSG_T) void k_msg(MsgParams p)
 }
 
 struct aisx_msg_batch {
+    explicit aisx_msg_batch(const MsgPlan& plan) : pl(plan) {}
     int dev = 0;
-    int nchan = 0, max_pdus = 0, lmax = 0, groups = 0;
+    const MsgPlan pl;        // the arguments, the sizes derived from them and the per-call sequence (k_msg.h)
     DevBuf<uint32_t> d_tab;  // [MSG_TAB_WORDS]
     DevBuf<int32_t> d_cols;  // [MSG_NCOL][max_pdus]
     DevBuf<uint32_t> d_strs; // [max_pdus][MSG_STR_WORDS]
@@ -44,22 +45,17 @@ extern "C" int aisx_msg_batch_create(aisx_msg_batch** out, int nchan, int max_pd
     if (!out)
         return AISX_ERR_INVALID;
     *out = nullptr;
-    if (nchan < 1 || max_pdus < 1 || length_max < 2 || length_max > MSG_MAX_OCTETS) {
-        set_err("aisx_msg_batch_create: need nchan >= 1, max_pdus >= 1, 2 <= length_max <= %d", MSG_MAX_OCTETS);
+    if (const char* why = MsgPlan::check(nchan, max_pdus, length_max)) {
+        set_err("aisx_msg_batch_create: %s", why);
         return AISX_ERR_INVALID;
     }
     int rc = require_device();
     if (rc != AISX_OK)
         return rc;
-    HandlePtr<aisx_msg_batch, aisx_msg_batch_destroy> h(new aisx_msg_batch());
+    HandlePtr<aisx_msg_batch, aisx_msg_batch_destroy> h(new aisx_msg_batch(MsgPlan(nchan, max_pdus, length_max)));
     AISX_HIPCHK(hipGetDevice(&h->dev));
-    h->nchan = nchan;
-    h->max_pdus = max_pdus;
-    h->lmax = length_max;
-    const long long groups = ((long long)max_pdus + MSG_T - 1) / MSG_T;
-    h->groups = (int)(groups < MSG_MAX_GROUPS ? groups : MSG_MAX_GROUPS);
-    if ((rc = h->d_tab.alloc((size_t)MSG_TAB_WORDS, false)) != AISX_OK || (rc = h->d_cols.alloc((size_t)MSG_NCOL * max_pdus, false)) != AISX_OK ||
-        (rc = h->d_strs.alloc((size_t)MSG_STR_WORDS * max_pdus, false)) != AISX_OK || (rc = h->d_count.alloc(4)) != AISX_OK)
+    if ((rc = h->d_tab.alloc(h->pl.tab)) != AISX_OK || (rc = h->d_cols.alloc(h->pl.cols)) != AISX_OK ||
+        (rc = h->d_strs.alloc(h->pl.strs)) != AISX_OK || (rc = h->d_count.alloc(h->pl.count)) != AISX_OK)
         return rc;
     if (hipMemcpy(h->d_tab, &MSG_TAB, sizeof(MsgTab), hipMemcpyHostToDevice) != hipSuccess) {
         set_err("aisx_msg_batch_create: copying the field table failed");
@@ -78,20 +74,11 @@ extern "C" int aisx_msg_batch_process(aisx_msg_batch* h, const aisx_pdu* d_pdus,
     }
     OnDevice on(h->dev);
     AISX_HIPCHK(on.err);
-    MsgParams p;
-    p.in = (const HdlcRec*)d_pdus;
-    p.bytes = d_bytes;
-    p.npdus = d_npdus;
-    p.nfound = d_nfound;
-    p.tab = h->d_tab;
-    p.nchan = h->nchan;
-    p.max_pdus = h->max_pdus;
-    p.max_len = h->lmax - 1;
-    p.nwaves = h->groups * (MSG_T / 64);
-    p.cols = h->d_cols;
-    p.strs = h->d_strs;
-    p.count = h->d_count;
-    hipLaunchKernelGGL(k_msg, dim3(h->groups), dim3(MSG_T), 0, (hipStream_t)stream, p);
+    const MsgBufs b = { h->d_tab, h->d_cols, h->d_strs, h->d_count };
+    h->pl.process(b, (const HdlcRec*)d_pdus, d_bytes, d_npdus, d_nfound, [&](const PlanLaunch& l, const MsgParams& p) {
+        hipLaunchKernelGGL(k_msg, dim3(l.gx), dim3(l.threads), 0, (hipStream_t)stream, p);
+        return true;
+    });
     AISX_HIPCHK(hipGetLastError());
     return AISX_OK;
 }
@@ -104,7 +91,7 @@ extern "C" int aisx_msg_batch_results_device(const aisx_msg_batch* h, const int3
     if (d_cols)
         *d_cols = h->d_cols;
     if (col_stride)
-        *col_stride = h->max_pdus;
+        *col_stride = h->pl.max_pdus;
     if (d_strs)
         *d_strs = (const char*)h->d_strs.get();
     if (d_count)
@@ -125,7 +112,7 @@ extern "C" int aisx_msg_batch_read(aisx_msg_batch* h, int32_t* cols, long col_st
     AISX_HIPCHK(hipStreamSynchronize(st));
     const int k = cnt[1] < cap ? cnt[1] : cap;
     if (k > 0) {
-        AISX_HIPCHK(hipMemcpy2DAsync(cols, sizeof(int32_t) * (size_t)col_stride, h->d_cols, sizeof(int32_t) * (size_t)h->max_pdus,
+        AISX_HIPCHK(hipMemcpy2DAsync(cols, sizeof(int32_t) * (size_t)col_stride, h->d_cols, sizeof(int32_t) * (size_t)h->pl.max_pdus,
                                      sizeof(int32_t) * (size_t)k, MSG_NCOL, hipMemcpyDeviceToHost, st));
         AISX_HIPCHK(hipMemcpyAsync(strs, h->d_strs, (size_t)MSG_STR * k, hipMemcpyDeviceToHost, st));
     }
@@ -137,7 +124,7 @@ extern "C" int aisx_msg_batch_read(aisx_msg_batch* h, int32_t* cols, long col_st
         *nfound = cnt[0];
     if (cnt[2]) {
         set_err("aisx_msg_batch_read: a call since the last read met a record count outside [0, %d], a channel outside "
-                "[0, %d) or a payload longer than %d octets: those rows hold no fields", h->max_pdus, h->nchan, h->lmax - 1);
+                "[0, %d) or a payload longer than %d octets: those rows hold no fields", h->pl.max_pdus, h->pl.nchan, h->pl.lmax - 1);
         return AISX_ERR_INVALID;
     }
     if (k < cnt[0]) {

@@ -1,10 +1,6 @@
 // aisx_nmea.hip -- C ABI of the batched NMEA armouring (include/aisx.h, aisx_nmea_batch_*): per call, one workgroup
 // sizes and places every record's text (k_nmea.h: nmea_scan_body) and one wave per record writes it
 // (nmea_write_body).  Everything is queued on the caller's stream; the record count is read on the device.
-#include <string.h>
-
-#include <vector>
-
 #include "aisx_devctx.h"
 #include "aisx_host.h"
 #include "k_nmea.h"
@@ -27,9 +23,9 @@ __global__ __launch_bounds__(NM_W_T) void k_nmea_write(NmeaWriteParams p)
 }
 
 struct aisx_nmea_batch {
+    explicit aisx_nmea_batch(NmeaPlan&& plan) : pl(std::move(plan)) {}
     int dev = 0;
-    int nchan = 0, max_pdus = 0, lmax = 0, write_groups = 0;
-    long long text_cap = 0;
+    const NmeaPlan pl;            // the arguments, the sizes derived from them and the per-call sequence (k_nmea.h)
     DevBuf<char> d_desig;         // [nchan][NM_DESIG]
     DevBuf<unsigned char> d_dlen; // [nchan]
     DevBuf<HdlcRec> d_out;        // [max_pdus]
@@ -52,45 +48,26 @@ extern "C" int aisx_nmea_batch_create(aisx_nmea_batch** out, const char* const* 
     if (!out)
         return AISX_ERR_INVALID;
     *out = nullptr;
-    if (!designators || nchan < 1 || max_pdus < 1 || length_max < 2 || length_max > NM_MAX_OCTETS || text_cap < 0) {
-        set_err("aisx_nmea_batch_create: need designators, nchan >= 1, max_pdus >= 1, 2 <= length_max <= %d, "
-                "text_cap >= 0", NM_MAX_OCTETS);
+    if (const char* why = NmeaPlan::check(designators, nchan, max_pdus, length_max, text_cap)) {
+        set_err("aisx_nmea_batch_create: %s", why);
         return AISX_ERR_INVALID;
     }
-    int max_dlen = 0;
-    for (int c = 0; c < nchan; c++) {
-        const size_t n = designators[c] ? strnlen(designators[c], NM_DESIG + 1) : NM_DESIG + 1;
-        if (n > (size_t)NM_DESIG) {
-            set_err("aisx_nmea_batch_create: designator %d is missing or longer than %d bytes", c, NM_DESIG);
-            return AISX_ERR_INVALID;
-        }
-        max_dlen = (int)n > max_dlen ? (int)n : max_dlen;
+    if (const int c = nm_bad_designator(designators, nchan); c >= 0) {
+        set_err("aisx_nmea_batch_create: designator %d is missing or longer than %d bytes", c, NM_DESIG);
+        return AISX_ERR_INVALID;
     }
     int rc = require_device();
     if (rc != AISX_OK)
         return rc;
-    HandlePtr<aisx_nmea_batch, aisx_nmea_batch_destroy> h(new aisx_nmea_batch());
+    HandlePtr<aisx_nmea_batch, aisx_nmea_batch_destroy> h(new aisx_nmea_batch(NmeaPlan(designators, nchan, max_pdus, length_max, text_cap)));
     AISX_HIPCHK(hipGetDevice(&h->dev));
-    h->nchan = nchan;
-    h->max_pdus = max_pdus;
-    h->lmax = length_max;
-    // the worst case: every record as long as a payload can be, on the channel with the longest designator
-    const long long worst = (long long)max_pdus * (nm_text_len(length_max - 1, max_dlen) + 1);
-    h->text_cap = text_cap == 0 || text_cap > worst ? worst : text_cap;
-    const long long groups = ((long long)max_pdus + NM_W_T / 64 - 1) / (NM_W_T / 64);
-    h->write_groups = (int)(groups < NM_W_MAX_GROUPS ? groups : NM_W_MAX_GROUPS);
-    std::vector<char> desig((size_t)nchan * NM_DESIG, 0);
-    std::vector<unsigned char> dlen(nchan);
-    for (int c = 0; c < nchan; c++) {
-        dlen[c] = (unsigned char)strlen(designators[c]);
-        memcpy(desig.data() + (size_t)c * NM_DESIG, designators[c], dlen[c]);
-    }
-    if ((rc = h->d_desig.alloc((size_t)nchan * NM_DESIG, false)) != AISX_OK || (rc = h->d_dlen.alloc((size_t)nchan, false)) != AISX_OK ||
-        (rc = h->d_out.alloc((size_t)max_pdus, false)) != AISX_OK || (rc = h->d_text.alloc((size_t)h->text_cap, false)) != AISX_OK ||
-        (rc = h->d_count.alloc(4)) != AISX_OK)
+    const NmeaPlan& pl = h->pl;
+    if ((rc = h->d_desig.alloc(pl.desig)) != AISX_OK || (rc = h->d_dlen.alloc(pl.dlen)) != AISX_OK ||
+        (rc = h->d_out.alloc(pl.out)) != AISX_OK || (rc = h->d_text.alloc(pl.text)) != AISX_OK ||
+        (rc = h->d_count.alloc(pl.count)) != AISX_OK)
         return rc;
-    if (hipMemcpy(h->d_desig, desig.data(), desig.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(h->d_dlen, dlen.data(), dlen.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    if (hipMemcpy(h->d_desig, pl.desig_host.data(), pl.desig.n, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(h->d_dlen, pl.dlen_host.data(), pl.dlen.n, hipMemcpyHostToDevice) != hipSuccess) {
         set_err("aisx_nmea_batch_create: copying the designators failed");
         return AISX_ERR_HIP;
     }
@@ -108,30 +85,16 @@ extern "C" int aisx_nmea_batch_process(aisx_nmea_batch* h, const aisx_pdu* d_pdu
     OnDevice on(h->dev);
     AISX_HIPCHK(on.err);
     const hipStream_t st = (hipStream_t)stream;
-    NmeaScanParams s;
-    s.in = (const HdlcRec*)d_pdus;
-    s.npdus = d_npdus;
-    s.nfound = d_nfound;
-    s.dlen = h->d_dlen;
-    s.nchan = h->nchan;
-    s.max_pdus = h->max_pdus;
-    s.max_len = h->lmax - 1;
-    s.text_cap = h->text_cap;
-    s.out = h->d_out;
-    s.count = h->d_count;
-    hipLaunchKernelGGL(k_nmea_scan, dim3(1), dim3(NM_SCAN_T), 0, st, s);
-    AISX_HIPCHK(hipGetLastError());
-    NmeaWriteParams w;
-    w.in = s.in;
-    w.bytes = d_bytes;
-    w.out = h->d_out;
-    w.count = h->d_count;
-    w.desig = h->d_desig;
-    w.dlen = h->d_dlen;
-    w.text = h->d_text;
-    w.nwaves = h->write_groups * (NM_W_T / 64);
-    hipLaunchKernelGGL(k_nmea_write, dim3(h->write_groups), dim3(NM_W_T), 0, st, w);
-    AISX_HIPCHK(hipGetLastError());
+    const NmeaBufs b = { h->d_desig, h->d_dlen, h->d_out, h->d_text, h->d_count };
+    hipError_t err = hipSuccess;
+    h->pl.process(b, (const HdlcRec*)d_pdus, d_bytes, d_npdus, d_nfound, [&](const PlanLaunch& l, const NmeaCall& c) {
+        if (l.kernel == NM_K_SCAN)
+            hipLaunchKernelGGL(k_nmea_scan, dim3(l.gx), dim3(l.threads), 0, st, c.s);
+        else
+            hipLaunchKernelGGL(k_nmea_write, dim3(l.gx), dim3(l.threads), 0, st, c.w);
+        return (err = hipGetLastError()) == hipSuccess;
+    });
+    AISX_LAUNCHCHK(err);
     return AISX_OK;
 }
 
@@ -179,7 +142,7 @@ extern "C" int aisx_nmea_batch_read(aisx_nmea_batch* h, aisx_pdu* recs, int rec_
         *nfound = cnt[0];
     if (cnt[2]) {
         set_err("aisx_nmea_batch_read: a call since the last read met a record count outside [0, %d], a channel "
-                "outside [0, %d) or a payload longer than %d octets: those gave no text", h->max_pdus, h->nchan, h->lmax - 1);
+                "outside [0, %d) or a payload longer than %d octets: those gave no text", h->pl.max_pdus, h->pl.nchan, h->pl.lmax - 1);
         return AISX_ERR_INVALID;
     }
     if (k < cnt[0]) {

@@ -3,8 +3,6 @@
 // the handle carries from call to call.
 #include <string.h>
 
-#include <vector>
-
 #include "aisx_devctx.h"
 #include "aisx_host.h"
 #include "k_nmea_parse.h"
@@ -13,6 +11,7 @@ using namespace aisx;
 
 static_assert(sizeof(HdlcRec) == sizeof(aisx_pdu), "pdu record layout");
 static_assert(NP_NCNT == AISX_NMEAP_NCNT, "counts layout");
+static_assert(AISX_NMEA_PARSE_REF_TAIL == 1, "the flag NmpPlan::check takes");
 
 #define NMP_KERNEL(name, threads, call)                                              \
     __global__ __launch_bounds__(threads) void name(NmpParams p)                    \
@@ -35,10 +34,9 @@ NMP_KERNEL(k_nmp_write, NP_T, nmp_write_body(cx, p))
 NMP_KERNEL(k_nmp_carry, 64, nmp_carry_body(cx, p))
 
 struct aisx_nmea_parse_batch {
+    explicit aisx_nmea_parse_batch(NmpPlan&& plan) : pl(std::move(plan)) {}
     int dev = 0;
-    int nchan = 0, lmax = 0, max_line = 0, flags = 0, max_lines = 0, max_pdus = 0;
-    long long max_bytes = 0;
-    int tile_groups = 0, line_groups = 0, pdu_groups = 0, ltile_groups = 0;
+    const NmpPlan pl; // the arguments, the sizes derived from them and the per-call sequence (k_nmea_parse.h)
     DevBuf<char> d_desig;
     DevBuf<unsigned char> d_dlen, d_lcarry, d_gcarry, d_bytes;
     DevBuf<NmpState> d_st;
@@ -66,62 +64,36 @@ extern "C" int aisx_nmea_parse_batch_create(aisx_nmea_parse_batch** out, const c
     if (!out)
         return AISX_ERR_INVALID;
     *out = nullptr;
-    if (!designators || nchan < 1 || length_max < 2 || length_max > NM_MAX_OCTETS || max_line < 64 || max_line > 4096 ||
-        (flags & ~AISX_NMEA_PARSE_REF_TAIL) || max_bytes < 1 || max_bytes > (1l << 30) || max_lines < 1 ||
-        max_lines > (1 << 26) || max_pdus < 1) {
-        set_err("aisx_nmea_parse_batch_create: need designators, nchan >= 1, 2 <= length_max <= %d, 64 <= max_line <= 4096, "
-                "flags 0 or 1, 1 <= max_bytes <= 2^30, 1 <= max_lines <= 2^26, max_pdus >= 1", NM_MAX_OCTETS);
+    if (const char* why = NmpPlan::check(designators, nchan, length_max, max_line, flags, max_bytes, max_lines, max_pdus)) {
+        set_err("aisx_nmea_parse_batch_create: %s", why);
         return AISX_ERR_INVALID;
     }
-    for (int c = 0; c < nchan; c++)
-        if (!designators[c] || strnlen(designators[c], NM_DESIG + 1) > (size_t)NM_DESIG) {
-            set_err("aisx_nmea_parse_batch_create: designator %d is missing or longer than %d bytes", c, NM_DESIG);
-            return AISX_ERR_INVALID;
-        }
+    if (const int c = nm_bad_designator(designators, nchan); c >= 0) {
+        set_err("aisx_nmea_parse_batch_create: designator %d is missing or longer than %d bytes", c, NM_DESIG);
+        return AISX_ERR_INVALID;
+    }
     int rc = require_device();
     if (rc != AISX_OK)
         return rc;
-    HandlePtr<aisx_nmea_parse_batch, aisx_nmea_parse_batch_destroy> h(new aisx_nmea_parse_batch());
+    HandlePtr<aisx_nmea_parse_batch, aisx_nmea_parse_batch_destroy> h(
+        new aisx_nmea_parse_batch(NmpPlan(designators, nchan, length_max, max_line, flags, max_bytes, max_lines, max_pdus)));
     AISX_HIPCHK(hipGetDevice(&h->dev));
-    h->nchan = nchan;
-    h->lmax = length_max;
-    h->max_line = max_line;
-    h->flags = flags;
-    h->max_bytes = max_bytes;
-    h->max_lines = max_lines;
-    h->max_pdus = max_pdus;
-    auto groups = [](long long items, int per_group) {
-        const long long g = (items + per_group - 1) / per_group;
-        return (int)(g < 1 ? 1 : g < NP_MAX_GROUPS ? g : NP_MAX_GROUPS);
-    };
-    const long long ntiles = (max_bytes + NP_T * NP_CHUNK - 1) / (NP_T * NP_CHUNK);
-    h->tile_groups = groups(ntiles, 1);
-    h->line_groups = groups(max_lines, NP_T / 64);
-    h->pdu_groups = groups(max_pdus, NP_T / 64);
-    const size_t nlt = ((size_t)max_lines + NP_GMAX + NP_T - 1) / NP_T; // tiles of lines / sentences
-    h->ltile_groups = groups((long long)nlt, 1);
-    std::vector<char> desig((size_t)nchan * NM_DESIG, 0);
-    std::vector<unsigned char> dlen(nchan);
-    for (int c = 0; c < nchan; c++) {
-        dlen[c] = (unsigned char)strlen(designators[c]);
-        memcpy(desig.data() + (size_t)c * NM_DESIG, designators[c], dlen[c]);
-    }
-    const size_t nl = (size_t)max_lines, np = (size_t)max_pdus;
-    if ((rc = h->d_desig.alloc(desig.size(), false)) != AISX_OK || (rc = h->d_dlen.alloc(dlen.size(), false)) != AISX_OK ||
-        (rc = h->d_lcarry.alloc(2 * (size_t)max_line)) != AISX_OK || (rc = h->d_gcarry.alloc(2 * (size_t)NP_GMAX * max_line)) != AISX_OK ||
-        (rc = h->d_bytes.alloc(np * (size_t)(length_max - 1), false)) != AISX_OK || (rc = h->d_st.alloc(2)) != AISX_OK ||
-        (rc = h->d_tcount.alloc((size_t)ntiles, false)) != AISX_OK || (rc = h->d_toff.alloc((size_t)ntiles, false)) != AISX_OK ||
-        (rc = h->d_meta.alloc(NP_M_N)) != AISX_OK || (rc = h->d_cidx.alloc(nl, false)) != AISX_OK ||
-        (rc = h->d_aux.alloc(np, false)) != AISX_OK || (rc = h->d_count.alloc(NP_NCNT)) != AISX_OK ||
-        (rc = h->d_lend.alloc(nl, false)) != AISX_OK || (rc = h->d_pos.alloc(nl, false)) != AISX_OK ||
-        (rc = h->d_tm.alloc(nl, false)) != AISX_OK || (rc = h->d_times.alloc(np, false)) != AISX_OK ||
-        (rc = h->d_key.alloc(nl, false)) != AISX_OK || (rc = h->d_rec.alloc(np, false)) != AISX_OK ||
-        (rc = h->d_next.alloc(1)) != AISX_OK || (rc = h->d_mlen.alloc(nl + NP_GMAX, false)) != AISX_OK ||
-        (rc = h->d_tl.alloc(nlt, false)) != AISX_OK || (rc = h->d_tlb.alloc(nlt, false)) != AISX_OK ||
-        (rc = h->d_bstat.alloc((size_t)NP_MAX_GROUPS * 8)) != AISX_OK)
+    const NmpPlan& pl = h->pl;
+    if ((rc = h->d_desig.alloc(pl.desig)) != AISX_OK || (rc = h->d_dlen.alloc(pl.dlen)) != AISX_OK ||
+        (rc = h->d_lcarry.alloc(pl.lcarry)) != AISX_OK || (rc = h->d_gcarry.alloc(pl.gcarry)) != AISX_OK ||
+        (rc = h->d_bytes.alloc(pl.bytes)) != AISX_OK || (rc = h->d_st.alloc(pl.st)) != AISX_OK ||
+        (rc = h->d_tcount.alloc(pl.tcount)) != AISX_OK || (rc = h->d_toff.alloc(pl.toff)) != AISX_OK ||
+        (rc = h->d_meta.alloc(pl.meta)) != AISX_OK || (rc = h->d_cidx.alloc(pl.cidx)) != AISX_OK ||
+        (rc = h->d_aux.alloc(pl.aux)) != AISX_OK || (rc = h->d_count.alloc(pl.count)) != AISX_OK ||
+        (rc = h->d_lend.alloc(pl.lend)) != AISX_OK || (rc = h->d_pos.alloc(pl.pos)) != AISX_OK ||
+        (rc = h->d_tm.alloc(pl.tm)) != AISX_OK || (rc = h->d_times.alloc(pl.times)) != AISX_OK ||
+        (rc = h->d_key.alloc(pl.key)) != AISX_OK || (rc = h->d_rec.alloc(pl.rec)) != AISX_OK ||
+        (rc = h->d_next.alloc(pl.next)) != AISX_OK || (rc = h->d_mlen.alloc(pl.mlen)) != AISX_OK ||
+        (rc = h->d_tl.alloc(pl.tl)) != AISX_OK || (rc = h->d_tlb.alloc(pl.tlb)) != AISX_OK ||
+        (rc = h->d_bstat.alloc(pl.bstat)) != AISX_OK)
         return rc;
-    if (hipMemcpy(h->d_desig, desig.data(), desig.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(h->d_dlen, dlen.data(), dlen.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    if (hipMemcpy(h->d_desig, pl.desig_host.data(), pl.desig.n, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(h->d_dlen, pl.dlen_host.data(), pl.dlen.n, hipMemcpyHostToDevice) != hipSuccess) {
         set_err("aisx_nmea_parse_batch_create: copying the designators failed");
         return AISX_ERR_HIP;
     }
@@ -136,9 +108,9 @@ extern "C" int aisx_nmea_parse_batch_reset(aisx_nmea_parse_batch* h)
     OnDevice on(h->dev);
     AISX_HIPCHK(on.err);
     AISX_HIPCHK(hipDeviceSynchronize());
-    AISX_HIPCHK(hipMemset(h->d_st, 0, 2 * sizeof(NmpState)));
-    AISX_HIPCHK(hipMemset(h->d_meta, 0, NP_M_N * sizeof(int)));
-    AISX_HIPCHK(hipMemset(h->d_count, 0, NP_NCNT * sizeof(int)));
+    AISX_HIPCHK(hipMemset(h->d_st, 0, h->pl.st.n * sizeof(NmpState)));
+    AISX_HIPCHK(hipMemset(h->d_meta, 0, h->pl.meta.n * sizeof(int)));
+    AISX_HIPCHK(hipMemset(h->d_count, 0, h->pl.count.n * sizeof(int)));
     return AISX_OK;
 }
 
@@ -152,57 +124,18 @@ extern "C" int aisx_nmea_parse_batch_process(aisx_nmea_parse_batch* h, const cha
     OnDevice on(h->dev);
     AISX_HIPCHK(on.err);
     const hipStream_t st = (hipStream_t)stream;
-    NmpParams p;
-    p.text = (const unsigned char*)d_text;
-    p.nbytes = d_nbytes;
-    p.max_bytes = h->max_bytes;
-    p.max_lines = h->max_lines;
-    p.max_pdus = h->max_pdus;
-    p.max_len = h->lmax - 1;
-    p.max_line = h->max_line;
-    p.flags = h->flags;
-    p.nchan = h->nchan;
-    p.desig = h->d_desig;
-    p.dlen = h->d_dlen;
-    p.st = h->d_st;
-    p.lcarry = h->d_lcarry;
-    p.gcarry = h->d_gcarry;
-    p.tcount = h->d_tcount;
-    p.toff = h->d_toff;
-    p.meta = h->d_meta;
-    p.lend = h->d_lend;
-    p.key = h->d_key;
-    p.pos = h->d_pos;
-    p.tm = h->d_tm;
-    p.cidx = h->d_cidx;
-    p.mlen = h->d_mlen;
-    p.tl = h->d_tl;
-    p.tlb = h->d_tlb;
-    p.bstat = h->d_bstat;
-    p.rec = h->d_rec;
-    p.aux = h->d_aux;
-    p.times = h->d_times;
-    p.bytes = h->d_bytes;
-    p.count = h->d_count;
-    p.next = h->d_next;
-    p.ngroups = h->tile_groups;
-    p.nwaves = h->line_groups * (NP_T / 64);
-    hipLaunchKernelGGL(k_nmp_count, dim3(h->tile_groups), dim3(NP_T), 0, st, p);
-    hipLaunchKernelGGL(k_nmp_scan, dim3(1), dim3(NP_SCAN_T), 0, st, p);
-    hipLaunchKernelGGL(k_nmp_index, dim3(h->tile_groups), dim3(NP_T), 0, st, p);
-    hipLaunchKernelGGL(k_nmp_parse, dim3(h->line_groups), dim3(NP_T), 0, st, p);
-    p.ngroups = h->ltile_groups;
-    hipLaunchKernelGGL(k_nmp_gcount, dim3(h->ltile_groups), dim3(NP_T), 0, st, p);
-    hipLaunchKernelGGL(k_nmp_gscan1, dim3(1), dim3(NP_SCAN_T), 0, st, p);
-    hipLaunchKernelGGL(k_nmp_gcompact, dim3(h->ltile_groups), dim3(NP_T), 0, st, p);
-    hipLaunchKernelGGL(k_nmp_gmsg, dim3(h->ltile_groups), dim3(NP_T), 0, st, p);
-    hipLaunchKernelGGL(k_nmp_gscan2, dim3(1), dim3(NP_SCAN_T), 0, st, p);
-    hipLaunchKernelGGL(k_nmp_gplace, dim3(h->ltile_groups), dim3(NP_T), 0, st, p);
-    AISX_HIPCHK(hipGetLastError());
-    p.nwaves = h->pdu_groups * (NP_T / 64);
-    hipLaunchKernelGGL(k_nmp_write, dim3(h->pdu_groups), dim3(NP_T), 0, st, p);
-    hipLaunchKernelGGL(k_nmp_carry, dim3(1), dim3(64), 0, st, p);
-    AISX_HIPCHK(hipGetLastError());
+    const NmpBufs b = { h->d_desig, h->d_dlen, h->d_st,  h->d_lcarry, h->d_gcarry, h->d_tcount, h->d_toff, h->d_meta,
+                        h->d_lend,  h->d_key,  h->d_pos, h->d_tm,     h->d_cidx,   h->d_mlen,   h->d_tl,   h->d_tlb,
+                        h->d_bstat, h->d_rec,  h->d_aux, h->d_times,  h->d_bytes,  h->d_count,  h->d_next };
+    hipError_t err = hipSuccess;
+    h->pl.process(b, (const unsigned char*)d_text, d_nbytes, [&](const PlanLaunch& l, const NmpParams& p) {
+        static void (*const kernels[NP_NKERNELS])(NmpParams) = { k_nmp_count,    k_nmp_scan, k_nmp_index,  k_nmp_parse,  k_nmp_gcount, k_nmp_gscan1,
+                                                                  k_nmp_gcompact, k_nmp_gmsg, k_nmp_gscan2, k_nmp_gplace, k_nmp_write,  k_nmp_carry };
+        hipLaunchKernelGGL(kernels[l.kernel], dim3(l.gx), dim3(l.threads), 0, st, p);
+        // (checked behind the last kernel of the lines and sentences, and behind the last of all)
+        return (l.kernel != NP_K_GPLACE && l.kernel != NP_K_CARRY) || (err = hipGetLastError()) == hipSuccess;
+    });
+    AISX_LAUNCHCHK(err);
     return AISX_OK;
 }
 
@@ -251,7 +184,7 @@ extern "C" int aisx_nmea_parse_batch_read(aisx_nmea_parse_batch* h, aisx_pdu* pd
     memcpy(counts, cnt, sizeof cnt);
     if (cnt[AISX_NMEAP_BAD_INPUT]) {
         set_err("aisx_nmea_parse_batch_read: a call since the last read had a byte count outside [0, %lld] or more than %d "
-                "line ends: it was refused and advanced nothing", h->max_bytes, h->max_lines);
+                "line ends: it was refused and advanced nothing", h->pl.max_bytes, h->pl.max_lines);
         return AISX_ERR_INVALID;
     }
     if (k < cnt[AISX_NMEAP_FOUND]) {

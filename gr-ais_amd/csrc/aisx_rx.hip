@@ -271,13 +271,9 @@ extern "C" int aisx_rx_create(aisx_rx** out, double rate, int nstreams, int ncha
         return AISX_ERR_INVALID;
     }
     int max_dlen = 0;
-    for (int c = 0; c < nchan_per_stream; c++) {
-        const size_t n = designators[c] ? strnlen(designators[c], NM_DESIG + 1) : NM_DESIG + 1;
-        if (n > (size_t)NM_DESIG) {
-            set_err("aisx_rx_create: designator %d is missing or longer than %d bytes", c, NM_DESIG);
-            return AISX_ERR_INVALID;
-        }
-        max_dlen = (int)n > max_dlen ? (int)n : max_dlen;
+    if (const int c = nm_bad_designator(designators, nchan_per_stream, &max_dlen); c >= 0) {
+        set_err("aisx_rx_create: designator %d is missing or longer than %d bytes", c, NM_DESIG);
+        return AISX_ERR_INVALID;
     }
     std::vector<float> own;
     if (!taps) {

@@ -39,9 +39,9 @@ __global__ __launch_bounds__(TRK_T) void k_trk_compact(TrkParams p, int32_t min_
 }
 
 struct aisx_track_batch {
+    explicit aisx_track_batch(const TrkPlan& plan) : pl(plan) {}
     int dev = 0;
-    int capacity = 0, max_rows = 0, hbits = 0, bbits = 0, row_groups = 0, cap_groups = 0, clear_groups = 0;
-    int cur = 0;                 // which table buffer the calls queued so far leave the table in
+    TrkPlan pl;                  // the arguments, the sizes derived from them and the per-call sequences (k_track.h)
     DevBuf<int32_t> d_tab[2];    // [TRK_NCOL][capacity]
     DevBuf<uint32_t> d_strs[2];  // [capacity][MSG_STR_WORDS]
     DevBuf<int32_t> d_hkey;      // [1 << hbits]
@@ -57,28 +57,28 @@ struct aisx_track_batch {
     DevBuf<int> d_count;         // [TRK_COUNT_WORDS]
 };
 
-static TrkParams trk_params(const aisx_track_batch* h)
+static TrkBufs trk_bufs(const aisx_track_batch* h)
 {
-    TrkParams p = {};
-    p.capacity = h->capacity;
-    p.max_rows = h->max_rows;
-    p.tab = h->d_tab[h->cur];
-    p.strs = h->d_strs[h->cur];
-    p.hkey = h->d_hkey;
-    p.hval = h->d_hval;
-    p.hbits = h->hbits;
-    p.bkey = h->d_bkey;
-    p.bfirst = h->d_bfirst;
-    p.bval = h->d_bval;
-    p.bj = h->d_bj;
-    p.bbits = h->bbits;
-    p.rslot = h->d_rslot;
-    p.bsum = h->d_bsum;
-    p.nbmax = std::max(h->row_groups, h->cap_groups);
-    p.win = h->d_win;
-    p.changed = h->d_changed;
-    p.count = h->d_count;
-    return p;
+    return TrkBufs{ { h->d_tab[0], h->d_tab[1] }, { h->d_strs[0], h->d_strs[1] }, h->d_hkey, h->d_hval, h->d_bkey, h->d_bfirst,
+                    h->d_bval, h->d_bj, h->d_rslot, h->d_bsum, h->d_win, h->d_changed, h->d_gcols, h->d_gstrs, h->d_count };
+}
+
+// a launch of the plan's on `st`: the kernel of its id
+static bool trk_launch(const PlanLaunch& l, const TrkCall& c, hipStream_t st)
+{
+    const dim3 grid(l.gx), threads(l.threads);
+    switch (l.kernel) {
+    case TRK_K_CLEAR: hipLaunchKernelGGL(k_trk_clear, grid, threads, 0, st, c.p); break;
+    case TRK_K_FIND: hipLaunchKernelGGL(k_trk_find, grid, threads, 0, st, c.p); break;
+    case TRK_K_CLASSIFY: hipLaunchKernelGGL(k_trk_classify, grid, threads, 0, st, c.p); break;
+    case TRK_K_ASSIGN: hipLaunchKernelGGL(k_trk_assign, grid, threads, 0, st, c.p); break;
+    case TRK_K_WINNER: hipLaunchKernelGGL(k_trk_winner, grid, threads, 0, st, c.p); break;
+    case TRK_K_APPLY: hipLaunchKernelGGL(k_trk_apply, grid, threads, 0, st, c.p); break;
+    case TRK_K_KEEP: hipLaunchKernelGGL(k_trk_keep, grid, threads, 0, st, c.p, c.min_stamp); break;
+    case TRK_K_COMPACT: hipLaunchKernelGGL(k_trk_compact, grid, threads, 0, st, c.p, c.min_stamp); break;
+    case TRK_K_GATHER: hipLaunchKernelGGL(k_trk_gather, grid, threads, 0, st, c.p); break;
+    }
+    return true;
 }
 
 extern "C" int aisx_track_batch_destroy(aisx_track_batch* h)
@@ -94,10 +94,10 @@ extern "C" int aisx_track_batch_destroy(aisx_track_batch* h)
 static int trk_empty(aisx_track_batch* h)
 {
     AISX_HIPCHK(hipDeviceSynchronize());
-    AISX_HIPCHK(hipMemsetD32(h->d_hkey, TRK_EMPTY, (size_t)1 << h->hbits));
+    AISX_HIPCHK(hipMemsetD32(h->d_hkey, TRK_EMPTY, h->pl.hkey.n));
     AISX_HIPCHK(hipMemset(h->d_count, 0, sizeof(int) * TRK_COUNT_WORDS));
     AISX_HIPCHK(hipDeviceSynchronize());
-    h->cur = 0;
+    h->pl.reset();
     return AISX_OK;
 }
 
@@ -106,34 +106,26 @@ extern "C" int aisx_track_batch_create(aisx_track_batch** out, int capacity, int
     if (!out)
         return AISX_ERR_INVALID;
     *out = nullptr;
-    if (capacity < 1 || capacity > TRK_MAX || max_rows < 1 || max_rows > TRK_MAX) {
-        set_err("aisx_track_batch_create: need 1 <= capacity <= %d and 1 <= max_rows <= %d", TRK_MAX, TRK_MAX);
+    if (const char* why = TrkPlan::check(capacity, max_rows)) {
+        set_err("aisx_track_batch_create: %s", why);
         return AISX_ERR_INVALID;
     }
     int rc = require_device();
     if (rc != AISX_OK)
         return rc;
-    HandlePtr<aisx_track_batch, aisx_track_batch_destroy> h(new aisx_track_batch());
+    HandlePtr<aisx_track_batch, aisx_track_batch_destroy> h(new aisx_track_batch(TrkPlan(capacity, max_rows)));
     AISX_HIPCHK(hipGetDevice(&h->dev));
-    h->capacity = capacity;
-    h->max_rows = max_rows;
-    h->hbits = trk_hash_bits(capacity);
-    h->bbits = trk_hash_bits(max_rows);
-    h->row_groups = (max_rows + TRK_T - 1) / TRK_T;
-    h->cap_groups = (capacity + TRK_T - 1) / TRK_T;
-    h->clear_groups = std::min(h->row_groups, 1024);
-    const size_t H = (size_t)1 << h->hbits, B = (size_t)1 << h->bbits, R = (size_t)max_rows, C = (size_t)capacity;
+    const TrkPlan& pl = h->pl;
     for (int k = 0; k < 2; k++)
-        if ((rc = h->d_tab[k].alloc(TRK_NCOL * C, false)) != AISX_OK || (rc = h->d_strs[k].alloc(MSG_STR_WORDS * C, false)) != AISX_OK)
+        if ((rc = h->d_tab[k].alloc(pl.tab)) != AISX_OK || (rc = h->d_strs[k].alloc(pl.strs)) != AISX_OK)
             return rc;
-    if ((rc = h->d_hkey.alloc(H, false)) != AISX_OK || (rc = h->d_hval.alloc(H, false)) != AISX_OK ||
-        (rc = h->d_bkey.alloc(B, false)) != AISX_OK || (rc = h->d_bfirst.alloc(B, false)) != AISX_OK ||
-        (rc = h->d_bval.alloc(B, false)) != AISX_OK || (rc = h->d_bj.alloc(B, false)) != AISX_OK ||
-        (rc = h->d_rslot.alloc(R, false)) != AISX_OK ||
-        (rc = h->d_bsum.alloc(2 * (size_t)std::max(h->row_groups, h->cap_groups), false)) != AISX_OK ||
-        (rc = h->d_win.alloc(TRK_NWIN * R, false)) != AISX_OK || (rc = h->d_changed.alloc(R, false)) != AISX_OK ||
-        (rc = h->d_gcols.alloc(TRK_NCOL * R, false)) != AISX_OK || (rc = h->d_gstrs.alloc(MSG_STR_WORDS * R, false)) != AISX_OK ||
-        (rc = h->d_count.alloc(TRK_COUNT_WORDS)) != AISX_OK || (rc = trk_empty(h.get())) != AISX_OK)
+    if ((rc = h->d_hkey.alloc(pl.hkey)) != AISX_OK || (rc = h->d_hval.alloc(pl.hval)) != AISX_OK ||
+        (rc = h->d_bkey.alloc(pl.bkey)) != AISX_OK || (rc = h->d_bfirst.alloc(pl.bfirst)) != AISX_OK ||
+        (rc = h->d_bval.alloc(pl.bval)) != AISX_OK || (rc = h->d_bj.alloc(pl.bj)) != AISX_OK ||
+        (rc = h->d_rslot.alloc(pl.rslot)) != AISX_OK || (rc = h->d_bsum.alloc(pl.bsum)) != AISX_OK ||
+        (rc = h->d_win.alloc(pl.win)) != AISX_OK || (rc = h->d_changed.alloc(pl.changed)) != AISX_OK ||
+        (rc = h->d_gcols.alloc(pl.gcols)) != AISX_OK || (rc = h->d_gstrs.alloc(pl.gstrs)) != AISX_OK ||
+        (rc = h->d_count.alloc(pl.count)) != AISX_OK || (rc = trk_empty(h.get())) != AISX_OK)
         return rc;
     *out = h.release();
     return AISX_OK;
@@ -151,7 +143,7 @@ extern "C" int aisx_track_batch_reset(aisx_track_batch* h)
 extern "C" int aisx_track_batch_process(aisx_track_batch* h, const int32_t* d_cols, long col_stride, const char* d_strs,
                                         const aisx_pdu* d_pdus, const int* d_nrows, int32_t stamp, void* stream)
 {
-    if (!h || !d_cols || !d_strs || !d_nrows || col_stride < h->max_rows || ((size_t)d_strs & 3)) {
+    if (!h || !d_cols || !d_strs || !d_nrows || col_stride < h->pl.max_rows || ((size_t)d_strs & 3)) {
         set_err("aisx_track_batch_process: a handle, columns of a stride of at least max_rows, strings aligned to four bytes and "
                 "a row count are needed");
         return AISX_ERR_INVALID;
@@ -159,21 +151,8 @@ extern "C" int aisx_track_batch_process(aisx_track_batch* h, const int32_t* d_co
     OnDevice on(h->dev);
     AISX_HIPCHK(on.err);
     const hipStream_t st = (hipStream_t)stream;
-    TrkParams p = trk_params(h);
-    p.in_cols = d_cols;
-    p.in_stride = col_stride;
-    p.in_strs = (const uint32_t*)d_strs;
-    p.in_recs = (const HdlcRec*)d_pdus;
-    p.nrows = d_nrows;
-    p.stamp = stamp;
-    p.grid = h->clear_groups;
-    hipLaunchKernelGGL(k_trk_clear, dim3(h->clear_groups), dim3(TRK_T), 0, st, p);
-    p.grid = h->row_groups;
-    hipLaunchKernelGGL(k_trk_find, dim3(h->row_groups), dim3(TRK_T), 0, st, p);
-    hipLaunchKernelGGL(k_trk_classify, dim3(h->row_groups), dim3(TRK_T), 0, st, p);
-    hipLaunchKernelGGL(k_trk_assign, dim3(h->row_groups), dim3(TRK_T), 0, st, p);
-    hipLaunchKernelGGL(k_trk_winner, dim3(h->row_groups), dim3(TRK_T), 0, st, p);
-    hipLaunchKernelGGL(k_trk_apply, dim3(h->row_groups), dim3(TRK_T), 0, st, p);
+    h->pl.process(trk_bufs(h), d_cols, col_stride, (const uint32_t*)d_strs, (const HdlcRec*)d_pdus, d_nrows, stamp,
+                  [&](const PlanLaunch& l, const TrkCall& c) { return trk_launch(l, c, st); });
     AISX_HIPCHK(hipGetLastError());
     return AISX_OK;
 }
@@ -187,14 +166,11 @@ extern "C" int aisx_track_batch_expire(aisx_track_batch* h, int32_t min_stamp, v
     OnDevice on(h->dev);
     AISX_HIPCHK(on.err);
     const hipStream_t st = (hipStream_t)stream;
-    TrkParams p = trk_params(h);
-    p.tab2 = h->d_tab[h->cur ^ 1];
-    p.strs2 = h->d_strs[h->cur ^ 1];
-    p.grid = h->cap_groups;
-    hipLaunchKernelGGL(k_trk_keep, dim3(h->cap_groups), dim3(TRK_T), 0, st, p, min_stamp);
-    hipLaunchKernelGGL(k_trk_compact, dim3(h->cap_groups), dim3(TRK_T), 0, st, p, min_stamp);
-    AISX_HIPCHK(hipGetLastError());
-    h->cur ^= 1;
+    hipError_t err = hipSuccess;
+    h->pl.expire(trk_bufs(h), min_stamp, [&](const PlanLaunch& l, const TrkCall& c) {
+        return trk_launch(l, c, st) && (l.kernel != TRK_K_COMPACT || (err = hipGetLastError()) == hipSuccess);
+    });
+    AISX_LAUNCHCHK(err);
     return AISX_OK;
 }
 
@@ -204,11 +180,11 @@ extern "C" int aisx_track_batch_results_device(const aisx_track_batch* h, const 
     if (!h)
         return AISX_ERR_INVALID;
     if (d_cols)
-        *d_cols = h->d_tab[h->cur];
+        *d_cols = h->d_tab[h->pl.cur];
     if (col_stride)
-        *col_stride = h->capacity;
+        *col_stride = h->pl.capacity;
     if (d_strs)
-        *d_strs = (const char*)h->d_strs[h->cur].get();
+        *d_strs = (const char*)h->d_strs[h->pl.cur].get();
     if (d_changed)
         *d_changed = h->d_changed;
     if (d_count)
@@ -228,7 +204,7 @@ static int trk_counts(aisx_track_batch* h, int* cnt, bool clear, hipStream_t st)
 
 static int trk_bad(const aisx_track_batch* h, const char* who)
 {
-    set_err("%s: a call since the last read met a row count outside [0, %d]: it merged nothing", who, h->max_rows);
+    set_err("%s: a call since the last read met a row count outside [0, %d]: it merged nothing", who, h->pl.max_rows);
     return AISX_ERR_INVALID;
 }
 
@@ -252,12 +228,12 @@ extern "C" int aisx_track_batch_read(aisx_track_batch* h, int first, int n, int3
     int cnt[TRK_NCNT], rc;
     if ((rc = trk_counts(h, cnt, true, st)) != AISX_OK)
         return rc;
-    const int nv = std::max(0, std::min(cnt[TN_VESSELS], h->capacity));
+    const int nv = std::max(0, std::min(cnt[TN_VESSELS], h->pl.capacity));
     const int k = std::max(0, std::min(n, nv - first));
     if (k > 0) {
-        AISX_HIPCHK(hipMemcpy2DAsync(cols, sizeof(int32_t) * (size_t)col_stride, h->d_tab[h->cur] + first,
-                                     sizeof(int32_t) * (size_t)h->capacity, sizeof(int32_t) * (size_t)k, TRK_NCOL, hipMemcpyDeviceToHost, st));
-        AISX_HIPCHK(hipMemcpyAsync(strs, h->d_strs[h->cur] + (size_t)first * MSG_STR_WORDS, (size_t)MSG_STR * k, hipMemcpyDeviceToHost, st));
+        AISX_HIPCHK(hipMemcpy2DAsync(cols, sizeof(int32_t) * (size_t)col_stride, h->d_tab[h->pl.cur] + first,
+                                     sizeof(int32_t) * (size_t)h->pl.capacity, sizeof(int32_t) * (size_t)k, TRK_NCOL, hipMemcpyDeviceToHost, st));
+        AISX_HIPCHK(hipMemcpyAsync(strs, h->d_strs[h->pl.cur] + (size_t)first * MSG_STR_WORDS, (size_t)MSG_STR * k, hipMemcpyDeviceToHost, st));
     }
     AISX_HIPCHK(hipStreamSynchronize(st));
     *nvessels = nv;
@@ -272,16 +248,12 @@ extern "C" int aisx_track_batch_read_changed(aisx_track_batch* h, int* idx, int3
     OnDevice on(h->dev);
     AISX_HIPCHK(on.err);
     const hipStream_t st = (hipStream_t)stream;
-    TrkParams p = trk_params(h);
-    p.tab2 = h->d_gcols;
-    p.strs2 = h->d_gstrs;
-    p.grid = h->row_groups;
-    hipLaunchKernelGGL(k_trk_gather, dim3(h->row_groups), dim3(TRK_T), 0, st, p);
+    h->pl.gather(trk_bufs(h), [&](const PlanLaunch& l, const TrkCall& c) { return trk_launch(l, c, st); });
     AISX_HIPCHK(hipGetLastError());
     int cnt[TRK_NCNT], rc;
     if ((rc = trk_counts(h, cnt, true, st)) != AISX_OK)
         return rc;
-    const int k = std::max(0, std::min(cnt[TN_CHANGED], h->max_rows));
+    const int k = std::max(0, std::min(cnt[TN_CHANGED], h->pl.max_rows));
     *nchanged = k;
     if (k > cap) {
         set_err("aisx_track_batch_read_changed: %d vessels changed, the buffers hold %d", k, cap);
@@ -289,7 +261,7 @@ extern "C" int aisx_track_batch_read_changed(aisx_track_batch* h, int* idx, int3
     }
     if (k > 0) {
         AISX_HIPCHK(hipMemcpyAsync(idx, h->d_changed, sizeof(int) * (size_t)k, hipMemcpyDeviceToHost, st));
-        AISX_HIPCHK(hipMemcpy2DAsync(cols, sizeof(int32_t) * (size_t)col_stride, h->d_gcols, sizeof(int32_t) * (size_t)h->max_rows,
+        AISX_HIPCHK(hipMemcpy2DAsync(cols, sizeof(int32_t) * (size_t)col_stride, h->d_gcols, sizeof(int32_t) * (size_t)h->pl.max_rows,
                                      sizeof(int32_t) * (size_t)k, TRK_NCOL, hipMemcpyDeviceToHost, st));
         AISX_HIPCHK(hipMemcpyAsync(strs, h->d_gstrs, (size_t)MSG_STR * k, hipMemcpyDeviceToHost, st));
         AISX_HIPCHK(hipStreamSynchronize(st));

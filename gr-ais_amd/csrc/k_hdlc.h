@@ -475,4 +475,135 @@ AISX_DI void hdlc_gather_body(Ctx& cx, const HdlcGatherParams& p)
         p.out_bytes[bb + k] = sb[k];
 }
 
+// ------------------------------------------------------------------
+// The launch plan of aisx_hdlc_batch_* (host only): the argument check, the derived sizes, the buffers and the
+// per-call sequence.  aisx_hdlc.hip runs it on device memory, tests/emul_hdlc on host memory.
+// ------------------------------------------------------------------
+enum { HD_K_DEFRAME, HD_K_DEFRAME_REPAIR, HD_K_DEFRAME_EVENTS, HD_K_SCAN, HD_K_GATHER };
+
+struct HdlcBufs { // a handle's buffers, sized by the HdlcPlan members of the same names
+    HdlcState* st;
+    unsigned long long* carry;
+    HdlcRec* srec;
+    unsigned char* sbytes;
+    int* cnt;        // [nchan] records, [nchan] bytes
+    long long* base; // [nchan] record bases, [nchan] byte bases
+    int* count;      // [0] found, [1] kept, [2] bad-count flag
+    HdlcRec* out;
+    unsigned char* out_bytes;
+    int* fix;        // [max_pdus] the records' repair marks
+    const HdlcRule* rules; // a handle with rules: they, the staging of the marks and the syndrome table in use
+    int* sfix;
+    const unsigned short* syn;
+};
+
+struct HdlcCall {
+    HdlcParams p;
+    HdlcScanParams s;
+    HdlcGatherParams g;
+};
+
+struct HdlcPlan {
+    int lmin, lmax, nchan, max_bits, max_pdus, scan_t;
+    int carry_words, rec_cap, byte_cap;
+    long long out_bytes_cap;
+    PlanBuf st, carry, srec, sbytes, cnt, base, count, out, out_bytes, fix, rules, sfix, syn;
+
+    // the argument check of aisx_hdlc_batch_create: nullptr when it passes, else what is needed
+    static const char* check(int length_min, int length_max, int nchan, int max_bits, int max_pdus)
+    {
+        static_assert(HD_MAX_OCTETS == 1024, "the bound in the text below");
+        if (length_min < 2 || length_max < length_min || length_max > HD_MAX_OCTETS || nchan < 1 || max_bits < 1 ||
+            max_bits > (1 << 28) || max_pdus < 1)
+            return "need 2 <= length_min <= length_max <= 1024, nchan >= 1, 1 <= max_bits <= 2^28, max_pdus >= 1";
+        return nullptr;
+    }
+    // scan_t: threads of the scan's one workgroup (the device runs HD_SCAN_T)
+    HdlcPlan(int length_min, int length_max, int nchan_, int max_bits_, int max_pdus_, int scan_t_ = HD_SCAN_T)
+        : lmin(length_min), lmax(length_max), nchan(nchan_), max_bits(max_bits_), max_pdus(max_pdus_), scan_t(scan_t_)
+    {
+        // a call's good frames per channel: disjoint runs of >= 8 length_min data bits, each closed by a bit of its
+        // own, all but the first inside the call's bits; their payload comes from the open frame and the call's bits
+        const long long span = 8LL * (lmax + 1) + max_bits;
+        carry_words = (8 * (lmax + 1) + 63) / 64;
+        rec_cap = (int)(span / (8LL * lmin + 1) + 2);
+        byte_cap = (int)(span / 8 + 8);
+        out_bytes_cap = (long long)max_pdus * (lmax - 1); // (a payload is at most length_max - 1 octets)
+        const size_t nc = (size_t)nchan;
+        st = { nc, true };
+        carry = { nc * carry_words, true };
+        srec = { nc * rec_cap, false };
+        sbytes = { nc * byte_cap, false };
+        cnt = { 2 * nc, true };
+        base = { 2 * nc, true };
+        count = { 4, true };
+        out = { (size_t)max_pdus, true };
+        out_bytes = { (size_t)out_bytes_cap, true };
+        fix = { (size_t)max_pdus, false }; // (filled with -1 while the handle has no rules)
+        rules = { HD_MAX_RULES, true };
+        sfix = { nc * rec_cap, false };
+        syn = { 65536, false };
+    }
+
+    // a call: nrules > 0 runs the repairing deframer, `events` the one of a mask that is not the single event alone
+    template <class Launch>
+    bool process(const HdlcBufs& b, const unsigned char* bits, long stride, const int* nbits, int nrules, bool events,
+                 Launch&& launch) const
+    {
+        HdlcCall c;
+        HdlcParams& p = c.p;
+        p.bits = bits;
+        p.stride = stride;
+        p.nbits = nbits;
+        p.max_bits = max_bits;
+        p.lmin = lmin;
+        p.lmax = lmax;
+        p.st = b.st;
+        p.carry = b.carry;
+        p.carry_words = carry_words;
+        p.srec = b.srec;
+        p.rec_cap = rec_cap;
+        p.sbytes = b.sbytes;
+        p.byte_cap = byte_cap;
+        p.cnt = b.cnt;
+        p.nbytes = b.cnt + nchan;
+        p.flags = b.count + 2;
+        if (nrules > 0) {
+            p.rules = b.rules;
+            p.nrules = nrules;
+            p.sfix = b.sfix;
+            p.syn_inv = b.syn;
+        }
+        HdlcScanParams& s = c.s;
+        s.cnt = p.cnt;
+        s.nbytes = p.nbytes;
+        s.rec_base = b.base;
+        s.byte_base = b.base + nchan;
+        s.nchan = nchan;
+        s.max_pdus = max_pdus;
+        s.count = b.count;
+        HdlcGatherParams& g = c.g;
+        g.srec = b.srec;
+        g.rec_cap = rec_cap;
+        g.sbytes = b.sbytes;
+        g.byte_cap = byte_cap;
+        g.cnt = p.cnt;
+        g.nbytes = p.nbytes;
+        g.rec_base = s.rec_base;
+        g.byte_base = s.byte_base;
+        g.max_pdus = max_pdus;
+        g.out = b.out;
+        g.out_bytes = b.out_bytes;
+        if (nrules > 0) {
+            g.sfix = b.sfix;
+            g.out_fix = b.fix;
+        }
+        const PlanLaunch deframe = nrules <= 0 ? PlanLaunch{ HD_K_DEFRAME, nchan, 1, HD_T, HD_LDS_BYTES }
+                                   : !events   ? PlanLaunch{ HD_K_DEFRAME_REPAIR, nchan, 1, HD_T, HD_LDS_BYTES_REPAIR }
+                                               : PlanLaunch{ HD_K_DEFRAME_EVENTS, nchan, 1, HD_T, HD_LDS_BYTES_REPAIR };
+        return launch(deframe, c) && launch(PlanLaunch{ HD_K_SCAN, 1, 1, scan_t, 2 * scan_t * 8 }, c) &&
+               launch(PlanLaunch{ HD_K_GATHER, nchan, 1, HD_T, 0 }, c);
+    }
+};
+
 } // namespace aisx

@@ -252,4 +252,69 @@ AISX_DI void mlse_body(Ctx& cx, const MlseParams& p)
     }
 }
 
+// ------------------------------------------------------------------
+// The launch plan of aisx_mlse_batch_* (host only): the argument check, the derived sizes, the buffers and the
+// per-call sequence.  aisx_mlse.hip runs it on device memory, tests/emul_mlse on host memory.
+// ------------------------------------------------------------------
+enum { MLSE_K_PROCESS, MLSE_K_FLUSH };
+
+struct MlseBufs {
+    MlseState* st[2];
+    cf* carry[2]; // [nchan][MLSE_CARRY]
+    int* flag;
+};
+
+struct MlsePlan {
+    int nchan, max_syms, groups;
+    int cur = 0; // which state / carry buffer the calls issued so far leave the channels in
+    MlseRot rot;
+    PlanBuf st, carry, flag;
+
+    // the argument check of aisx_mlse_batch_create (bt_ok: mlse_model took the bt): nullptr when it passes
+    static const char* check(int nchan, int max_syms, bool bt_ok)
+    {
+        if (nchan < 1 || nchan > (1 << 20) || max_syms < 1 || max_syms > (1 << 27) || !bt_ok)
+            return "need 0.1 <= bt <= 1, 1 <= nchan <= 2^20 and 1 <= max_syms <= 2^27";
+        return nullptr;
+    }
+    MlsePlan(const MlseRot& rot_, int nchan_, int max_syms_) : nchan(nchan_), max_syms(max_syms_), rot(rot_)
+    {
+        // a call decides at most (max_syms + MLSE_B - 1) / MLSE_B blocks of a channel
+        const int blocks = (max_syms + MLSE_B - 1) / MLSE_B;
+        groups = (blocks + MLSE_T - 1) / MLSE_T;
+        groups = groups < 1 ? 1 : groups;
+        st = { (size_t)nchan, true };
+        carry = { (size_t)nchan * MLSE_CARRY, true };
+        flag = { 1, true };
+    }
+    void reset() { cur = 0; }
+
+    // a call with symbols, or (syms == nullptr) the flush: one launch, after which the buffers have changed roles
+    template <class Launch>
+    bool process(const MlseBufs& b, const cf* syms, long syms_stride, const int* nsyms, unsigned char* bits, long bits_stride,
+                 int* nbits, Launch&& launch)
+    {
+        MlseParams p = {};
+        p.max_syms = max_syms;
+        p.bits = bits;
+        p.bit_stride = bits_stride;
+        p.nbits = nbits;
+        p.st_in = b.st[cur];
+        p.st_out = b.st[cur ^ 1];
+        p.carry_in = b.carry[cur];
+        p.carry_out = b.carry[cur ^ 1];
+        p.flag = b.flag;
+        p.rot = rot;
+        p.syms = syms;
+        p.sym_stride = syms_stride;
+        p.nsyms = nsyms;
+        // (at a flush at most two blocks of a channel are left)
+        const PlanLaunch l = { syms ? MLSE_K_PROCESS : MLSE_K_FLUSH, nchan, syms ? groups : 1, MLSE_T, MLSE_LDS_BYTES };
+        if (!launch(l, p))
+            return false;
+        cur ^= 1;
+        return true;
+    }
+};
+
 } // namespace aisx

@@ -116,4 +116,60 @@ AISX_DI void msg_body(Ctx& cx, const MsgParams& p)
     }
 }
 
+// ------------------------------------------------------------------
+// The launch plan of aisx_msg_batch_* (host only): the argument check, the derived sizes, the buffers and the
+// per-call sequence.  aisx_msg.hip runs it on device memory, tests/emul_msg on host memory.
+// ------------------------------------------------------------------
+struct MsgBufs {
+    const uint32_t* tab; // MSG_TAB
+    int32_t* cols;       // [MSG_NCOL][max_pdus]
+    uint32_t* strs;      // [max_pdus][MSG_STR_WORDS]
+    int* count;          // [0] found, [1] rows written, [2] bad-input flag
+};
+
+struct MsgPlan {
+    int nchan, max_pdus, lmax, threads, groups;
+    PlanBuf tab, cols, strs, count;
+
+    // the argument check of aisx_msg_batch_create: nullptr when it passes, else what is needed
+    static const char* check(int nchan, int max_pdus, int length_max)
+    {
+        static_assert(MSG_MAX_OCTETS == 1024, "the bound in the text below");
+        if (nchan < 1 || max_pdus < 1 || length_max < 2 || length_max > MSG_MAX_OCTETS)
+            return "need nchan >= 1, max_pdus >= 1, 2 <= length_max <= 1024";
+        return nullptr;
+    }
+    // threads_: of a workgroup, a multiple of 64; max_groups: workgroups at most
+    MsgPlan(int nchan_, int max_pdus_, int length_max, int threads_ = MSG_T, int max_groups = MSG_MAX_GROUPS)
+        : nchan(nchan_), max_pdus(max_pdus_), lmax(length_max), threads(threads_)
+    {
+        const long long g = ((long long)max_pdus + threads - 1) / threads;
+        groups = (int)(g < max_groups ? g : max_groups);
+        tab = { (size_t)MSG_TAB_WORDS, false };
+        cols = { (size_t)MSG_NCOL * max_pdus, false };
+        strs = { (size_t)MSG_STR_WORDS * max_pdus, false };
+        count = { 4, true };
+    }
+
+    template <class Launch>
+    bool process(const MsgBufs& b, const HdlcRec* pdus, const unsigned char* bytes, const int* npdus, const int* nfound,
+                 Launch&& launch) const
+    {
+        MsgParams p;
+        p.in = pdus;
+        p.bytes = bytes;
+        p.npdus = npdus;
+        p.nfound = nfound;
+        p.tab = b.tab;
+        p.nchan = nchan;
+        p.max_pdus = max_pdus;
+        p.max_len = lmax - 1;
+        p.nwaves = groups * (threads / 64);
+        p.cols = b.cols;
+        p.strs = b.strs;
+        p.count = b.count;
+        return launch(PlanLaunch{ 0, groups, 1, threads, msg_lds_bytes(threads) }, p);
+    }
+};
+
 } // namespace aisx

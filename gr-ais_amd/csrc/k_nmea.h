@@ -11,6 +11,10 @@
 //          payload characters from bits 6k .. 6k + 5 of the payload; the checksum is an XOR over the wave.
 // No atomic decides where anything goes.
 #pragma once
+#include <string.h>
+
+#include <vector>
+
 #include "aisx_common.h"
 #include "k_hdlc.h"
 
@@ -252,5 +256,117 @@ AISX_DI void nmea_write_body(Ctx& cx, const NmeaWriteParams& p)
         }
     }
 }
+
+// ------------------------------------------------------------------
+// The launch plan of aisx_nmea_batch_* (host only): the argument checks, the derived sizes, the buffers and the
+// per-call sequence.  aisx_nmea.hip runs it on device memory, tests/emul_nmea on host memory.
+// ------------------------------------------------------------------
+
+// the designator check of aisx_nmea_batch_create, aisx_nmea_parse_batch_create and aisx_rx_create: the index of the
+// first one that is missing or longer than NM_DESIG bytes, -1 when there is none; *max_dlen: the longest
+inline int nm_bad_designator(const char* const* designators, int nchan, int* max_dlen = nullptr)
+{
+    int longest = 0;
+    for (int c = 0; c < nchan; c++) {
+        const size_t n = designators[c] ? strnlen(designators[c], NM_DESIG + 1) : NM_DESIG + 1;
+        if (n > (size_t)NM_DESIG)
+            return c;
+        longest = (int)n > longest ? (int)n : longest;
+    }
+    if (max_dlen)
+        *max_dlen = longest;
+    return -1;
+}
+
+// checked designators as the kernels read them: desig [nchan][NM_DESIG] (not NUL-terminated), dlen [nchan]
+inline void nm_pack_designators(const char* const* designators, int nchan, std::vector<char>& desig, std::vector<unsigned char>& dlen)
+{
+    desig.assign((size_t)nchan * NM_DESIG, 0);
+    dlen.assign(nchan, 0);
+    for (int c = 0; c < nchan; c++) {
+        dlen[c] = (unsigned char)strlen(designators[c]);
+        memcpy(desig.data() + (size_t)c * NM_DESIG, designators[c], dlen[c]);
+    }
+}
+
+enum { NM_K_SCAN, NM_K_WRITE };
+
+struct NmeaBufs {
+    const char* desig;
+    const unsigned char* dlen;
+    HdlcRec* out;
+    char* text;
+    int* count; // [0] found, [1] records written, [2] bad-input flag
+};
+
+struct NmeaCall {
+    NmeaScanParams s;
+    NmeaWriteParams w;
+};
+
+struct NmeaPlan {
+    int nchan, max_pdus, lmax, scan_t, write_t, write_groups;
+    long long text_cap;
+    std::vector<char> desig_host;         // what the handle's desig and dlen buffers hold
+    std::vector<unsigned char> dlen_host;
+    PlanBuf desig, dlen, out, text, count;
+
+    // the argument check of aisx_nmea_batch_create but the designators' own (nm_bad_designator): nullptr when it passes
+    static const char* check(const char* const* designators, int nchan, int max_pdus, int length_max, long text_cap)
+    {
+        static_assert(NM_MAX_OCTETS == 1024, "the bound in the text below");
+        if (!designators || nchan < 1 || max_pdus < 1 || length_max < 2 || length_max > NM_MAX_OCTETS || text_cap < 0)
+            return "need designators, nchan >= 1, max_pdus >= 1, 2 <= length_max <= 1024, text_cap >= 0";
+        return nullptr;
+    }
+    // scan_t, write_t: threads of the scan's one workgroup and of a write workgroup; max_groups: write workgroups at most
+    NmeaPlan(const char* const* designators, int nchan_, int max_pdus_, int length_max, long text_cap_, int scan_t_ = NM_SCAN_T,
+             int write_t_ = NM_W_T, int max_groups = NM_W_MAX_GROUPS)
+        : nchan(nchan_), max_pdus(max_pdus_), lmax(length_max), scan_t(scan_t_), write_t(write_t_)
+    {
+        int max_dlen = 0;
+        nm_bad_designator(designators, nchan, &max_dlen);
+        // the worst case: every record as long as a payload can be, on the channel with the longest designator
+        const long long worst = (long long)max_pdus * (nm_text_len(length_max - 1, max_dlen) + 1);
+        text_cap = text_cap_ == 0 || text_cap_ > worst ? worst : text_cap_;
+        const long long groups = ((long long)max_pdus + write_t / 64 - 1) / (write_t / 64);
+        write_groups = (int)(groups < max_groups ? groups : max_groups);
+        nm_pack_designators(designators, nchan, desig_host, dlen_host);
+        desig = { desig_host.size(), false };
+        dlen = { dlen_host.size(), false };
+        out = { (size_t)max_pdus, false };
+        text = { (size_t)text_cap, false };
+        count = { 4, true };
+    }
+
+    template <class Launch>
+    bool process(const NmeaBufs& b, const HdlcRec* pdus, const unsigned char* bytes, const int* npdus, const int* nfound,
+                 Launch&& launch) const
+    {
+        NmeaCall c;
+        NmeaScanParams& s = c.s;
+        s.in = pdus;
+        s.npdus = npdus;
+        s.nfound = nfound;
+        s.dlen = b.dlen;
+        s.nchan = nchan;
+        s.max_pdus = max_pdus;
+        s.max_len = lmax - 1;
+        s.text_cap = text_cap;
+        s.out = b.out;
+        s.count = b.count;
+        NmeaWriteParams& w = c.w;
+        w.in = s.in;
+        w.bytes = bytes;
+        w.out = b.out;
+        w.count = b.count;
+        w.desig = b.desig;
+        w.dlen = b.dlen;
+        w.text = b.text;
+        w.nwaves = write_groups * (write_t / 64);
+        return launch(PlanLaunch{ NM_K_SCAN, 1, 1, scan_t, (2 * (scan_t / 64) + 2) * 4 }, c) &&
+               launch(PlanLaunch{ NM_K_WRITE, write_groups, 1, write_t, 0 }, c);
+    }
+};
 
 } // namespace aisx

@@ -865,4 +865,142 @@ AISX_DI void nmp_carry_body(Ctx& cx, const NmpParams& p)
         p.meta[NP_M_CUR] = nc;
 }
 
+// ------------------------------------------------------------------
+// The launch plan of aisx_nmea_parse_batch_* (host only): the argument checks, the derived sizes, the buffers and the
+// per-call sequence.  aisx_nmea_parse.hip runs it on device memory, tests/emul_nmea_parse on host memory.
+// ------------------------------------------------------------------
+enum {
+    NP_K_COUNT, NP_K_SCAN, NP_K_INDEX, NP_K_PARSE, NP_K_GCOUNT, NP_K_GSCAN1, NP_K_GCOMPACT, NP_K_GMSG, NP_K_GSCAN2, NP_K_GPLACE,
+    NP_K_WRITE, NP_K_CARRY, NP_NKERNELS
+};
+
+struct NmpBufs { // a handle's buffers, sized by the NmpPlan members of the same names (NmpParams says what they hold)
+    const char* desig;
+    const unsigned char* dlen;
+    NmpState* st;
+    unsigned char *lcarry, *gcarry;
+    int *tcount, *toff, *meta;
+    long long* lend;
+    NmpKey* key;
+    long long *pos, *tm;
+    int *cidx, *mlen, *tl;
+    long long* tlb;
+    int* bstat;
+    HdlcRec* rec;
+    int* aux;
+    long long* times;
+    unsigned char* bytes;
+    int* count;
+    NmpNext* next;
+};
+
+struct NmpPlan {
+    int nchan, lmax, max_line, flags, max_lines, max_pdus, threads, scan_t;
+    long long max_bytes, ntiles, nlt; // tiles of text; tiles of lines / sentences
+    int tile_groups, line_groups, pdu_groups, ltile_groups;
+    std::vector<char> desig_host;         // what the handle's desig and dlen buffers hold
+    std::vector<unsigned char> dlen_host;
+    PlanBuf desig, dlen, st, lcarry, gcarry, tcount, toff, meta, lend, key, pos, tm, cidx, mlen, tl, tlb, bstat, rec, aux, times,
+        bytes, count, next;
+
+    // the argument check of aisx_nmea_parse_batch_create but the designators' own (nm_bad_designator): nullptr when it
+    // passes (the one flag there is: AISX_NMEA_PARSE_REF_TAIL = 1)
+    static const char* check(const char* const* designators, int nchan, int length_max, int max_line, int flags, long max_bytes,
+                             int max_lines, int max_pdus)
+    {
+        static_assert(NM_MAX_OCTETS == 1024, "the bound in the text below");
+        if (!designators || nchan < 1 || length_max < 2 || length_max > NM_MAX_OCTETS || max_line < 64 || max_line > 4096 ||
+            (flags & ~1) || max_bytes < 1 || max_bytes > (1l << 30) || max_lines < 1 || max_lines > (1 << 26) || max_pdus < 1)
+            return "need designators, nchan >= 1, 2 <= length_max <= 1024, 64 <= max_line <= 4096, flags 0 or 1, "
+                   "1 <= max_bytes <= 2^30, 1 <= max_lines <= 2^26, max_pdus >= 1";
+        return nullptr;
+    }
+    // threads_: of a tile / wave kernel's workgroup; scan_t_: of a scan's one workgroup; max_groups: workgroups at most
+    NmpPlan(const char* const* designators, int nchan_, int length_max, int max_line_, int flags_, long max_bytes_, int max_lines_,
+            int max_pdus_, int threads_ = NP_T, int scan_t_ = NP_SCAN_T, int max_groups = NP_MAX_GROUPS)
+        : nchan(nchan_), lmax(length_max), max_line(max_line_), flags(flags_), max_lines(max_lines_), max_pdus(max_pdus_),
+          threads(threads_), scan_t(scan_t_), max_bytes(max_bytes_)
+    {
+        auto groups = [max_groups](long long items, int per_group) {
+            const long long g = (items + per_group - 1) / per_group;
+            return (int)(g < 1 ? 1 : g < max_groups ? g : max_groups);
+        };
+        ntiles = (max_bytes + threads * NP_CHUNK - 1) / (threads * NP_CHUNK);
+        tile_groups = groups(ntiles, 1);
+        line_groups = groups(max_lines, threads / 64);
+        pdu_groups = groups(max_pdus, threads / 64);
+        nlt = ((long long)max_lines + NP_GMAX + threads - 1) / threads;
+        ltile_groups = groups(nlt, 1);
+        nm_pack_designators(designators, nchan, desig_host, dlen_host);
+        const size_t nl = (size_t)max_lines, np = (size_t)max_pdus;
+        desig = { desig_host.size(), false };
+        dlen = { dlen_host.size(), false };
+        st = { 2, true };
+        lcarry = { 2 * (size_t)max_line, true };
+        gcarry = { 2 * (size_t)NP_GMAX * max_line, true };
+        tcount = toff = { (size_t)ntiles, false };
+        meta = { NP_M_N, true };
+        lend = key = pos = tm = cidx = { nl, false };
+        mlen = { nl + NP_GMAX, false };
+        tl = tlb = { (size_t)nlt, false };
+        bstat = { (size_t)max_groups * 8, true };
+        rec = aux = times = { np, false };
+        bytes = { np * (size_t)(length_max - 1), false };
+        count = { NP_NCNT, true };
+        next = { 1, true };
+    }
+
+    // a call: twelve launches on four grids; the tile kernels read their grid from ngroups, the wave kernels theirs from
+    // nwaves, and both are set for the launches that read them
+    template <class Launch>
+    bool process(const NmpBufs& b, const unsigned char* text, const long long* nbytes, Launch&& launch) const
+    {
+        NmpParams p;
+        p.text = text;
+        p.nbytes = nbytes;
+        p.max_bytes = max_bytes;
+        p.max_lines = max_lines;
+        p.max_pdus = max_pdus;
+        p.max_len = lmax - 1;
+        p.max_line = max_line;
+        p.flags = flags;
+        p.nchan = nchan;
+        p.desig = b.desig;
+        p.dlen = b.dlen;
+        p.st = b.st;
+        p.lcarry = b.lcarry;
+        p.gcarry = b.gcarry;
+        p.tcount = b.tcount;
+        p.toff = b.toff;
+        p.meta = b.meta;
+        p.lend = b.lend;
+        p.key = b.key;
+        p.pos = b.pos;
+        p.tm = b.tm;
+        p.cidx = b.cidx;
+        p.mlen = b.mlen;
+        p.tl = b.tl;
+        p.tlb = b.tlb;
+        p.bstat = b.bstat;
+        p.rec = b.rec;
+        p.aux = b.aux;
+        p.times = b.times;
+        p.bytes = b.bytes;
+        p.count = b.count;
+        p.next = b.next;
+        auto on = [&](int kernel, int groups, int t) { return launch(PlanLaunch{ kernel, groups, 1, t, NP_LDS_BYTES }, p); };
+        p.ngroups = tile_groups;
+        p.nwaves = line_groups * (threads / 64);
+        if (!on(NP_K_COUNT, tile_groups, threads) || !on(NP_K_SCAN, 1, scan_t) || !on(NP_K_INDEX, tile_groups, threads) ||
+            !on(NP_K_PARSE, line_groups, threads))
+            return false;
+        p.ngroups = ltile_groups;
+        if (!on(NP_K_GCOUNT, ltile_groups, threads) || !on(NP_K_GSCAN1, 1, scan_t) || !on(NP_K_GCOMPACT, ltile_groups, threads) ||
+            !on(NP_K_GMSG, ltile_groups, threads) || !on(NP_K_GSCAN2, 1, scan_t) || !on(NP_K_GPLACE, ltile_groups, threads))
+            return false;
+        p.nwaves = pdu_groups * (threads / 64);
+        return on(NP_K_WRITE, pdu_groups, threads) && on(NP_K_CARRY, 1, 64);
+    }
+};
+
 } // namespace aisx

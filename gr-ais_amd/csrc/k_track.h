@@ -426,4 +426,140 @@ AISX_DI void trk_gather_body(Ctx& cx, const TrkParams& p)
         p.strs2[j * MSG_STR_WORDS + k] = p.strs[(long long)v * MSG_STR_WORDS + k];
 }
 
+// ------------------------------------------------------------------
+// The launch plan of aisx_track_batch_* (host only): the argument check, the derived sizes, the buffers and the
+// per-call sequences.  aisx_track.hip runs it on device memory, tests/emul_track on host memory.
+// ------------------------------------------------------------------
+enum { TRK_K_CLEAR, TRK_K_FIND, TRK_K_CLASSIFY, TRK_K_ASSIGN, TRK_K_WINNER, TRK_K_APPLY, TRK_K_KEEP, TRK_K_COMPACT, TRK_K_GATHER };
+
+struct TrkBufs {
+    int32_t* tab[2];   // [TRK_NCOL][capacity]
+    uint32_t* strs[2]; // [capacity][MSG_STR_WORDS]
+    int32_t* hkey;     // [1 << hbits], TRK_EMPTY in an empty table
+    int* hval;
+    int32_t* bkey;     // [1 << bbits]
+    int *bfirst, *bval, *bj;
+    int* rslot;        // [max_rows]
+    int* bsum;         // [2][max(row_groups, cap_groups)]
+    int* win;          // [TRK_NWIN][max_rows]
+    int* changed;      // [max_rows]
+    int32_t* gcols;    // [TRK_NCOL][max_rows]   the changed vessels' rows, gathered
+    uint32_t* gstrs;   // [max_rows][MSG_STR_WORDS]
+    int* count;        // [TRK_COUNT_WORDS]
+};
+
+struct TrkCall {
+    TrkParams p;
+    int32_t min_stamp; // TRK_K_KEEP and TRK_K_COMPACT
+};
+
+struct TrkPlan {
+    int capacity, max_rows, hbits, bbits, row_groups, cap_groups, clear_groups, nbmax;
+    int cur = 0; // which table buffer the calls issued so far leave the table in
+    PlanBuf tab, strs, hkey, hval, bkey, bfirst, bval, bj, rslot, bsum, win, changed, gcols, gstrs, count;
+
+    // the argument check of aisx_track_batch_create: nullptr when it passes, else what is needed
+    static const char* check(int capacity, int max_rows)
+    {
+        static_assert(TRK_MAX == 16777216, "the bound in the text below");
+        if (capacity < 1 || capacity > TRK_MAX || max_rows < 1 || max_rows > TRK_MAX)
+            return "need 1 <= capacity <= 16777216 and 1 <= max_rows <= 16777216";
+        return nullptr;
+    }
+    TrkPlan(int capacity_, int max_rows_) : capacity(capacity_), max_rows(max_rows_)
+    {
+        hbits = trk_hash_bits(capacity);
+        bbits = trk_hash_bits(max_rows);
+        row_groups = (max_rows + TRK_T - 1) / TRK_T;
+        cap_groups = (capacity + TRK_T - 1) / TRK_T;
+        clear_groups = row_groups < 1024 ? row_groups : 1024;
+        nbmax = row_groups > cap_groups ? row_groups : cap_groups;
+        const size_t H = (size_t)1 << hbits, B = (size_t)1 << bbits, R = (size_t)max_rows, C = (size_t)capacity;
+        tab = { TRK_NCOL * C, false };
+        strs = { MSG_STR_WORDS * C, false };
+        hkey = { H, false }; // (filled with TRK_EMPTY)
+        hval = { H, false };
+        bkey = bfirst = bval = bj = { B, false };
+        rslot = { R, false };
+        bsum = { 2 * (size_t)nbmax, false };
+        win = { TRK_NWIN * R, false };
+        changed = { R, false };
+        gcols = { TRK_NCOL * R, false };
+        gstrs = { MSG_STR_WORDS * R, false };
+        count = { TRK_COUNT_WORDS, true };
+    }
+    void reset() { cur = 0; }
+
+    TrkParams params(const TrkBufs& b) const
+    {
+        TrkParams p = {};
+        p.capacity = capacity;
+        p.max_rows = max_rows;
+        p.tab = b.tab[cur];
+        p.strs = b.strs[cur];
+        p.hkey = b.hkey;
+        p.hval = b.hval;
+        p.hbits = hbits;
+        p.bkey = b.bkey;
+        p.bfirst = b.bfirst;
+        p.bval = b.bval;
+        p.bj = b.bj;
+        p.bbits = bbits;
+        p.rslot = b.rslot;
+        p.bsum = b.bsum;
+        p.nbmax = nbmax;
+        p.win = b.win;
+        p.changed = b.changed;
+        p.count = b.count;
+        return p;
+    }
+    static PlanLaunch on(int kernel, int groups) { return PlanLaunch{ kernel, groups, 1, TRK_T, TRK_LDS_BYTES }; }
+
+    // aisx_track_batch_process: six kernels
+    template <class Launch>
+    bool process(const TrkBufs& b, const int32_t* cols, long col_stride, const uint32_t* strs_in, const HdlcRec* recs,
+                 const int* nrows, int32_t stamp, Launch&& launch) const
+    {
+        TrkCall c = { params(b), 0 };
+        TrkParams& p = c.p;
+        p.in_cols = cols;
+        p.in_stride = col_stride;
+        p.in_strs = strs_in;
+        p.in_recs = recs;
+        p.nrows = nrows;
+        p.stamp = stamp;
+        p.grid = clear_groups;
+        if (!launch(on(TRK_K_CLEAR, clear_groups), c))
+            return false;
+        p.grid = row_groups;
+        for (int k = TRK_K_FIND; k <= TRK_K_APPLY; k++)
+            if (!launch(on(k, row_groups), c))
+                return false;
+        return true;
+    }
+    // aisx_track_batch_expire: two kernels, after which the table is in the other buffer
+    template <class Launch>
+    bool expire(const TrkBufs& b, int32_t min_stamp, Launch&& launch)
+    {
+        TrkCall c = { params(b), min_stamp };
+        c.p.tab2 = b.tab[cur ^ 1];
+        c.p.strs2 = b.strs[cur ^ 1];
+        c.p.grid = cap_groups;
+        if (!launch(on(TRK_K_KEEP, cap_groups), c) || !launch(on(TRK_K_COMPACT, cap_groups), c))
+            return false;
+        cur ^= 1;
+        return true;
+    }
+    // the gather of aisx_track_batch_read_changed: one kernel
+    template <class Launch>
+    bool gather(const TrkBufs& b, Launch&& launch) const
+    {
+        TrkCall c = { params(b), 0 };
+        c.p.tab2 = b.gcols;
+        c.p.strs2 = b.gstrs;
+        c.p.grid = row_groups;
+        return launch(on(TRK_K_GATHER, row_groups), c);
+    }
+};
+
 } // namespace aisx

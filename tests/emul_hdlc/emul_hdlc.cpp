@@ -1,103 +1,96 @@
-// emul_hdlc.cpp -- CPU model of the batched HDLC deframer (TEST INFRASTRUCTURE, see ../emul/emul.cpp): the kernel
-// bodies of gr-ais_amd/csrc/k_hdlc.h run one OS thread per lane under the same EmuCtx, driven the way
-// aisx_hdlc.hip drives them on the device (host memory in place of device memory).
+// emul_hdlc.cpp -- CPU model of the batched HDLC deframer, with and without the repair by CRC syndrome (TEST
+// INFRASTRUCTURE, see ../emul/emul.cpp): the kernel bodies of gr-ais_amd/csrc/k_hdlc.h run one OS thread per lane under
+// the same EmuCtx, driven by the launch plan that drives them on the device (HdlcPlan, k_hdlc.h) with host memory in
+// place of device memory.  The tables are the host form's (aisx_framing.cpp, built into this library), as on the device.
 #include "../emul/emul.cpp"
+#include "../emul/emul_plan.h"
+#include "../../gr-ais_amd/csrc/aisx_repair.h"
 #include "../../gr-ais_amd/csrc/k_hdlc.h"
 
 namespace {
 
+constexpr int EMU_SCAN_T = 64; // (the device runs HD_SCAN_T threads)
+
 struct EmuHdlc {
-    int lmin, lmax, nchan, max_bits, max_pdus, carry_words, rec_cap, byte_cap;
+    explicit EmuHdlc(const HdlcPlan& plan) : pl(plan) {}
+    const HdlcPlan pl;
     std::vector<HdlcState> st;
     std::vector<unsigned long long> carry;
     std::vector<HdlcRec> srec, out;
     std::vector<unsigned char> sbytes, out_bytes;
-    std::vector<int> cnt, nbytes;
-    std::vector<long long> rec_base, byte_base;
-    int count[4] = { 0, 0, 0, 0 };
+    std::vector<int> cnt, count, sfix, fix;
+    std::vector<long long> base;
+    std::vector<HdlcRule> rules;
+    std::vector<unsigned short> ev_tab;
+    int nrules = 0, events = AISX_HDLC_EV_SINGLE;
 };
 
 } // namespace
 
 extern "C" {
 
-// the argument checks are the product's (aisx_hdlc_batch_create); returns nullptr where it returns AISX_ERR_INVALID
+// returns nullptr where aisx_hdlc_batch_create returns AISX_ERR_INVALID
 void* emu_hdlc_create(int lmin, int lmax, int nchan, int max_bits, int max_pdus)
 {
-    if (lmin < 2 || lmax < lmin || lmax > HD_MAX_OCTETS || nchan < 1 || max_bits < 1 || max_bits > (1 << 28) || max_pdus < 1)
+    if (HdlcPlan::check(lmin, lmax, nchan, max_bits, max_pdus))
         return nullptr;
-    EmuHdlc* h = new EmuHdlc();
-    h->lmin = lmin;
-    h->lmax = lmax;
-    h->nchan = nchan;
-    h->max_bits = max_bits;
-    h->max_pdus = max_pdus;
-    const long long span = 8LL * (lmax + 1) + max_bits;
-    h->carry_words = (8 * (lmax + 1) + 63) / 64;
-    h->rec_cap = (int)(span / (8LL * lmin + 1) + 2);
-    h->byte_cap = (int)(span / 8 + 8);
-    h->st.assign(nchan, HdlcState{});
-    h->carry.assign((size_t)nchan * h->carry_words, 0);
-    h->srec.resize((size_t)nchan * h->rec_cap);
-    h->sbytes.resize((size_t)nchan * h->byte_cap);
-    h->cnt.assign(nchan, 0);
-    h->nbytes.assign(nchan, 0);
-    h->rec_base.assign(nchan, 0);
-    h->byte_base.assign(nchan, 0);
-    h->out.resize(max_pdus);
-    h->out_bytes.resize((size_t)max_pdus * (lmax - 1) + 1);
+    EmuHdlc* h = new EmuHdlc(HdlcPlan(lmin, lmax, nchan, max_bits, max_pdus, EMU_SCAN_T));
+    const HdlcPlan& pl = h->pl;
+    emu_alloc(h->st, pl.st);
+    emu_alloc(h->carry, pl.carry);
+    emu_alloc(h->srec, pl.srec);
+    emu_alloc(h->sbytes, pl.sbytes);
+    emu_alloc(h->cnt, pl.cnt);
+    emu_alloc(h->base, pl.base);
+    emu_alloc(h->count, pl.count);
+    emu_alloc(h->out, pl.out);
+    emu_alloc(h->out_bytes, pl.out_bytes);
+    emu_alloc(h->rules, pl.rules);
+    emu_alloc(h->sfix, pl.sfix);
+    h->fix.assign(pl.fix.n, -1);
     return h;
 }
 
 void emu_hdlc_destroy(void* hv) { delete (EmuHdlc*)hv; }
 
+// the rules and the mask as aisx_hdlc_batch_set_repair_events takes them, already checked by the caller; nrules == 0: off
+void emu_hdlc_set_repair(void* hv, const HdlcRule* rules, int nrules, int events)
+{
+    EmuHdlc* h = (EmuHdlc*)hv;
+    if (nrules == 0 && h->nrules > 0)
+        h->fix.assign(h->fix.size(), -1);
+    std::copy(rules, rules + nrules, h->rules.begin());
+    h->nrules = nrules;
+    h->events = events;
+    if (events != AISX_HDLC_EV_SINGLE) {
+        h->ev_tab.resize(h->pl.syn.n);
+        aisx::hdlc_event_table(events, h->ev_tab.data());
+    }
+}
+
 void emu_hdlc_process(void* hv, const unsigned char* bits, long stride, const int* nbits)
 {
     EmuHdlc* h = (EmuHdlc*)hv;
-    HdlcParams p;
-    p.bits = bits;
-    p.stride = stride;
-    p.nbits = nbits;
-    p.max_bits = h->max_bits;
-    p.lmin = h->lmin;
-    p.lmax = h->lmax;
-    p.st = h->st.data();
-    p.carry = h->carry.data();
-    p.carry_words = h->carry_words;
-    p.srec = h->srec.data();
-    p.rec_cap = h->rec_cap;
-    p.sbytes = h->sbytes.data();
-    p.byte_cap = h->byte_cap;
-    p.cnt = h->cnt.data();
-    p.nbytes = h->nbytes.data();
-    p.flags = h->count + 2;
-    run_grid(h->nchan, 1, HD_T, HD_LDS_BYTES, [&](EmuCtx& cx) { hdlc_deframe_body(cx, p); });
-    HdlcScanParams s;
-    s.cnt = p.cnt;
-    s.nbytes = p.nbytes;
-    s.rec_base = h->rec_base.data();
-    s.byte_base = h->byte_base.data();
-    s.nchan = h->nchan;
-    s.max_pdus = h->max_pdus;
-    s.count = h->count;
-    run_grid(1, 1, 64, 2 * 64 * 8, [&](EmuCtx& cx) { hdlc_scan_body(cx, s); }); // (the device runs HD_SCAN_T threads)
-    HdlcGatherParams g;
-    g.srec = h->srec.data();
-    g.rec_cap = h->rec_cap;
-    g.sbytes = h->sbytes.data();
-    g.byte_cap = h->byte_cap;
-    g.cnt = p.cnt;
-    g.nbytes = p.nbytes;
-    g.rec_base = s.rec_base;
-    g.byte_base = s.byte_base;
-    g.max_pdus = h->max_pdus;
-    g.out = h->out.data();
-    g.out_bytes = h->out_bytes.data();
-    run_grid(h->nchan, 1, HD_T, 64, [&](EmuCtx& cx) { hdlc_gather_body(cx, g); });
+    const bool single = h->events == AISX_HDLC_EV_SINGLE;
+    const HdlcBufs b = { h->st.data(),  h->carry.data(),     h->srec.data(), h->sbytes.data(), h->cnt.data(),
+                         h->base.data(), h->count.data(),     h->out.data(),  h->out_bytes.data(), h->fix.data(),
+                         h->rules.data(), h->sfix.data(),     single ? aisx::hdlc_syndrome_table() : h->ev_tab.data() };
+    h->pl.process(b, bits, stride, nbits, h->nrules, !single, [&](const PlanLaunch& l, const HdlcCall& c) {
+        run_grid(l.gx, l.gy, l.threads, l.lds, [&](EmuCtx& cx) {
+            switch (l.kernel) {
+            case HD_K_DEFRAME: hdlc_deframe_body(cx, c.p); break;
+            case HD_K_DEFRAME_REPAIR: hdlc_deframe_body<EmuCtx, true>(cx, c.p); break;
+            case HD_K_DEFRAME_EVENTS: hdlc_deframe_body<EmuCtx, true, true>(cx, c.p); break;
+            case HD_K_SCAN: hdlc_scan_body(cx, c.s); break;
+            case HD_K_GATHER: hdlc_gather_body(cx, c.g); break;
+            }
+        });
+        return true;
+    });
 }
 
-// count[0] found, [1] kept, [2] bad-count flag (cleared here); records and bytes of the kept ones
-void emu_hdlc_read(void* hv, HdlcRec* pdus, unsigned char* bytes, int* count)
+// count[0] found, [1] kept, [2] bad-count flag (cleared here); records, bytes and (fix != nullptr) marks of the kept ones
+void emu_hdlc_read(void* hv, HdlcRec* pdus, unsigned char* bytes, int* fix, int* count)
 {
     EmuHdlc* h = (EmuHdlc*)hv;
     for (int k = 0; k < 3; k++)
@@ -105,10 +98,27 @@ void emu_hdlc_read(void* hv, HdlcRec* pdus, unsigned char* bytes, int* count)
     h->count[2] = 0;
     const int kept = h->count[1];
     memcpy(pdus, h->out.data(), sizeof(HdlcRec) * kept);
+    if (fix)
+        memcpy(fix, h->fix.data(), sizeof(int) * kept);
     const long long nb = kept ? h->out[kept - 1].offset + h->out[kept - 1].len : 0;
     memcpy(bytes, h->out_bytes.data(), (size_t)nb);
 }
 
+// the host form's single-error table (not part of the C ABI), for the tests that compare tables with it
+void emu_hdlc_syndrome_table(unsigned short* out) { memcpy(out, aisx::hdlc_syndrome_table(), sizeof(unsigned short) * 65536); }
+
 int emu_hdlc_rec_size() { return (int)sizeof(HdlcRec); }
+int emu_hdlc_rule_size() { return (int)sizeof(HdlcRule); }
+
+// the plan at the device's constants: out[4] = carry_words, rec_cap, byte_cap, out_bytes_cap; 0 where it refuses
+int emu_hdlc_plan(int lmin, int lmax, int nchan, int max_bits, int max_pdus, long long* out)
+{
+    if (HdlcPlan::check(lmin, lmax, nchan, max_bits, max_pdus))
+        return 0;
+    const HdlcPlan pl(lmin, lmax, nchan, max_bits, max_pdus);
+    const long long v[4] = { pl.carry_words, pl.rec_cap, pl.byte_cap, pl.out_bytes_cap };
+    memcpy(out, v, sizeof v);
+    return 1;
+}
 
 }

@@ -1,5 +1,5 @@
 // events_san.cpp -- a stand-alone program for the sanitizers (make san): the host form of the error-event repair
-// (gr-ais_amd/csrc/aisx_framing.cpp) and the kernel bodies on the lane model (emul_hdlc_events.cpp) on the same ragged
+// (gr-ais_amd/csrc/aisx_framing.cpp) and the kernel bodies on the lane model (emul_hdlc.cpp) on the same ragged
 // multi-channel script -- frames of the rules' lengths with one planted event of every kind (at the frame's first bit,
 // across octets, in the FCS, at its last bit) or two, in noise, three calls per mask, the mask switched between them, the
 // rows off 16-byte alignment -- compared record for record, bytes and marks.  Prints "events_san ok".
@@ -7,7 +7,7 @@
 
 #include <random>
 
-#include "emul_hdlc_events.cpp"
+#include "emul_hdlc.cpp"
 
 namespace {
 
@@ -88,14 +88,14 @@ int main()
     for (int c = 0; c < nchan; c++)
         if (aisx_hdlc_create(&host[c], lmin, lmax) != AISX_OK)
             return 2;
-    void* lane = emu_hdlce_create(lmin, lmax, nchan, max_bits, max_pdus);
+    void* lane = emu_hdlc_create(lmin, lmax, nchan, max_bits, max_pdus);
     std::vector<unsigned char> rows((size_t)nchan * stride + 16), hbytes((size_t)max_pdus * lmax), lbytes((size_t)max_pdus * lmax + 1);
     std::vector<HdlcRec> recs(max_pdus);
     std::vector<int> n(nchan), offs(max_pdus + 1), lfix(max_pdus), hfix(max_pdus);
     long total = 0, fixed = 0;
     for (int call = 0; call < 8; call++) {
         const int nrules = call == 6 ? 0 : 5;
-        emu_hdlce_set_repair(lane, (const HdlcRule*)rules, nrules, masks[call]);
+        emu_hdlc_set_repair(lane, (const HdlcRule*)rules, nrules, masks[call]);
         unsigned char* base = rows.data() + (call % 3) * 5; // rows off 16-byte alignment
         for (int c = 0; c < nchan; c++) {
             if (aisx_hdlc_set_repair_events(host[c], rules, nrules, masks[call]) != AISX_OK)
@@ -105,9 +105,9 @@ int main()
             if (!s.empty())
                 memcpy(base + (size_t)c * stride, s.data(), s.size());
         }
-        emu_hdlce_process(lane, base, stride, n.data());
+        emu_hdlc_process(lane, base, stride, n.data());
         int count[3];
-        emu_hdlce_read(lane, recs.data(), lbytes.data(), lfix.data(), count);
+        emu_hdlc_read(lane, recs.data(), lbytes.data(), lfix.data(), count);
         int k = 0;
         for (int c = 0; c < nchan; c++) {
             int found = -1;
@@ -132,7 +132,7 @@ int main()
     }
     for (int c = 0; c < nchan; c++)
         aisx_hdlc_destroy(host[c]);
-    emu_hdlce_destroy(lane);
+    emu_hdlc_destroy(lane);
     if (total < 100 || fixed < 40) {
         printf("events_san: only %ld records, %ld repaired\n", total, fixed);
         return 1;

@@ -1,7 +1,8 @@
 // emul_nmea.cpp -- CPU model of the batched NMEA armouring (TEST INFRASTRUCTURE, see ../emul/emul.cpp): the kernel
-// bodies of gr-ais_amd/csrc/k_nmea.h run one OS thread per lane under the same EmuCtx, driven the way aisx_nmea.hip
-// drives them on the device (host memory in place of device memory).
+// bodies of gr-ais_amd/csrc/k_nmea.h run one OS thread per lane under the same EmuCtx, driven by the launch plan that
+// drives them on the device (NmeaPlan, k_nmea.h) with host memory in place of device memory.
 #include "../emul/emul.cpp"
+#include "../emul/emul_plan.h"
 #include "../../gr-ais_amd/csrc/k_nmea.h"
 
 namespace {
@@ -11,79 +12,48 @@ constexpr int EMU_W_T = 128;
 constexpr int EMU_W_GROUPS = 3;  // (the device takes up to NM_W_MAX_GROUPS: a few waves make every wave loop)
 
 struct EmuNmea {
-    int nchan, max_pdus, lmax;
-    long long text_cap;
-    std::vector<char> desig, text;
-    std::vector<unsigned char> dlen;
+    explicit EmuNmea(NmeaPlan&& plan) : pl(std::move(plan)) {}
+    const NmeaPlan pl;
+    std::vector<char> text;
     std::vector<HdlcRec> out;
-    int count[4] = { 0, 0, 0, 0 };
+    std::vector<int> count;
 };
 
 } // namespace
 
 extern "C" {
 
-// the argument checks and the text capacity are the product's (aisx_nmea_batch_create); returns nullptr where it
-// returns AISX_ERR_INVALID
+// returns nullptr where aisx_nmea_batch_create returns AISX_ERR_INVALID
 void* emu_nmea_create(const char* const* designators, int nchan, int max_pdus, int length_max, long text_cap)
 {
-    if (!designators || nchan < 1 || max_pdus < 1 || length_max < 2 || length_max > NM_MAX_OCTETS || text_cap < 0)
+    if (NmeaPlan::check(designators, nchan, max_pdus, length_max, text_cap) || nm_bad_designator(designators, nchan) >= 0)
         return nullptr;
-    int max_dlen = 0;
-    for (int c = 0; c < nchan; c++) {
-        const size_t n = designators[c] ? strnlen(designators[c], NM_DESIG + 1) : NM_DESIG + 1;
-        if (n > (size_t)NM_DESIG)
-            return nullptr;
-        max_dlen = std::max(max_dlen, (int)n);
-    }
-    EmuNmea* h = new EmuNmea();
-    h->nchan = nchan;
-    h->max_pdus = max_pdus;
-    h->lmax = length_max;
-    const long long worst = (long long)max_pdus * (nm_text_len(length_max - 1, max_dlen) + 1);
-    h->text_cap = text_cap == 0 || text_cap > worst ? worst : text_cap;
-    h->desig.assign((size_t)nchan * NM_DESIG, 0);
-    h->dlen.assign(nchan, 0);
-    for (int c = 0; c < nchan; c++) {
-        h->dlen[c] = (unsigned char)strlen(designators[c]);
-        memcpy(h->desig.data() + (size_t)c * NM_DESIG, designators[c], h->dlen[c]);
-    }
-    h->out.resize(max_pdus);
-    h->text.assign((size_t)h->text_cap, 0);
+    EmuNmea* h = new EmuNmea(NmeaPlan(designators, nchan, max_pdus, length_max, text_cap, EMU_SCAN_T, EMU_W_T, EMU_W_GROUPS));
+    emu_alloc(h->out, h->pl.out);
+    emu_alloc(h->text, h->pl.text);
+    emu_alloc(h->count, h->pl.count);
     return h;
 }
 
 void emu_nmea_destroy(void* hv) { delete (EmuNmea*)hv; }
 
-long emu_nmea_text_cap(void* hv) { return (long)((EmuNmea*)hv)->text_cap; }
+long emu_nmea_text_cap(void* hv) { return (long)((EmuNmea*)hv)->pl.text_cap; }
 
 int emu_nmea_text_len(int len, int dlen) { return nm_text_len(len, dlen); }
 
 void emu_nmea_process(void* hv, const HdlcRec* pdus, const unsigned char* bytes, const int* npdus, const int* nfound)
 {
     EmuNmea* h = (EmuNmea*)hv;
-    NmeaScanParams s;
-    s.in = pdus;
-    s.npdus = npdus;
-    s.nfound = nfound;
-    s.dlen = h->dlen.data();
-    s.nchan = h->nchan;
-    s.max_pdus = h->max_pdus;
-    s.max_len = h->lmax - 1;
-    s.text_cap = h->text_cap;
-    s.out = h->out.data();
-    s.count = h->count;
-    run_grid(1, 1, EMU_SCAN_T, (2 * (EMU_SCAN_T / 64) + 2) * 4, [&](EmuCtx& cx) { nmea_scan_body(cx, s); });
-    NmeaWriteParams w;
-    w.in = pdus;
-    w.bytes = bytes;
-    w.out = h->out.data();
-    w.count = h->count;
-    w.desig = h->desig.data();
-    w.dlen = h->dlen.data();
-    w.text = h->text.data();
-    w.nwaves = EMU_W_GROUPS * (EMU_W_T / 64);
-    run_grid(EMU_W_GROUPS, 1, EMU_W_T, 0, [&](EmuCtx& cx) { nmea_write_body(cx, w); });
+    const NmeaBufs b = { h->pl.desig_host.data(), h->pl.dlen_host.data(), h->out.data(), h->text.data(), h->count.data() };
+    h->pl.process(b, pdus, bytes, npdus, nfound, [&](const PlanLaunch& l, const NmeaCall& c) {
+        run_grid(l.gx, l.gy, l.threads, l.lds, [&](EmuCtx& cx) {
+            if (l.kernel == NM_K_SCAN)
+                nmea_scan_body(cx, c.s);
+            else
+                nmea_write_body(cx, c.w);
+        });
+        return true;
+    });
 }
 
 // count[0] found, [1] records written, [2] bad-input flag (cleared here); the records written and the text up to
@@ -99,6 +69,17 @@ void emu_nmea_read(void* hv, HdlcRec* recs, char* text, int* count)
     const HdlcRec* last = kept ? &h->out[kept - 1] : nullptr;
     const long long nt = last ? last->offset + last->len + (last->len > 0) : 0;
     memcpy(text, h->text.data(), (size_t)nt);
+}
+
+// the plan at the device's constants: out[2] = text_cap, write_groups; 0 where it refuses
+int emu_nmea_plan(const char* const* designators, int nchan, int max_pdus, int length_max, long text_cap, long long* out)
+{
+    if (NmeaPlan::check(designators, nchan, max_pdus, length_max, text_cap) || nm_bad_designator(designators, nchan) >= 0)
+        return 0;
+    const NmeaPlan pl(designators, nchan, max_pdus, length_max, text_cap);
+    out[0] = pl.text_cap;
+    out[1] = pl.write_groups;
+    return 1;
 }
 
 }

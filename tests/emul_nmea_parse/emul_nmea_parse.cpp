@@ -1,7 +1,9 @@
 // emul_nmea_parse.cpp -- CPU model of the batched NMEA parser (TEST INFRASTRUCTURE, see ../emul/emul.cpp): the kernel
-// bodies of gr-ais_amd/csrc/k_nmea_parse.h run one OS thread per lane under the same EmuCtx, driven the way
-// aisx_nmea_parse.hip drives them on the device (host memory in place of device memory).
+// bodies of gr-ais_amd/csrc/k_nmea_parse.h run one OS thread per lane under the same EmuCtx, driven by the launch plan that
+// drives them on the device (NmpPlan, k_nmea_parse.h: its four grids, ngroups and nwaves as it sets them between the
+// launches) with host memory in place of device memory.
 #include "../emul/emul.cpp"
+#include "../emul/emul_plan.h"
 #include "../../gr-ais_amd/csrc/k_nmea_parse.h"
 
 namespace {
@@ -11,66 +13,56 @@ constexpr int EMU_SCAN_T = 128; // (the device runs NP_SCAN_T)
 constexpr int EMU_GROUPS = 3;   // (the device takes up to NP_MAX_GROUPS: a few make every strided loop turn)
 
 struct EmuNmp {
-    int nchan, lmax, max_line, flags, max_lines, max_pdus;
-    long long max_bytes;
-    std::vector<char> desig;
-    std::vector<unsigned char> dlen, lcarry, gcarry, bytes;
+    explicit EmuNmp(NmpPlan&& plan) : pl(std::move(plan)) {}
+    const NmpPlan pl;
+    std::vector<unsigned char> lcarry, gcarry, bytes;
     std::vector<NmpState> st;
     std::vector<int> tcount, toff, meta, cidx, aux, count, mlen, tl, bstat;
     std::vector<long long> lend, pos, tm, times, tlb;
     std::vector<NmpKey> key;
     std::vector<HdlcRec> rec;
-    NmpNext next;
+    std::vector<NmpNext> next;
 };
 
 void emu_nmp_clear(EmuNmp* h)
 {
-    h->st.assign(2, NmpState{});
-    h->meta.assign(NP_M_N, 0);
-    h->count.assign(NP_NCNT, 0);
-    h->next = NmpNext{};
+    emu_alloc(h->st, h->pl.st);
+    emu_alloc(h->meta, h->pl.meta);
+    emu_alloc(h->count, h->pl.count);
 }
 
 } // namespace
 
 extern "C" {
 
-// (the arguments are taken as they come: the product's checks are the product's, aisx_nmea_parse_batch_create)
+// returns nullptr where aisx_nmea_parse_batch_create returns AISX_ERR_INVALID
 void* emu_nmp_create(const char* const* designators, int nchan, int length_max, int max_line, int flags, long max_bytes,
                      int max_lines, int max_pdus)
 {
-    EmuNmp* h = new EmuNmp();
-    h->nchan = nchan;
-    h->lmax = length_max;
-    h->max_line = max_line;
-    h->flags = flags;
-    h->max_bytes = max_bytes;
-    h->max_lines = max_lines;
-    h->max_pdus = max_pdus;
-    h->desig.assign((size_t)nchan * NM_DESIG, 0);
-    h->dlen.assign(nchan, 0);
-    for (int c = 0; c < nchan; c++) {
-        h->dlen[c] = (unsigned char)strlen(designators[c]);
-        memcpy(h->desig.data() + (size_t)c * NM_DESIG, designators[c], h->dlen[c]);
-    }
-    const size_t ntiles = (size_t)((max_bytes + EMU_T * NP_CHUNK - 1) / (EMU_T * NP_CHUNK));
-    h->lcarry.assign(2 * (size_t)max_line, 0);
-    h->gcarry.assign(2 * (size_t)NP_GMAX * max_line, 0);
-    h->bytes.assign((size_t)max_pdus * (length_max - 1), 0);
-    h->tcount.assign(ntiles, 0);
-    h->toff.assign(ntiles, 0);
-    h->cidx.assign(max_lines, 0);
-    h->mlen.assign((size_t)max_lines + NP_GMAX, 0);
-    h->tl.assign(((size_t)max_lines + NP_GMAX + EMU_T - 1) / EMU_T, 0);
-    h->tlb.assign(h->tl.size(), 0);
-    h->bstat.assign((size_t)NP_MAX_GROUPS * 8, 0);
-    h->aux.assign(max_pdus, 0);
-    h->lend.assign(max_lines, 0);
-    h->pos.assign(max_lines, 0);
-    h->tm.assign(max_lines, 0);
-    h->times.assign(max_pdus, 0);
-    h->key.assign(max_lines, NmpKey{});
-    h->rec.assign(max_pdus, HdlcRec{});
+    if (NmpPlan::check(designators, nchan, length_max, max_line, flags, max_bytes, max_lines, max_pdus) ||
+        nm_bad_designator(designators, nchan) >= 0)
+        return nullptr;
+    EmuNmp* h = new EmuNmp(NmpPlan(designators, nchan, length_max, max_line, flags, max_bytes, max_lines, max_pdus, EMU_T, EMU_SCAN_T,
+                                   EMU_GROUPS));
+    const NmpPlan& pl = h->pl;
+    emu_alloc(h->lcarry, pl.lcarry);
+    emu_alloc(h->gcarry, pl.gcarry);
+    emu_alloc(h->bytes, pl.bytes);
+    emu_alloc(h->tcount, pl.tcount);
+    emu_alloc(h->toff, pl.toff);
+    emu_alloc(h->cidx, pl.cidx);
+    emu_alloc(h->mlen, pl.mlen);
+    emu_alloc(h->tl, pl.tl);
+    emu_alloc(h->tlb, pl.tlb);
+    emu_alloc(h->bstat, pl.bstat);
+    emu_alloc(h->aux, pl.aux);
+    emu_alloc(h->lend, pl.lend);
+    emu_alloc(h->pos, pl.pos);
+    emu_alloc(h->tm, pl.tm);
+    emu_alloc(h->times, pl.times);
+    emu_alloc(h->key, pl.key);
+    emu_alloc(h->rec, pl.rec);
+    emu_alloc(h->next, pl.next);
     emu_nmp_clear(h);
     return h;
 }
@@ -82,53 +74,30 @@ void emu_nmp_reset(void* hv) { emu_nmp_clear((EmuNmp*)hv); }
 void emu_nmp_process(void* hv, const unsigned char* text, const long long* nbytes)
 {
     EmuNmp* h = (EmuNmp*)hv;
-    NmpParams p;
-    p.text = text;
-    p.nbytes = nbytes;
-    p.max_bytes = h->max_bytes;
-    p.max_lines = h->max_lines;
-    p.max_pdus = h->max_pdus;
-    p.max_len = h->lmax - 1;
-    p.max_line = h->max_line;
-    p.flags = h->flags;
-    p.nchan = h->nchan;
-    p.desig = h->desig.data();
-    p.dlen = h->dlen.data();
-    p.st = h->st.data();
-    p.lcarry = h->lcarry.data();
-    p.gcarry = h->gcarry.data();
-    p.tcount = h->tcount.data();
-    p.toff = h->toff.data();
-    p.meta = h->meta.data();
-    p.lend = h->lend.data();
-    p.key = h->key.data();
-    p.pos = h->pos.data();
-    p.tm = h->tm.data();
-    p.cidx = h->cidx.data();
-    p.mlen = h->mlen.data();
-    p.tl = h->tl.data();
-    p.tlb = h->tlb.data();
-    p.bstat = h->bstat.data();
-    p.rec = h->rec.data();
-    p.aux = h->aux.data();
-    p.times = h->times.data();
-    p.bytes = h->bytes.data();
-    p.count = h->count.data();
-    p.next = &h->next;
-    p.ngroups = EMU_GROUPS;
-    p.nwaves = EMU_GROUPS * (EMU_T / 64);
-    run_grid(EMU_GROUPS, 1, EMU_T, NP_LDS_BYTES, [&](EmuCtx& cx) { nmp_count_body(cx, p); });
-    run_grid(1, 1, EMU_SCAN_T, NP_LDS_BYTES, [&](EmuCtx& cx) { nmp_scan_body(cx, p, EMU_T); });
-    run_grid(EMU_GROUPS, 1, EMU_T, NP_LDS_BYTES, [&](EmuCtx& cx) { nmp_index_body(cx, p); });
-    run_grid(EMU_GROUPS, 1, EMU_T, NP_LDS_BYTES, [&](EmuCtx& cx) { nmp_parse_body(cx, p); });
-    run_grid(EMU_GROUPS, 1, EMU_T, NP_LDS_BYTES, [&](EmuCtx& cx) { nmp_gcount_body(cx, p); });
-    run_grid(1, 1, EMU_SCAN_T, NP_LDS_BYTES, [&](EmuCtx& cx) { nmp_gscan1_body(cx, p, EMU_T); });
-    run_grid(EMU_GROUPS, 1, EMU_T, NP_LDS_BYTES, [&](EmuCtx& cx) { nmp_gcompact_body(cx, p); });
-    run_grid(EMU_GROUPS, 1, EMU_T, NP_LDS_BYTES, [&](EmuCtx& cx) { nmp_gmsg_body(cx, p); });
-    run_grid(1, 1, EMU_SCAN_T, NP_LDS_BYTES, [&](EmuCtx& cx) { nmp_gscan2_body(cx, p, EMU_T); });
-    run_grid(EMU_GROUPS, 1, EMU_T, NP_LDS_BYTES, [&](EmuCtx& cx) { nmp_gplace_body(cx, p); });
-    run_grid(EMU_GROUPS, 1, EMU_T, NP_LDS_BYTES, [&](EmuCtx& cx) { nmp_write_body(cx, p); });
-    run_grid(1, 1, 64, NP_LDS_BYTES, [&](EmuCtx& cx) { nmp_carry_body(cx, p); });
+    const NmpBufs b = { h->pl.desig_host.data(), h->pl.dlen_host.data(), h->st.data(), h->lcarry.data(), h->gcarry.data(),
+                        h->tcount.data(), h->toff.data(), h->meta.data(), h->lend.data(), h->key.data(), h->pos.data(), h->tm.data(),
+                        h->cidx.data(), h->mlen.data(), h->tl.data(), h->tlb.data(), h->bstat.data(), h->rec.data(), h->aux.data(),
+                        h->times.data(), h->bytes.data(), h->count.data(), h->next.data() };
+    const int T = h->pl.threads; // (the scans are told the threads of the kernels whose tile sums they scan)
+    h->pl.process(b, text, nbytes, [&](const PlanLaunch& l, const NmpParams& p) {
+        run_grid(l.gx, l.gy, l.threads, l.lds, [&](EmuCtx& cx) {
+            switch (l.kernel) {
+            case NP_K_COUNT: nmp_count_body(cx, p); break;
+            case NP_K_SCAN: nmp_scan_body(cx, p, T); break;
+            case NP_K_INDEX: nmp_index_body(cx, p); break;
+            case NP_K_PARSE: nmp_parse_body(cx, p); break;
+            case NP_K_GCOUNT: nmp_gcount_body(cx, p); break;
+            case NP_K_GSCAN1: nmp_gscan1_body(cx, p, T); break;
+            case NP_K_GCOMPACT: nmp_gcompact_body(cx, p); break;
+            case NP_K_GMSG: nmp_gmsg_body(cx, p); break;
+            case NP_K_GSCAN2: nmp_gscan2_body(cx, p, T); break;
+            case NP_K_GPLACE: nmp_gplace_body(cx, p); break;
+            case NP_K_WRITE: nmp_write_body(cx, p); break;
+            case NP_K_CARRY: nmp_carry_body(cx, p); break;
+            }
+        });
+        return true;
+    });
 }
 
 // counts [NP_NCNT] (the bad-input flag is cleared here), the records kept, their bytes and times
@@ -143,6 +112,30 @@ void emu_nmp_read(void* hv, HdlcRec* recs, unsigned char* bytes, long long* time
     memcpy(times, h->times.data(), sizeof(long long) * kept);
     const long long nb = kept ? h->rec[kept - 1].offset + h->rec[kept - 1].len : 0;
     memcpy(bytes, h->bytes.data(), (size_t)nb);
+}
+
+// the plan at the device's constants: out[6] = ntiles, nlt, tile_groups, line_groups, ltile_groups, pdu_groups, then
+// (grid, ngroups, nwaves) of each of the call's launches in order, out[6 + 3 * NP_NKERNELS] in all; 0 where it refuses
+int emu_nmp_plan(const char* const* designators, int nchan, int length_max, int max_line, int flags, long max_bytes, int max_lines,
+                 int max_pdus, long long* out)
+{
+    if (NmpPlan::check(designators, nchan, length_max, max_line, flags, max_bytes, max_lines, max_pdus) ||
+        nm_bad_designator(designators, nchan) >= 0)
+        return 0;
+    const NmpPlan pl(designators, nchan, length_max, max_line, flags, max_bytes, max_lines, max_pdus);
+    const long long v[6] = { pl.ntiles, pl.nlt, pl.tile_groups, pl.line_groups, pl.ltile_groups, pl.pdu_groups };
+    memcpy(out, v, sizeof v);
+    int k = 0;
+    pl.process(NmpBufs{}, nullptr, nullptr, [&](const PlanLaunch& l, const NmpParams& p) {
+        if (l.kernel != k) // (the kernels in their order)
+            return false;
+        long long* o = out + 6 + 3 * k++;
+        o[0] = l.gx;
+        o[1] = p.ngroups;
+        o[2] = p.nwaves;
+        return true;
+    });
+    return k == NP_NKERNELS;
 }
 
 }

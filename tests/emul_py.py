@@ -2,74 +2,47 @@
 product's kernel-body templates (gr-ais_amd/csrc/k_*.h) one OS thread per lane.
 TEST INFRASTRUCTURE for the -m "not gpu" suite."""
 import ctypes as C
-import glob
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL_DIR = os.path.join(_HERE, "emul")
-CSRC = os.path.join(os.path.dirname(_HERE), "gr-ais_amd", "csrc")
-_LIB = None
+import emul_load
+from emul_load import f32, f64, i32, lng, u32, u64, vp
 
 TAG_DTYPE = np.dtype([("offset", "<u8"), ("value", "<f8"), ("key", "<i4"), ("chan", "<i4")])
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        so = os.path.join(EMUL_DIR, "libaisx_emul.so")
-        deps = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(EMUL_DIR, "emul.cpp")]
-        if (not os.path.exists(so)) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            subprocess.check_call(["make", "-C", EMUL_DIR, "-s", "-B"])
-        L = C.CDLL(so)
-        vp, i32, f32, u32, u64, lng = C.c_void_p, C.c_int, C.c_float, C.c_uint, C.c_uint64, C.c_long
-        L.emu_corr_create.restype = vp
-        L.emu_corr_create.argtypes = [vp, i32, f32, u32, f32, i32]
-        L.emu_corr_destroy.argtypes = [vp]
-        L.emu_corr_set_dma.argtypes = [i32]
-        L.emu_corr_threshold.restype = f32
-        L.emu_corr_threshold.argtypes = [vp]
-        L.emu_corr_output_multiple.restype = i32
-        L.emu_corr_output_multiple.argtypes = [vp]
-        L.emu_corr_symbols.argtypes = [vp, vp]
-        L.emu_corr_grid.argtypes = [i32, i32, i32, i32, i32, vp, vp]
-        L.emu_corr_process.restype = i32
-        L.emu_corr_process.argtypes = [vp, vp, lng, vp, lng, vp, lng, i32, vp, i32, vp, i32]
-        L.emu_msk_create.restype = vp
-        L.emu_msk_create.argtypes = [f32, f32, f32, i32, i32]
-        L.emu_msk_destroy.argtypes = [vp]
-        L.emu_msk_set_lpw.argtypes = [vp, i32]
-        L.emu_msk_set_time_parallel.argtypes = [vp, i32, i32, i32]
-        L.emu_msk_tp_stats.argtypes = [vp, vp]
-        L.emu_msk_set_tp_join.argtypes = [vp, i32]
-        L.emu_msk_process_stream.restype = i32
-        L.emu_msk_process_stream.argtypes = [vp, vp, lng, i32, vp, vp, i32, vp, vp, vp, vp, lng, vp, vp]
-        L.emu_msk_general_work.restype = i32
-        L.emu_msk_general_work.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, u64, vp, vp]
-        f64 = C.c_double
-        L.emu_agc_create.restype = vp
-        L.emu_agc_create.argtypes = [i32, f32, i32]
-        L.emu_agc_destroy.argtypes = [vp]
-        L.emu_agc_process.argtypes = [vp, vp, lng, vp, lng, i32]
-        L.emu_agc_set_streaming.argtypes = [vp, i32]
-        L.emu_fs_agc_process.restype = i32
-        L.emu_fs_agc_process.argtypes = [vp, vp, vp, lng, i32, vp, lng, vp, lng]
-        L.emu_fs_create.restype = vp
-        L.emu_fs_create.argtypes = [f64, f64, i32, i32, i32]
-        L.emu_fs_destroy.argtypes = [vp]
-        L.emu_fs_process.restype = i32
-        L.emu_fs_process.argtypes = [vp, vp, lng, i32, vp, lng, vp, lng]
-        L.emu_freqest_work.argtypes = [vp, vp, lng, vp, lng, i32]
-        L.emu_freqest_any.argtypes = [vp, lng, vp, lng, i32, i32, i32, f32, i32]
-        L.emu_pfb_create.restype = vp
-        L.emu_pfb_create.argtypes = [i32, vp, i32, i32]
-        L.emu_pfb_destroy.argtypes = [vp]
-        L.emu_pfb_process.restype = i32
-        L.emu_pfb_process.argtypes = [vp, vp, lng, i32, vp, lng]
-        _LIB = L
-    return _LIB
+    return emul_load.load("emul", [
+        ("emu_corr_create", vp, [vp, i32, f32, u32, f32, i32]),
+        ("emu_corr_destroy", None, [vp]),
+        ("emu_corr_set_dma", None, [i32]),
+        ("emu_corr_threshold", f32, [vp]),
+        ("emu_corr_output_multiple", i32, [vp]),
+        ("emu_corr_symbols", None, [vp, vp]),
+        ("emu_corr_grid", None, [i32, i32, i32, i32, i32, vp, vp]),
+        ("emu_corr_process", i32, [vp, vp, lng, vp, lng, vp, lng, i32, vp, i32, vp, i32]),
+        ("emu_msk_create", vp, [f32, f32, f32, i32, i32]),
+        ("emu_msk_destroy", None, [vp]),
+        ("emu_msk_set_lpw", None, [vp, i32]),
+        ("emu_msk_set_time_parallel", None, [vp, i32, i32, i32]),
+        ("emu_msk_tp_stats", None, [vp, vp]),
+        ("emu_msk_set_tp_join", None, [vp, i32]),
+        ("emu_msk_process_stream", i32, [vp, vp, lng, i32, vp, vp, i32, vp, vp, vp, vp, lng, vp, vp]),
+        ("emu_msk_general_work", i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, u64, vp, vp]),
+        ("emu_agc_create", vp, [i32, f32, i32]),
+        ("emu_agc_destroy", None, [vp]),
+        ("emu_agc_process", None, [vp, vp, lng, vp, lng, i32]),
+        ("emu_agc_set_streaming", None, [vp, i32]),
+        ("emu_fs_agc_process", i32, [vp, vp, vp, lng, i32, vp, lng, vp, lng]),
+        ("emu_fs_create", vp, [f64, f64, i32, i32, i32]),
+        ("emu_fs_destroy", None, [vp]),
+        ("emu_fs_process", i32, [vp, vp, lng, i32, vp, lng, vp, lng]),
+        ("emu_freqest_work", None, [vp, vp, lng, vp, lng, i32]),
+        ("emu_freqest_any", None, [vp, lng, vp, lng, i32, i32, i32, f32, i32]),
+        ("emu_pfb_create", vp, [i32, vp, i32, i32]),
+        ("emu_pfb_destroy", None, [vp]),
+        ("emu_pfb_process", i32, [vp, vp, lng, i32, vp, lng]),
+    ])
 
 
 def _p(a):

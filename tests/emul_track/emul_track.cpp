@@ -1,8 +1,9 @@
 // emul_track.cpp -- CPU model of the vessel table in device memory (TEST INFRASTRUCTURE, see ../emul/emul.cpp): the
-// kernel bodies of gr-ais_amd/csrc/k_track.h run one OS thread per lane, driven the way aisx_track.hip drives them on the
-// device (host memory in place of device memory).  The lanes of a workgroup are free-running threads, so the races on a
-// hash slot, a first row and a winner cell are real here.
+// kernel bodies of gr-ais_amd/csrc/k_track.h run one OS thread per lane, driven by the launch plan that drives them on the
+// device (TrkPlan, k_track.h) with host memory in place of device memory.  The lanes of a workgroup are free-running
+// threads, so the races on a hash slot, a first row and a winner cell are real here.
 #include "../emul/emul.cpp"
+#include "../emul/emul_plan.h"
 #include "../../gr-ais_amd/csrc/k_track.h"
 
 namespace {
@@ -32,80 +33,68 @@ struct TrkCtx : EmuCtx {
 };
 
 struct EmuTrk {
-    int capacity, max_rows, hbits, bbits, row_groups, cap_groups, cur = 0;
+    explicit EmuTrk(const TrkPlan& plan) : pl(plan) {}
+    TrkPlan pl;
     std::vector<int32_t> tab[2], hkey, bkey, gcols;
     std::vector<uint32_t> strs[2], gstrs;
-    std::vector<int> hval, bfirst, bval, bj, rslot, bsum, win, changed;
-    int count[TRK_COUNT_WORDS] = {};
+    std::vector<int> hval, bfirst, bval, bj, rslot, bsum, win, changed, count;
 };
 
-TrkParams params(EmuTrk* h)
+TrkBufs bufs(EmuTrk* h)
 {
-    TrkParams p = {};
-    p.capacity = h->capacity;
-    p.max_rows = h->max_rows;
-    p.tab = h->tab[h->cur].data();
-    p.strs = h->strs[h->cur].data();
-    p.hkey = h->hkey.data();
-    p.hval = h->hval.data();
-    p.hbits = h->hbits;
-    p.bkey = h->bkey.data();
-    p.bfirst = h->bfirst.data();
-    p.bval = h->bval.data();
-    p.bj = h->bj.data();
-    p.bbits = h->bbits;
-    p.rslot = h->rslot.data();
-    p.bsum = h->bsum.data();
-    p.nbmax = std::max(h->row_groups, h->cap_groups);
-    p.win = h->win.data();
-    p.changed = h->changed.data();
-    p.count = h->count;
-    return p;
+    return TrkBufs{ { h->tab[0].data(), h->tab[1].data() }, { h->strs[0].data(), h->strs[1].data() }, h->hkey.data(), h->hval.data(),
+                    h->bkey.data(), h->bfirst.data(), h->bval.data(), h->bj.data(), h->rslot.data(), h->bsum.data(), h->win.data(),
+                    h->changed.data(), h->gcols.data(), h->gstrs.data(), h->count.data() };
 }
 
-template <class Body>
-void run(int groups, Body body)
+// a launch of the plan's: the body of its id
+bool run(const PlanLaunch& l, const TrkCall& c)
 {
-    run_grid(groups, 1, TRK_T, TRK_LDS_BYTES, [&](EmuCtx& cx) {
-        TrkCtx tc(cx);
-        body(tc);
+    run_grid(l.gx, l.gy, l.threads, l.lds, [&](EmuCtx& ec) {
+        TrkCtx cx(ec);
+        switch (l.kernel) {
+        case TRK_K_CLEAR: trk_clear_body(cx, c.p); break;
+        case TRK_K_FIND: trk_find_body(cx, c.p); break;
+        case TRK_K_CLASSIFY: trk_classify_body(cx, c.p); break;
+        case TRK_K_ASSIGN: trk_assign_body(cx, c.p); break;
+        case TRK_K_WINNER: trk_winner_body(cx, c.p); break;
+        case TRK_K_APPLY: trk_apply_body(cx, c.p); break;
+        case TRK_K_KEEP: trk_keep_body(cx, c.p, c.min_stamp); break;
+        case TRK_K_COMPACT: trk_compact_body(cx, c.p, c.min_stamp); break;
+        case TRK_K_GATHER: trk_gather_body(cx, c.p); break;
+        }
     });
+    return true;
 }
 
 } // namespace
 
 extern "C" {
 
-// the argument checks are the product's (aisx_track_batch_create); returns nullptr where it returns AISX_ERR_INVALID
+// returns nullptr where aisx_track_batch_create returns AISX_ERR_INVALID
 void* emu_trk_create(int capacity, int max_rows)
 {
-    if (capacity < 1 || capacity > TRK_MAX || max_rows < 1 || max_rows > TRK_MAX)
+    if (TrkPlan::check(capacity, max_rows))
         return nullptr;
-    EmuTrk* h = new EmuTrk();
-    h->capacity = capacity;
-    h->max_rows = max_rows;
-    h->hbits = trk_hash_bits(capacity);
-    h->bbits = trk_hash_bits(max_rows);
-    h->row_groups = (max_rows + TRK_T - 1) / TRK_T;
-    h->cap_groups = (capacity + TRK_T - 1) / TRK_T;
-    const size_t H = (size_t)1 << h->hbits, B = (size_t)1 << h->bbits, R = (size_t)max_rows, C = (size_t)capacity;
-    const int junk = 0x5a5a5a5a; // (what is not written shows)
+    EmuTrk* h = new EmuTrk(TrkPlan(capacity, max_rows));
+    const TrkPlan& pl = h->pl;
     for (int k = 0; k < 2; k++) {
-        h->tab[k].assign(TRK_NCOL * C, junk);
-        h->strs[k].assign(MSG_STR_WORDS * C, 0x5a5a5a5au);
+        emu_alloc(h->tab[k], pl.tab);
+        emu_alloc(h->strs[k], pl.strs);
     }
-    h->hkey.assign(H, TRK_EMPTY);
-    h->hval.assign(H, junk);
-    h->bkey.assign(B, junk);
-    h->bfirst.assign(B, junk);
-    h->bval.assign(B, junk);
-    h->bj.assign(B, junk);
-    h->rslot.assign(R, junk);
-    h->bsum.assign(2 * (size_t)std::max(h->row_groups, h->cap_groups), junk);
-    h->win.assign(TRK_NWIN * R, junk);
-    h->changed.assign(R, junk);
-    h->gcols.assign(TRK_NCOL * R, junk);
-    h->gstrs.assign(MSG_STR_WORDS * R, 0x5a5a5a5au);
+    h->hkey.assign(pl.hkey.n, TRK_EMPTY);
+    emu_alloc(h->hval, pl.hval);
+    emu_alloc(h->bkey, pl.bkey);
+    emu_alloc(h->bfirst, pl.bfirst);
+    emu_alloc(h->bval, pl.bval);
+    emu_alloc(h->bj, pl.bj);
+    emu_alloc(h->rslot, pl.rslot);
+    emu_alloc(h->bsum, pl.bsum);
+    emu_alloc(h->win, pl.win);
+    emu_alloc(h->changed, pl.changed);
+    emu_alloc(h->gcols, pl.gcols);
+    emu_alloc(h->gstrs, pl.gstrs);
+    emu_alloc(h->count, pl.count);
     return h;
 }
 
@@ -115,32 +104,13 @@ void emu_trk_process(void* hv, const int32_t* cols, long col_stride, const uint3
                      int32_t stamp)
 {
     EmuTrk* h = (EmuTrk*)hv;
-    TrkParams p = params(h);
-    p.in_cols = cols;
-    p.in_stride = col_stride;
-    p.in_strs = strs;
-    p.in_recs = recs;
-    p.nrows = nrows;
-    p.stamp = stamp;
-    p.grid = h->row_groups;
-    run(h->row_groups, [&](TrkCtx& cx) { trk_clear_body(cx, p); });
-    run(h->row_groups, [&](TrkCtx& cx) { trk_find_body(cx, p); });
-    run(h->row_groups, [&](TrkCtx& cx) { trk_classify_body(cx, p); });
-    run(h->row_groups, [&](TrkCtx& cx) { trk_assign_body(cx, p); });
-    run(h->row_groups, [&](TrkCtx& cx) { trk_winner_body(cx, p); });
-    run(h->row_groups, [&](TrkCtx& cx) { trk_apply_body(cx, p); });
+    h->pl.process(bufs(h), cols, col_stride, strs, recs, nrows, stamp, run);
 }
 
 void emu_trk_expire(void* hv, int32_t min_stamp)
 {
     EmuTrk* h = (EmuTrk*)hv;
-    TrkParams p = params(h);
-    p.tab2 = h->tab[h->cur ^ 1].data();
-    p.strs2 = h->strs[h->cur ^ 1].data();
-    p.grid = h->cap_groups;
-    run(h->cap_groups, [&](TrkCtx& cx) { trk_keep_body(cx, p, min_stamp); });
-    run(h->cap_groups, [&](TrkCtx& cx) { trk_compact_body(cx, p, min_stamp); });
-    h->cur ^= 1;
+    h->pl.expire(bufs(h), min_stamp, run);
 }
 
 // count [TRK_NCNT] (the bad-input flag cleared here); the whole table, written or not: cols [TRK_NCOL][capacity],
@@ -148,31 +118,38 @@ void emu_trk_expire(void* hv, int32_t min_stamp)
 void emu_trk_read(void* hv, int32_t* cols, char* strs, int* changed, int* count)
 {
     EmuTrk* h = (EmuTrk*)hv;
-    memcpy(count, h->count, sizeof(int) * TRK_NCNT);
+    memcpy(count, h->count.data(), sizeof(int) * TRK_NCNT);
     h->count[TN_BAD] = 0;
-    memcpy(cols, h->tab[h->cur].data(), sizeof(int32_t) * h->tab[h->cur].size());
-    memcpy(strs, h->strs[h->cur].data(), sizeof(uint32_t) * h->strs[h->cur].size());
-    memcpy(changed, h->changed.data(), sizeof(int) * h->changed.size());
+    memcpy(cols, h->tab[h->pl.cur].data(), sizeof(int32_t) * h->pl.tab.n);
+    memcpy(strs, h->strs[h->pl.cur].data(), sizeof(uint32_t) * h->pl.strs.n);
+    memcpy(changed, h->changed.data(), sizeof(int) * h->pl.changed.n);
 }
 
 // one cell of the table set from outside (a count just short of saturation cannot be reached by feeding rows)
 void emu_trk_poke(void* hv, int col, int vessel, int32_t value)
 {
     EmuTrk* h = (EmuTrk*)hv;
-    h->tab[h->cur][(size_t)col * h->capacity + vessel] = value;
+    h->tab[h->pl.cur][(size_t)col * h->pl.capacity + vessel] = value;
 }
 
 // the gather of aisx_track_batch_read_changed: cols [TRK_NCOL][max_rows], strs [max_rows][MSG_STR]
 void emu_trk_gather(void* hv, int32_t* cols, char* strs)
 {
     EmuTrk* h = (EmuTrk*)hv;
-    TrkParams p = params(h);
-    p.tab2 = h->gcols.data();
-    p.strs2 = h->gstrs.data();
-    p.grid = h->row_groups;
-    run(h->row_groups, [&](TrkCtx& cx) { trk_gather_body(cx, p); });
-    memcpy(cols, h->gcols.data(), sizeof(int32_t) * h->gcols.size());
-    memcpy(strs, h->gstrs.data(), sizeof(uint32_t) * h->gstrs.size());
+    h->pl.gather(bufs(h), run);
+    memcpy(cols, h->gcols.data(), sizeof(int32_t) * h->pl.gcols.n);
+    memcpy(strs, h->gstrs.data(), sizeof(uint32_t) * h->pl.gstrs.n);
+}
+
+// the plan: out[7] = hbits, bbits, row_groups, cap_groups, clear_groups, the length of bsum, nbmax; 0 where it refuses
+int emu_trk_plan(int capacity, int max_rows, long long* out)
+{
+    if (TrkPlan::check(capacity, max_rows))
+        return 0;
+    const TrkPlan pl(capacity, max_rows);
+    const long long v[7] = { pl.hbits, pl.bbits, pl.row_groups, pl.cap_groups, pl.clear_groups, (long long)pl.bsum.n, pl.nbmax };
+    memcpy(out, v, sizeof v);
+    return 1;
 }
 
 }

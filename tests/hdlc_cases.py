@@ -3,10 +3,28 @@ tests/test_gpu_hdlc_batch.py on the device), the per-channel host reference (one
 channel, the specification) and a small Python restatement of it that also tells the end bit of each frame."""
 import numpy as np
 
+import emul_load
 import synth
+from emul_load import i32, lng, vp
 
 REC_DTYPE = np.dtype([("end_bit", "<u8"), ("offset", "<i8"), ("chan", "<i4"), ("len", "<i4")])
 FLAG = [0, 1, 1, 1, 1, 1, 1, 0]
+
+
+def emu():
+    """the CPU lane model of the batched deframer (tests/emul_hdlc): one library for the plain, the single-bit and the
+    event tests"""
+    L = emul_load.load("emul_hdlc", [
+        ("emu_hdlc_create", vp, [i32, i32, i32, i32, i32]),
+        ("emu_hdlc_destroy", None, [vp]),
+        ("emu_hdlc_set_repair", None, [vp, vp, i32, i32]),
+        ("emu_hdlc_process", None, [vp, vp, lng, vp]),
+        ("emu_hdlc_read", None, [vp, vp, vp, vp, vp]),
+        ("emu_hdlc_syndrome_table", None, [vp]),
+        ("emu_hdlc_plan", i32, [i32, i32, i32, i32, i32, vp]),
+    ], extra_deps=["aisx_framing.cpp", "../../include/aisx.h"])
+    assert L.emu_hdlc_rec_size() == REC_DTYPE.itemsize
+    return L
 
 
 def octets_to_bits(octets):

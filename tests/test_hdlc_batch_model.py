@@ -3,9 +3,6 @@
 channel fed the same bits call by call) and, on the short streams, a Python restatement that also tells each
 frame's end bit.  Plus the C ABI's argument checks and its refusal without a device.  -m "not gpu"."""
 import ctypes as C
-import glob
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,29 +10,7 @@ import pytest
 import hdlc_cases as hc
 import torch  # noqa: F401  (before libaisx.so: one HIP runtime in the process)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL = os.path.join(HERE, "emul_hdlc")
-CSRC = os.path.join(os.path.dirname(HERE), "gr-ais_amd", "csrc")
-_L = None
-
-
-def emu():
-    global _L
-    if _L is None:
-        so = os.path.join(EMUL, "libaisx_emul_hdlc.so")
-        deps = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(EMUL, "emul_hdlc.cpp"), os.path.join(HERE, "emul", "emul.cpp")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            subprocess.check_call(["make", "-C", EMUL, "-s", "-B"])
-        L = C.CDLL(so)
-        vp, i32, lng = C.c_void_p, C.c_int, C.c_long
-        L.emu_hdlc_create.restype = vp
-        L.emu_hdlc_create.argtypes = [i32, i32, i32, i32, i32]
-        L.emu_hdlc_destroy.argtypes = [vp]
-        L.emu_hdlc_process.argtypes = [vp, vp, lng, vp]
-        L.emu_hdlc_read.argtypes = [vp, vp, vp, vp]
-        assert L.emu_hdlc_rec_size() == hc.REC_DTYPE.itemsize
-        _L = L
-    return _L
+emu = hc.emu
 
 
 class EmuBatch:
@@ -55,7 +30,7 @@ class EmuBatch:
         recs = np.zeros(self.max_pdus, dtype=hc.REC_DTYPE)
         data = np.zeros(self.max_pdus * (self.lmax - 1) + 1, dtype=np.uint8)
         cnt = np.zeros(3, dtype=np.int32)
-        emu().emu_hdlc_read(self.h, recs.ctypes.data, data.ctypes.data, cnt.ctypes.data)
+        emu().emu_hdlc_read(self.h, recs.ctypes.data, data.ctypes.data, None, cnt.ctypes.data)
         return int(cnt[0]), int(cnt[2]), recs[: cnt[1]], data
 
 

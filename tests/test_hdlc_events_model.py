@@ -2,11 +2,10 @@
 aisx_hdlc_event_table, the host form (aisx_hdlc_set_repair_events / aisx_hdlc_work_repair,
 ais_amd.hdlc_deframer_bp(repair=, events=)) against the Python restatement of its rule (tests/hdlc_events_cases.py), its
 false accepts on noise and what it recovers near the threshold, and the kernel bodies of gr-ais_amd/csrc/k_hdlc.h with
-the event repair compiled in, on the CPU lane model (tests/emul_hdlc_events), against the host form bit for bit, marks
+the event repair compiled in, on the CPU lane model (tests/emul_hdlc), against the host form bit for bit, marks
 included."""
 import concurrent.futures as cf
 import ctypes as C
-import glob
 import os
 import subprocess
 
@@ -20,60 +19,41 @@ import mlse_cases as mc
 import torch  # noqa: F401  (before libaisx.so: one HIP runtime in the process)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL = os.path.join(HERE, "emul_hdlc_events")
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "gr-ais_amd", "csrc")
-_L = None
+EMUL = os.path.join(HERE, "emul_hdlc")
 R21 = {21: (1, 2, 3, 4, 9, 11, 18, 24)}
 REACH = 16383
 
 
 def emu():
-    global _L
-    if _L is None:
-        so = os.path.join(EMUL, "libaisx_emul_hdlc_events.so")
-        deps = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(EMUL, "emul_hdlc_events.cpp"), os.path.join(HERE, "emul", "emul.cpp"),
-                                                       os.path.join(CSRC, "aisx_framing.cpp"), os.path.join(ROOT, "include", "aisx.h")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            subprocess.check_call(["make", "-C", EMUL, "-s", "-B"])
-        L = C.CDLL(so)
-        vp, i32, lng = C.c_void_p, C.c_int, C.c_long
-        L.emu_hdlce_create.restype = vp
-        L.emu_hdlce_create.argtypes = [i32, i32, i32, i32, i32]
-        L.emu_hdlce_destroy.argtypes = [vp]
-        L.emu_hdlce_set_repair.argtypes = [vp, vp, i32, i32]
-        L.emu_hdlce_process.argtypes = [vp, vp, lng, vp]
-        L.emu_hdlce_read.argtypes = [vp, vp, vp, vp, vp]
-        L.emu_hdlce_syndrome_table.argtypes = [vp]
-        assert L.emu_hdlce_rec_size() == hc.REC_DTYPE.itemsize and L.emu_hdlce_rule_size() == rc.RULE_DTYPE.itemsize
-        _L = L
-    return _L
+    L = hc.emu()
+    assert L.emu_hdlc_rule_size() == rc.RULE_DTYPE.itemsize
+    return L
 
 
 class EmuBatch:
     def __init__(self, lmin, lmax, nch, max_bits, max_pdus=4096, rules=None, events=1):
-        self.h = emu().emu_hdlce_create(lmin, lmax, nch, max_bits, max_pdus)
+        self.h = emu().emu_hdlc_create(lmin, lmax, nch, max_bits, max_pdus)
         assert self.h
         self.nch, self.max_pdus, self.lmax, self.max_bits = nch, max_pdus, lmax, max_bits
         self.set_repair(rules, events)
 
     def __del__(self):
-        emu().emu_hdlce_destroy(self.h)
+        emu().emu_hdlc_destroy(self.h)
 
     def set_repair(self, rules, events=1):
         a = rc.rule_array(rules)
-        emu().emu_hdlce_set_repair(self.h, a.ctypes.data if a.size else None, a.size, events)
+        emu().emu_hdlc_set_repair(self.h, a.ctypes.data if a.size else None, a.size, events)
 
     def process(self, call, pad_front=0):
         rows, n = hc.pack(call, self.max_bits + 3, pad_front)
-        emu().emu_hdlce_process(self.h, rows.ctypes.data, rows.strides[0], n.ctypes.data)
+        emu().emu_hdlc_process(self.h, rows.ctypes.data, rows.strides[0], n.ctypes.data)
 
     def read(self):
         recs = np.zeros(self.max_pdus, dtype=hc.REC_DTYPE)
         data = np.zeros(self.max_pdus * (self.lmax - 1) + 1, dtype=np.uint8)
         fix = np.full(self.max_pdus, -9, dtype=np.int32)
         cnt = np.zeros(3, dtype=np.int32)
-        emu().emu_hdlce_read(self.h, recs.ctypes.data, data.ctypes.data, fix.ctypes.data, cnt.ctypes.data)
+        emu().emu_hdlc_read(self.h, recs.ctypes.data, data.ctypes.data, fix.ctypes.data, cnt.ctypes.data)
         return int(cnt[0]), int(cnt[2]), recs[: cnt[1]], data, fix[: cnt[1]]
 
 
@@ -157,7 +137,7 @@ def test_event_tables():
     d = np.arange(REACH)
     syn = [s[:REACH], s[:REACH] ^ s[1:REACH + 1], s[:REACH] ^ s[2:REACH + 2]]
     single = np.zeros(65536, dtype=np.uint16)
-    emu().emu_hdlce_syndrome_table(single.ctypes.data)
+    emu().emu_hdlc_syndrome_table(single.ctypes.data)
     for mask in ec.MASKS:
         ids = [e for e in range(3) if (mask >> e) & 1]
         best = np.full(65536, 1 << 30, dtype=np.int64)
@@ -175,6 +155,14 @@ def test_event_tables():
     # the single event alone: hdlc_syndrome_table() wherever that is within reach
     assert np.array_equal(framing.event_table(ec.SINGLE), np.where(single <= REACH, single, 0))
     assert (single > REACH).any()
+    # hdlc_syndrome_table() itself, by a walk of the CRC register of its own: 0x8000 for the frame's last bit, one step
+    # per bit before it, the nearest bit where two give the same syndrome
+    walk, v = np.zeros(65536, dtype=np.uint16), 0x8000
+    for k in range(32767):
+        if not walk[v]:
+            walk[v] = k + 1
+        v = (v >> 1) ^ (0x8408 if v & 1 else 0)
+    assert np.array_equal(single, walk)
     # single syndromes are never pair or skip ones; pair at 0 and skip at 7140 collide, and the pair wins
     assert not set(syn[0].tolist()) & (set(syn[1].tolist()) | set(syn[2].tolist()))
     assert syn[1][0] == syn[2][7140]
@@ -528,7 +516,7 @@ def test_lane_model_single_mask_on_the_single_bit_cases():
 
 
 def test_sanitizer_program_runs_clean():
-    """tests/emul_hdlc_events `make san`: the host form and the lane model side by side in a stand-alone program under
+    """tests/emul_hdlc `make san`: the host form and the lane model side by side in a stand-alone program under
     AddressSanitizer and UndefinedBehaviorSanitizer"""
     subprocess.check_call(["make", "-C", EMUL, "-s", "san"])
     r = subprocess.run([os.path.join(EMUL, "events_san")], capture_output=True, text=True)

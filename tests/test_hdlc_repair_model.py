@@ -1,11 +1,7 @@
 """Single-bit repair by CRC syndrome in the HDLC deframers, -m "not gpu": the host form (aisx_hdlc_set_repair /
 aisx_hdlc_work_repair, ais_amd.hdlc_deframer_bp(repair=...)) against the Python restatement of its rule
 (tests/hdlc_repair_cases.py), and the kernel bodies of gr-ais_amd/csrc/k_hdlc.h with the repair compiled in, on the CPU
-lane model (tests/emul_hdlc_repair), against the host form bit for bit, marks included."""
-import ctypes as C
-import glob
-import os
-import subprocess
+lane model (tests/emul_hdlc), against the host form bit for bit, marks included."""
 
 import numpy as np
 import pytest
@@ -15,57 +11,39 @@ import hdlc_repair_cases as rc
 import test_hdlc_batch_model as plain
 import torch  # noqa: F401  (before libaisx.so: one HIP runtime in the process)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL = os.path.join(HERE, "emul_hdlc_repair")
-CSRC = os.path.join(os.path.dirname(HERE), "gr-ais_amd", "csrc")
-_L = None
 R21 = {21: (1, 2, 3, 4, 9, 11, 18, 24)}
 
 
 def emu():
-    global _L
-    if _L is None:
-        so = os.path.join(EMUL, "libaisx_emul_hdlc_repair.so")
-        deps = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(EMUL, "emul_hdlc_repair.cpp"), os.path.join(HERE, "emul", "emul.cpp")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            subprocess.check_call(["make", "-C", EMUL, "-s", "-B"])
-        L = C.CDLL(so)
-        vp, i32, lng = C.c_void_p, C.c_int, C.c_long
-        L.emu_hdlcr_create.restype = vp
-        L.emu_hdlcr_create.argtypes = [i32, i32, i32, i32, i32]
-        L.emu_hdlcr_destroy.argtypes = [vp]
-        L.emu_hdlcr_set_repair.argtypes = [vp, vp, i32]
-        L.emu_hdlcr_process.argtypes = [vp, vp, lng, vp]
-        L.emu_hdlcr_read.argtypes = [vp, vp, vp, vp, vp]
-        assert L.emu_hdlcr_rec_size() == hc.REC_DTYPE.itemsize and L.emu_hdlcr_rule_size() == rc.RULE_DTYPE.itemsize
-        _L = L
-    return _L
+    L = hc.emu()
+    assert L.emu_hdlc_rule_size() == rc.RULE_DTYPE.itemsize
+    return L
 
 
 class EmuBatch:
     def __init__(self, lmin, lmax, nch, max_bits, max_pdus=4096, rules=None):
-        self.h = emu().emu_hdlcr_create(lmin, lmax, nch, max_bits, max_pdus)
+        self.h = emu().emu_hdlc_create(lmin, lmax, nch, max_bits, max_pdus)
         assert self.h
         self.nch, self.max_pdus, self.lmax, self.max_bits = nch, max_pdus, lmax, max_bits
         self.set_repair(rules)
 
     def __del__(self):
-        emu().emu_hdlcr_destroy(self.h)
+        emu().emu_hdlc_destroy(self.h)
 
     def set_repair(self, rules):
         a = rc.rule_array(rules)
-        emu().emu_hdlcr_set_repair(self.h, a.ctypes.data if a.size else None, a.size)
+        emu().emu_hdlc_set_repair(self.h, a.ctypes.data if a.size else None, a.size, 1)
 
     def process(self, call, pad_front=0):
         rows, n = hc.pack(call, self.max_bits + 3, pad_front)
-        emu().emu_hdlcr_process(self.h, rows.ctypes.data, rows.strides[0], n.ctypes.data)
+        emu().emu_hdlc_process(self.h, rows.ctypes.data, rows.strides[0], n.ctypes.data)
 
     def read(self):
         recs = np.zeros(self.max_pdus, dtype=hc.REC_DTYPE)
         data = np.zeros(self.max_pdus * (self.lmax - 1) + 1, dtype=np.uint8)
         fix = np.full(self.max_pdus, -9, dtype=np.int32)
         cnt = np.zeros(3, dtype=np.int32)
-        emu().emu_hdlcr_read(self.h, recs.ctypes.data, data.ctypes.data, fix.ctypes.data, cnt.ctypes.data)
+        emu().emu_hdlc_read(self.h, recs.ctypes.data, data.ctypes.data, fix.ctypes.data, cnt.ctypes.data)
         return int(cnt[0]), int(cnt[2]), recs[: cnt[1]], data, fix[: cnt[1]]
 
 

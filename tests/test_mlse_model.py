@@ -11,12 +11,13 @@ import subprocess
 import numpy as np
 import pytest
 
+import emul_load
+from emul_load import i32, lng, vp
 import mlse_cases as mc
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 EMUL = os.path.join(HERE, "emul_mlse")
 CSRC = os.path.join(os.path.dirname(HERE), "gr-ais_amd", "csrc")
-_L = None
 
 
 def _stale(target, extra=()):
@@ -25,22 +26,15 @@ def _stale(target, extra=()):
 
 
 def emu():
-    global _L
-    if _L is None:
-        so = os.path.join(EMUL, "libaisx_emul_mlse.so")
-        if _stale(so):
-            subprocess.check_call(["make", "-C", EMUL, "-s", "-B", "libaisx_emul_mlse.so"])
-        L = C.CDLL(so)
-        vp, i32, lng = C.c_void_p, C.c_int, C.c_long
-        L.emu_mlse_create.restype = vp
-        L.emu_mlse_create.argtypes = [vp, i32, i32]
-        L.emu_mlse_destroy.argtypes = [vp]
-        L.emu_mlse_reset.argtypes = [vp]
-        L.emu_mlse_process.argtypes = [vp, vp, lng, vp, vp, lng, vp]
-        L.emu_mlse_flush.argtypes = [vp, vp, lng, vp]
-        L.emu_mlse_status.argtypes = [vp]
-        _L = L
-    return _L
+    return emul_load.load("emul_mlse", [
+        ("emu_mlse_create", vp, [vp, i32, i32]),
+        ("emu_mlse_destroy", None, [vp]),
+        ("emu_mlse_reset", None, [vp]),
+        ("emu_mlse_process", None, [vp, vp, lng, vp, vp, lng, vp]),
+        ("emu_mlse_flush", None, [vp, vp, lng, vp]),
+        ("emu_mlse_status", None, [vp]),
+        ("emu_mlse_plan", i32, [i32, i32, vp]),
+    ])
 
 
 class LaneForm:

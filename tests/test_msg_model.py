@@ -3,39 +3,28 @@ decoder of tests/msg_cases.py, the published sentences, the agreement with aisx_
 kernel body (gr-ais_amd/csrc/k_msg.h) on the CPU lane model (tests/emul_msg) row for row against the host function,
 the C ABI's argument checks and its refusal without a device.  -m "not gpu"."""
 import ctypes as C
-import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emul_load
+from emul_load import i32, vp
 import msg_cases as mc
 import torch  # noqa: F401  (before libaisx.so: one HIP runtime in the process)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL = os.path.join(HERE, "emul_msg")
-CSRC = os.path.join(os.path.dirname(HERE), "gr-ais_amd", "csrc")
 NCOL = len(mc.COLUMNS)
-_L = None
 
 
 def emu():
-    global _L
-    if _L is None:
-        so = os.path.join(EMUL, "libaisx_emul_msg.so")
-        deps = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(EMUL, "emul_msg.cpp"), os.path.join(HERE, "emul", "emul.cpp")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            subprocess.check_call(["make", "-C", EMUL, "-s", "-B"])
-        L = C.CDLL(so)
-        vp, i32 = C.c_void_p, C.c_int
-        L.emu_msg_create.restype = vp
-        L.emu_msg_create.argtypes = [i32, i32, i32]
-        L.emu_msg_destroy.argtypes = [vp]
-        L.emu_msg_process.argtypes = [vp, vp, vp, vp, vp]
-        L.emu_msg_read.argtypes = [vp, vp, vp, vp]
-        _L = L
-    return _L
+    return emul_load.load("emul_msg", [
+        ("emu_msg_create", vp, [i32, i32, i32]),
+        ("emu_msg_destroy", None, [vp]),
+        ("emu_msg_process", None, [vp, vp, vp, vp, vp]),
+        ("emu_msg_read", None, [vp, vp, vp, vp]),
+        ("emu_msg_plan", i32, [i32, i32, i32, vp]),
+    ])
 
 
 @pytest.fixture(scope="module")

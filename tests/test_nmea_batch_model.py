@@ -3,41 +3,26 @@ record by record against the host aisx_pdu_to_nmea that is their specification a
 oracle's orc_pdu_to_nmea.  Plus the closed-form text length, the C ABI's argument checks and its refusal without a
 device.  -m "not gpu"."""
 import ctypes as C
-import glob
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emul_load
+from emul_load import i32, lng, vp
 import nmea_cases as nc
 import torch  # noqa: F401  (before libaisx.so: one HIP runtime in the process)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL = os.path.join(HERE, "emul_nmea")
-CSRC = os.path.join(os.path.dirname(HERE), "gr-ais_amd", "csrc")
-_L = None
-
 
 def emu():
-    global _L
-    if _L is None:
-        so = os.path.join(EMUL, "libaisx_emul_nmea.so")
-        deps = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(EMUL, "emul_nmea.cpp"), os.path.join(HERE, "emul", "emul.cpp")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            subprocess.check_call(["make", "-C", EMUL, "-s", "-B"])
-        L = C.CDLL(so)
-        vp, i32, lng = C.c_void_p, C.c_int, C.c_long
-        L.emu_nmea_create.restype = vp
-        L.emu_nmea_create.argtypes = [C.POINTER(C.c_char_p), i32, i32, i32, lng]
-        L.emu_nmea_destroy.argtypes = [vp]
-        L.emu_nmea_text_cap.restype = lng
-        L.emu_nmea_text_cap.argtypes = [vp]
-        L.emu_nmea_text_len.argtypes = [i32, i32]
-        L.emu_nmea_process.argtypes = [vp, vp, vp, vp, vp]
-        L.emu_nmea_read.argtypes = [vp, vp, vp, vp]
-        _L = L
-    return _L
+    return emul_load.load("emul_nmea", [
+        ("emu_nmea_create", vp, [C.POINTER(C.c_char_p), i32, i32, i32, lng]),
+        ("emu_nmea_destroy", None, [vp]),
+        ("emu_nmea_text_cap", lng, [vp]),
+        ("emu_nmea_text_len", None, [i32, i32]),
+        ("emu_nmea_process", None, [vp, vp, vp, vp, vp]),
+        ("emu_nmea_read", None, [vp, vp, vp, vp]),
+        ("emu_nmea_plan", i32, [C.POINTER(C.c_char_p), i32, i32, i32, lng, vp]),
+    ])
 
 
 def _designators(des):

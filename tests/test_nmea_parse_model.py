@@ -3,44 +3,33 @@
 bytes, times and every count.  Plus the refusal of a bad call, the max_pdus overflow, the C ABI's refusal without a
 device and the names of the counts.  -m "not gpu"."""
 import ctypes as C
-import glob
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import emul_load
+from emul_load import i32, lng, vp
 import nmea_parse_cases as nc
 import torch  # noqa: F401  (before libaisx.so: one HIP runtime in the process)
 import ais_amd
 from ais_amd import _lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL = os.path.join(HERE, "emul_nmea_parse")
-CSRC = os.path.join(os.path.dirname(HERE), "gr-ais_amd", "csrc")
 PDU_DTYPE = np.dtype([("end_bit", "<u8"), ("offset", "<i8"), ("chan", "<i4"), ("len", "<i4")])
 CASES = nc.build_cases()
-_L = None
 
 
 def emu():
-    global _L
-    if _L is None:
-        so = os.path.join(EMUL, "libaisx_emul_nmea_parse.so")
-        deps = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(EMUL, "emul_nmea_parse.cpp"), os.path.join(HERE, "emul", "emul.cpp")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            subprocess.check_call(["make", "-C", EMUL, "-s", "-B"])
-        L = C.CDLL(so)
-        vp, i32, lng = C.c_void_p, C.c_int, C.c_long
-        L.emu_nmp_create.restype = vp
-        L.emu_nmp_create.argtypes = [C.POINTER(C.c_char_p), i32, i32, i32, i32, lng, i32, i32]
-        L.emu_nmp_destroy.argtypes = [vp]
-        L.emu_nmp_reset.argtypes = [vp]
-        L.emu_nmp_process.argtypes = [vp, vp, vp]
-        L.emu_nmp_read.argtypes = [vp, vp, vp, vp, vp]
-        _L = L
-    return _L
+    return emul_load.load("emul_nmea_parse", [
+        ("emu_nmp_create", vp, [C.POINTER(C.c_char_p), i32, i32, i32, i32, lng, i32, i32]),
+        ("emu_nmp_destroy", None, [vp]),
+        ("emu_nmp_reset", None, [vp]),
+        ("emu_nmp_process", None, [vp, vp, vp]),
+        ("emu_nmp_read", None, [vp, vp, vp, vp, vp]),
+        ("emu_nmp_plan", i32, [C.POINTER(C.c_char_p), i32, i32, i32, i32, lng, i32, i32, vp]),
+    ])
 
 
 class EmuParser:

@@ -2,43 +2,32 @@
 tests/track_cases.py, and the kernel bodies (gr-ais_amd/csrc/k_track.h) on the CPU lane model (tests/emul_track), whose
 lanes are free-running threads, against the host form, array for array.  -m "not gpu"."""
 import ctypes as C
-import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emul_load
+from emul_load import i32, lng, vp
 import msg_cases as mc
 import track_cases as tc
 import torch  # noqa: F401  (before libaisx.so: one HIP runtime in the process)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL = os.path.join(HERE, "emul_track")
-CSRC = os.path.join(os.path.dirname(HERE), "gr-ais_amd", "csrc")
 MAX_ROWS = 257  # one workgroup of 256 and one row: several waves and a ragged tail
-_L = None
 
 
 def emu():
-    global _L
-    if _L is None:
-        so = os.path.join(EMUL, "libaisx_emul_track.so")
-        deps = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(EMUL, "emul_track.cpp"), os.path.join(HERE, "emul", "emul.cpp")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            subprocess.check_call(["make", "-C", EMUL, "-s", "-B"])
-        L = C.CDLL(so)
-        vp, i32 = C.c_void_p, C.c_int
-        L.emu_trk_create.restype = vp
-        L.emu_trk_create.argtypes = [i32, i32]
-        L.emu_trk_destroy.argtypes = [vp]
-        L.emu_trk_process.argtypes = [vp, vp, C.c_long, vp, vp, vp, i32]
-        L.emu_trk_expire.argtypes = [vp, i32]
-        L.emu_trk_read.argtypes = [vp, vp, vp, vp, vp]
-        L.emu_trk_gather.argtypes = [vp, vp, vp]
-        L.emu_trk_poke.argtypes = [vp, i32, i32, i32]
-        _L = L
-    return _L
+    return emul_load.load("emul_track", [
+        ("emu_trk_create", vp, [i32, i32]),
+        ("emu_trk_destroy", None, [vp]),
+        ("emu_trk_process", None, [vp, vp, lng, vp, vp, vp, i32]),
+        ("emu_trk_expire", None, [vp, i32]),
+        ("emu_trk_read", None, [vp, vp, vp, vp, vp]),
+        ("emu_trk_gather", None, [vp, vp, vp]),
+        ("emu_trk_poke", None, [vp, i32, i32, i32]),
+        ("emu_trk_plan", i32, [i32, i32, vp]),
+    ])
 
 
 class HostForm:

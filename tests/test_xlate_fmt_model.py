@@ -4,45 +4,31 @@ through ragged calls; the outputs equal, bit for bit, the fc32 path fed numpy's 
 (raw.astype(float32) - float32(bias)) * float32(scale).  Also a stream that changes format between calls, and the
 argument checks of aisx_xlate_process_fmt and aisx_rx_create, which need no device.  -m "not gpu"."""
 import ctypes as C
-import glob
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emul_load
+from emul_load import f32, f64, i32, lng, vp
 import torch  # noqa: F401  (before libaisx.so: one HIP runtime in the process)
 import xlate_cases as xc
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL = os.path.join(HERE, "emul_xlate_fmt")
-CSRC = os.path.join(os.path.dirname(HERE), "gr-ais_amd", "csrc")
 NT = 64
 CF32, CS16, CS8, CU8 = 0, 1, 2, 3
 DTYPES = {CS16: np.int16, CS8: np.int8, CU8: np.uint8}
 # (scale, bias) per format: powers of two and the RTL-SDR's half-integer bias, and values that round
 PARAMS = {CS16: [(2.0 ** -13, 0.0), (1.0 / 3000.0, 0.25)], CS8: [(2.0 ** -6, 0.0), (0.013, -0.5)],
           CU8: [(2.0 ** -7, 127.5), (1.0 / 127.0, 127.4)]}
-_L = None
 
 
 def emu():
-    global _L
-    if _L is None:
-        so = os.path.join(EMUL, "libaisx_emul_xlate_fmt.so")
-        deps = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(EMUL, "emul_xlate_fmt.cpp"), os.path.join(HERE, "emul", "emul.cpp")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            subprocess.check_call(["make", "-C", EMUL, "-s", "-B"])
-        L = C.CDLL(so)
-        vp, i32, lng, f64, f32 = C.c_void_p, C.c_int, C.c_long, C.c_double, C.c_float
-        L.emu_xlate_fmt_create.restype = vp
-        L.emu_xlate_fmt_create.argtypes = [i32, vp, i32, vp, i32, f64, i32, i32, i32]
-        L.emu_xlate_fmt_destroy.argtypes = [vp]
-        L.emu_xlate_fmt_output_count.argtypes = [vp, i32]
-        L.emu_xlate_fmt_item_bytes.argtypes = [i32]
-        L.emu_xlate_fmt_process.argtypes = [vp, vp, i32, f32, f32, lng, i32, vp, lng]
-        _L = L
-    return _L
+    return emul_load.load("emul_xlate_fmt", [
+        ("emu_xlate_fmt_create", vp, [i32, vp, i32, vp, i32, f64, i32, i32, i32]),
+        ("emu_xlate_fmt_destroy", None, [vp]),
+        ("emu_xlate_fmt_output_count", None, [vp, i32]),
+        ("emu_xlate_fmt_item_bytes", None, [i32]),
+        ("emu_xlate_fmt_process", None, [vp, vp, i32, f32, f32, lng, i32, vp, lng]),
+    ])
 
 
 class EmuFmt:

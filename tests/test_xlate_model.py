@@ -3,42 +3,28 @@
 counts, centres and channel counts through ragged call sequences, split invariance bit for bit, retunes against the
 closed form; plus the C ABI's argument checks and its refusal without a device.  -m "not gpu"."""
 import ctypes as C
-import glob
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emul_load
+from emul_load import f64, i32, lng, vp
 import torch  # noqa: F401  (before libaisx.so: one HIP runtime in the process)
 import xlate_cases as xc
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL = os.path.join(HERE, "emul_xlate")
-CSRC = os.path.join(os.path.dirname(HERE), "gr-ais_amd", "csrc")
 NT = 64  # lanes per workgroup in the model (the device runs 256: the plan follows)
-_L = None
 
 
 def emu():
-    global _L
-    if _L is None:
-        so = os.path.join(EMUL, "libaisx_emul_xlate.so")
-        deps = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(EMUL, "emul_xlate.cpp"), os.path.join(HERE, "emul", "emul.cpp")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            subprocess.check_call(["make", "-C", EMUL, "-s", "-B"])
-        L = C.CDLL(so)
-        vp, i32, lng, f64 = C.c_void_p, C.c_int, C.c_long, C.c_double
-        L.emu_xlate_create.restype = vp
-        L.emu_xlate_create.argtypes = [i32, vp, i32, vp, i32, f64, i32, i32, i32]
-        L.emu_xlate_destroy.argtypes = [vp]
-        L.emu_xlate_plan.argtypes = [vp, vp]
-        L.emu_xlate_output_count.argtypes = [vp, i32]
-        L.emu_xlate_set_center_freq.argtypes = [vp, i32, i32, f64]
-        L.emu_xlate_reset.argtypes = [vp]
-        L.emu_xlate_process.argtypes = [vp, vp, lng, i32, vp, lng]
-        _L = L
-    return _L
+    return emul_load.load("emul_xlate", [
+        ("emu_xlate_create", vp, [i32, vp, i32, vp, i32, f64, i32, i32, i32]),
+        ("emu_xlate_destroy", None, [vp]),
+        ("emu_xlate_plan", None, [vp, vp]),
+        ("emu_xlate_output_count", None, [vp, i32]),
+        ("emu_xlate_set_center_freq", None, [vp, i32, i32, f64]),
+        ("emu_xlate_reset", None, [vp]),
+        ("emu_xlate_process", None, [vp, vp, lng, i32, vp, lng]),
+    ])
 
 
 class EmuXlate:
