@@ -237,6 +237,12 @@ def lib(device=True):
     sig("aisx_nmea_batch_process", i32, [vp, vp, vp, vp, vp, vp])
     sig("aisx_nmea_batch_results_device", i32, [vp, pvp, pvp, pvp])
     sig("aisx_nmea_batch_read", i32, [vp, vp, i32, vp, lng, pi32, pi32, vp])
+    sig("aisx_pdu_to_nmea_std", i32, [C.c_char_p, vp, i32, i32, C.c_char_p, C.c_int64, C.c_char_p, i32])
+    sig("aisx_nmea_std_text_len", i32, [i32, i32, i32, C.c_int64])
+    sig("aisx_nmea_batch_create_std", i32, [pvp, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), i32, i32, i32, lng])
+    sig("aisx_nmea_batch_set_time", i32, [vp, C.c_int64])
+    sig("aisx_nmea_batch_reset", i32, [vp])
+    sig("aisx_nmea_batch_next_id", i32, [vp, pi32, vp])
     ppc = C.POINTER(C.c_char_p)
     sig("aisx_nmea_parse_create", i32, [pvp, ppc, i32, i32, i32, i32])
     sig("aisx_nmea_parse_destroy", i32, [vp])
@@ -296,6 +302,7 @@ def lib(device=True):
     sig("aisx_mlse_batch_status", i32, [vp, pi32, vp])
     sig("aisx_mlse_batch_status_device", i32, [vp, pvp])
     sig("aisx_rx_enable_mlse", i32, [vp, f64])
+    sig("aisx_rx_enable_standard_nmea", i32, [vp, C.POINTER(C.c_char_p), C.c_int64])
     _lib = L
     return L
 

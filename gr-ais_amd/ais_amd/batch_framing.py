@@ -205,6 +205,17 @@ def nmea_text_len(length, dlen):
     return F * (18 + (2 if F >= 10 else 1) + dlen) + max(F - 9, 0) + P - 1
 
 
+def nmea_std_text_len(length, dlen, slen=0, time=-1):
+    """nmea_text_len for the standard form (pdu_to_nmea(..., standard=True)): a payload of `length` octets (at most
+    378), a designator of dlen bytes, a station of slen bytes and a time (-1: none)"""
+    if length <= 0:
+        return 0
+    P = (8 * length + 5) // 6
+    F = (P + 55) // 56
+    fields = (2 + slen if slen else 0) + (1 if slen and time >= 0 else 0) + (2 + len(str(int(time))) if time >= 0 else 0)
+    return F * ((fields + 5 if fields else 0) + 18 + (F > 1) + dlen) + P + F - 1
+
+
 def _text_end(offset, length):
     """where a pdu_to_nmea_batch record's text ends in the text buffer: behind its newline, which an empty text lacks
     (integers, numpy or torch values alike)"""
@@ -236,9 +247,15 @@ class pdu_to_nmea_batch:
         nm.work(hd, stream=s)                            # and armour its PDUs, still on s: nothing waits
         sys.stdout.buffer.write(text)                    # (records: chan, end_bit, offset / len of each text)
 
-    The read of step k - 1 comes before step k's work is queued: both handles' results are replaced by it."""
+    The read of step k - 1 comes before step k's work is queued: both handles' results are replaced by it.
 
-    def __init__(self, designators, nchan, max_pdus, length_max, text_cap=0):
+    standard=True: per record the text of ais_amd.pdu_to_nmea(designator, standard=True, station=stations[chan],
+    time=...) instead -- exact armouring, tag blocks, message ids (length_max <= 379).  stations: None, one str for
+    every channel or nchan str.  set_time(t) sets the c: value of the following calls (a launch parameter: nothing
+    waits); the ids run 0..9 round over the multi-sentence records written, call after call, from a counter in device
+    memory that next_id() reads and reset() zeroes."""
+
+    def __init__(self, designators, nchan, max_pdus, length_max, text_cap=0, standard=False, stations=None):
         nchan = int(nchan)
         if isinstance(designators, (str, bytes)):
             designators = [designators] * nchan
@@ -247,13 +264,30 @@ class pdu_to_nmea_batch:
             raise ValueError("pdu_to_nmea_batch: %d designators for %d channels" % (len(designators), nchan))
         arr = (C.c_char_p * nchan)(*designators)
         h = C.c_void_p()
-        check(_lib.lib().aisx_nmea_batch_create(C.byref(h), arr, nchan, int(max_pdus), int(length_max), int(text_cap)),
-              "pdu_to_nmea_batch")
+        self.standard = bool(standard)
+        if stations is not None and not standard:
+            raise ValueError("pdu_to_nmea_batch: stations belong to the standard form (standard=True)")
+        if standard:
+            if stations is None or isinstance(stations, (str, bytes)):
+                stations = [stations or ""] * nchan
+            stations = [s.encode() if isinstance(s, str) else bytes(s) for s in stations]
+            if len(stations) != nchan:
+                raise ValueError("pdu_to_nmea_batch: %d stations for %d channels" % (len(stations), nchan))
+            check(_lib.lib().aisx_nmea_batch_create_std(C.byref(h), arr, (C.c_char_p * nchan)(*stations), nchan, int(max_pdus),
+                                                        int(length_max), int(text_cap)), "pdu_to_nmea_batch")
+            self.stations = [s.decode("latin-1") for s in stations]
+        else:
+            check(_lib.lib().aisx_nmea_batch_create(C.byref(h), arr, nchan, int(max_pdus), int(length_max), int(text_cap)),
+                  "pdu_to_nmea_batch")
         self._h = h
         self.nchan, self.max_pdus, self.length_max = nchan, int(max_pdus), int(length_max)
         self.designators = [d.decode("latin-1") for d in designators]
         self.found = 0  # PDUs the last call's producer found (armoured or not)
-        worst = self.max_pdus * (nmea_text_len(self.length_max - 1, max(len(d) for d in designators)) + 1)
+        if standard:
+            worst = self.max_pdus * (nmea_std_text_len(self.length_max - 1, max(len(d) for d in designators),
+                                                       max(len(s) for s in stations), 10 ** 18 - 1) + 1)
+        else:
+            worst = self.max_pdus * (nmea_text_len(self.length_max - 1, max(len(d) for d in designators)) + 1)
         self.text_cap = worst if int(text_cap) == 0 or int(text_cap) > worst else int(text_cap)  # (the handle's)
         self._recs = np.zeros(self.max_pdus, dtype=PDU_DTYPE)  # read-back buffers, reused by every call
         self._text = np.zeros(self.text_cap, dtype=np.uint8)
@@ -263,6 +297,20 @@ class pdu_to_nmea_batch:
         if h and _lib is not None:
             _lib.lib().aisx_nmea_batch_destroy(h)
             self._h = None
+
+    def set_time(self, t):
+        """standard form: the c: value of the following calls' tag blocks (-1: none); nothing waits"""
+        check(_lib.lib().aisx_nmea_batch_set_time(self._h, int(t)), "pdu_to_nmea_batch.set_time")
+
+    def reset(self):
+        """standard form: the id counter back to 0, the time to -1; waits for the handle's queued work"""
+        check(_lib.lib().aisx_nmea_batch_reset(self._h), "pdu_to_nmea_batch.reset")
+
+    def next_id(self, stream=None):
+        """standard form: the id the next multi-sentence record gets (synchronises `stream`)"""
+        n = C.c_int(0)
+        check(_lib.lib().aisx_nmea_batch_next_id(self._h, C.byref(n), _stream_ptr(stream)), "pdu_to_nmea_batch.next_id")
+        return n.value
 
     def work(self, deframer, stream=None):
         """Armours the PDUs of the deframer's last call (queued on `stream`, default the current one; nothing

@@ -860,11 +860,16 @@ class ais_rx:
     block popped last were put right.  repair_events=mask (ais_amd.AIS_REPAIR_EVENTS: all) makes it the repair of one
     error event: one wrong bit, the two adjacent wrong bits one wrong decision of the differential slicer gives, and the
     two wrong bits two apart of the sequence detector's error event.  ais_amd.repair_mark reads a mark.
+
+    nmea="standard" makes the text the standard form (ais_amd.pdu_to_nmea(..., standard=True): exact armouring, message
+    ids, tag blocks) where the default, "reference", is the reference's text byte for byte.  stations: None, one str for
+    every stream or nstreams str, the s: field of every sentence of that stream; t0: the second of block 0's first
+    item, block b's sentences carry c: t0 + floor(b * block_items / rate) -- or no time for t0 < 0.
     """
 
     def __init__(self, freq, rate, designator, nstreams=1, fmt="cf32", scale=1.0, bias=0.0, block_items=None,
                  preamble_symbols=None, taps=None, max_pdus_per_block=1 << 16, decode=False, tracks=None, repair=None,
-                 detector=None, bt=0.4, repair_events=1):
+                 detector=None, bt=0.4, repair_events=1, nmea="reference", stations=None, t0=-1):
         from .batch_framing import PDU_DTYPE
         from .modulate import gmsk_mod, modulate_vector_bc
 
@@ -903,6 +908,18 @@ class ais_rx:
                                         t.ctypes.data_as(C.c_void_p) if t is not None else None, t.size if t is not None else 0,
                                         sym.ctypes.data_as(C.c_void_p), sym.size, int(max_pdus_per_block)), "ais_rx")
         self._h = h
+        if nmea not in ("reference", "standard"):
+            raise ValueError("ais_rx: nmea is 'reference' or 'standard'")
+        if nmea == "reference" and (stations is not None or t0 >= 0):
+            raise ValueError("ais_rx: stations and t0 belong to nmea='standard'")
+        self.nmea = nmea
+        if nmea == "standard":  # (before the geometry is read: the text of a block can be longer)
+            if stations is None or isinstance(stations, (str, bytes)):
+                stations = [stations or ""] * self.nstreams
+            sta = [x.encode() if isinstance(x, str) else bytes(x) for x in stations]
+            if len(sta) != self.nstreams:
+                raise ValueError("ais_rx: %d stations for %d streams" % (len(sta), self.nstreams))
+            check(_lib.lib().aisx_rx_enable_standard_nmea(h, (C.c_char_p * len(sta))(*sta), int(t0)), "ais_rx")
         d, T, nch, nin, nres, tc = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_long()
         check(_lib.lib().aisx_rx_geometry(h, C.byref(d), C.byref(T), C.byref(nch), C.byref(nin), C.byref(nres), C.byref(tc)),
               "ais_rx")

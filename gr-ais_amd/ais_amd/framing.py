@@ -170,12 +170,30 @@ class mlse_detector:
 
 
 class pdu_to_nmea:
-    def __init__(self, designator):
-        self.designator = str(designator)
+    """`ais.pdu_to_nmea(designator)`: msg_to_sentence(pdu) gives the reference's text byte for byte, its three defects
+    included (a wrong last payload character when len % 3 != 0, the fill count on every fragment, no message id).
+    standard=True gives the standard form instead (aisx_pdu_to_nmea_std, include/aisx.h): exact armouring, the fill
+    count on the last fragment, a tag block \\s:station,c:time*HH\\ before every fragment (station: 0..15 bytes of A-Z
+    a-z 0-9 _ -; time: -1 for none, else 0 .. 10^18 - 1) and, on messages of more than one sentence, a message id that
+    the object counts 0..9 round (next_id; msg_to_sentence(pdu, time=...) overrides the time for one message).  At most
+    378 octets in that form."""
 
-    def msg_to_sentence(self, pdu):
+    def __init__(self, designator, standard=False, station="", time=-1):
+        self.designator = str(designator)
+        self.standard, self.station, self.time = bool(standard), str(station), int(time)
+        self.next_id = 0
+
+    def msg_to_sentence(self, pdu, time=None):
         p = np.frombuffer(bytes(pdu), dtype=np.uint8)
         out = C.create_string_buffer(4096)
+        if self.standard:
+            n = check(_lib.lib(device=False).aisx_pdu_to_nmea_std(self.designator.encode(), p.ctypes.data_as(C.c_void_p), p.size,
+                                                                  self.next_id, self.station.encode(),
+                                                                  self.time if time is None else int(time), out, 4096),
+                      "pdu_to_nmea")
+            if 6 * 56 < 8 * p.size:  # (more than one sentence: the id is taken)
+                self.next_id = (self.next_id + 1) % 10
+            return out.raw[:n].decode("latin-1")
         n = check(_lib.lib(device=False).aisx_pdu_to_nmea(self.designator.encode(), p.ctypes.data_as(C.c_void_p), p.size, out, 4096),
                   "pdu_to_nmea")
         return out.raw[:n].decode("latin-1")

@@ -6,7 +6,10 @@
 //                    last two octets, which carry the FCS low byte first;
 //   aisx_pdu_to_nmea the sentence format of ais.pdu_to_nmea (observable behaviour of
 //                    lib/pdu_to_nmea_impl.cc:63-131): ITU-R M.1371 / NMEA 0183 six-bit
-//                    armouring, 56 payload characters per !AIVDM fragment, XOR checksum.
+//                    armouring, 56 payload characters per !AIVDM fragment, XOR checksum;
+//   aisx_pdu_to_nmea_std  the same PDU as standard sentences (include/aisx.h states the form): the
+//                    exact last character, the fill count on the last fragment only, a message id
+//                    on multi-sentence messages, a tag block with the station and the time.
 //
 // Per-packet, bytes-per-second work: no GPU involved.  Written from the protocol rules; the
 // reference's observable quirks that a consumer could depend on are kept and named below.
@@ -19,6 +22,7 @@
 
 #include "../../include/aisx.h"
 #include "aisx_repair.h"
+#include "k_nmea_std.h"
 
 namespace {
 
@@ -415,6 +419,75 @@ extern "C" int aisx_pdu_to_nmea(const char* designator, const uint8_t* pdu, int 
             w.put(payload[(size_t)k]);
         w.put(',');
         w.put_number(fill_bits);
+        w.close();
+    }
+    if (w.used() > cap - 1)
+        return AISX_ERR_OVERFLOW;
+    out[w.used()] = '\0';
+    return w.used();
+}
+
+extern "C" int aisx_nmea_std_text_len(int len, int dlen, int slen, int64_t time)
+{
+    if (len < 0 || len > aisx::NMS_MAX_OCTETS || dlen < 0 || slen < 0 || slen > aisx::NMS_STATION || !aisx::nms_time_ok(time))
+        return AISX_ERR_INVALID;
+    return aisx::nms_text_len(len, dlen, aisx::nms_tag_len(slen, aisx::nms_time_digits(time)));
+}
+
+extern "C" int aisx_pdu_to_nmea_std(const char* designator, const uint8_t* pdu, int len, int seq, const char* station, int64_t time,
+                                    char* out, int cap)
+{
+    const char* sta = station ? station : "";
+    if (!designator || !pdu || len < 1 || len > aisx::NMS_MAX_OCTETS || seq < 0 || seq > 9 || !aisx::nms_station_ok(sta) ||
+        !aisx::nms_time_ok(time) || !out || cap < 1)
+        return AISX_ERR_INVALID;
+    // payload: the PDU's bits, most significant first, in groups of six, zeros behind the last bit
+    const int total = (8 * len + 5) / 6, fill_bits = 6 * total - 8 * len;
+    std::vector<char> payload((size_t)total);
+    for (int k = 0; k < total; k++) {
+        unsigned v = 0;
+        for (int i = 6 * k; i < 6 * k + 6; i++)
+            v = v << 1 | (i < 8 * len ? (pdu[i >> 3] >> (7 - (i & 7))) & 1u : 0u);
+        payload[(size_t)k] = (char)(v < 40 ? v + 48 : v + 56);
+    }
+    // the tag block every fragment carries: \s:station,c:time*HH\ with HH over the fields
+    char tag[64] = "";
+    if (sta[0] || time >= 0) {
+        char fields[48];
+        int n = 0;
+        if (sta[0])
+            n += snprintf(fields + n, sizeof fields - (size_t)n, "s:%s", sta);
+        if (time >= 0)
+            n += snprintf(fields + n, sizeof fields - (size_t)n, "%sc:%lld", sta[0] ? "," : "", (long long)time);
+        uint8_t sum = 0;
+        for (int k = 0; k < n; k++)
+            sum ^= (uint8_t)fields[k];
+        snprintf(tag, sizeof tag, "\\%s*%02X\\", fields, sum);
+    }
+    const int per_fragment = 56;
+    const int fragments = (total + per_fragment - 1) / per_fragment; // (at most nine: one digit)
+    SentenceWriter w(out, cap - 1);
+    for (int f = 0; f < fragments; f++) {
+        if (f)
+            w.raw('\n');
+        for (const char* t = tag; *t; t++)
+            w.raw(*t);
+        w.open();
+        w.put("AIVDM,");
+        w.put_number(fragments);
+        w.put(',');
+        w.put_number(f + 1);
+        w.put(',');
+        if (fragments > 1)
+            w.put_number(seq); // the sequential message id, on multi-sentence messages only
+        w.put(',');
+        w.put(designator);
+        w.put(',');
+        const int first = f * per_fragment, last = first + per_fragment < total ? first + per_fragment : total;
+        for (int k = first; k < last; k++)
+            w.put(payload[(size_t)k]);
+        w.put(',');
+        w.put_number(f + 1 == fragments ? fill_bits : 0); // the fill count belongs to the last fragment
         w.close();
     }
     if (w.used() > cap - 1)

@@ -20,7 +20,7 @@
 #include "aisx_devctx.h"
 #include "aisx_host.h"
 #include "k_mlse.h"
-#include "k_nmea.h"
+#include "k_nmea_std.h"
 #include "k_xlate.h"
 
 using namespace aisx;
@@ -101,6 +101,11 @@ struct aisx_rx {
     aisx_chain* chain = nullptr;
     aisx_hdlc_batch* hd = nullptr;
     aisx_nmea_batch* nm = nullptr;
+    double rate = 0.0;
+    std::vector<std::string> des;      // the designators, one per centre (a NMEA stage made again gets them again)
+    int max_dlen = 0;
+    bool std_nmea = false;             // only after aisx_rx_enable_standard_nmea: the NMEA stage writes the standard form,
+    long long t0 = -1;                 // its tag blocks' time counted from here (-1: none)
     aisx_msg_batch* mg = nullptr;      // only after aisx_rx_enable_messages
     size_t msg_off = 0;                // of the table in a result slot: int32 cols[AISX_MSG_NCOL][max_pdus], char strs[max_pdus][AISX_MSG_STR]
     const int32_t* d_mg_cols = nullptr;
@@ -202,6 +207,9 @@ static int rx_build(aisx_rx* h, double rate, const double* center_freqs, const c
     std::vector<const char*> des((size_t)rows);
     for (int r = 0; r < rows; r++)
         des[r] = designators[r % h->nch];
+    h->rate = rate;
+    h->des.assign(designators, designators + h->nch);
+    h->max_dlen = max_dlen;
     h->text_cap = (long long)h->max_pdus * (nm_text_len(RX_LMAX - 1, max_dlen) + 1);
     if ((rc = aisx_hdlc_batch_create(&h->hd, RX_LMIN, RX_LMAX, rows, h->cap, h->max_pdus)) != AISX_OK ||
         (rc = aisx_nmea_batch_create(&h->nm, des.data(), rows, h->max_pdus, RX_LMAX, (long)h->text_cap)) != AISX_OK ||
@@ -376,6 +384,9 @@ static int rx_issue(aisx_rx* h, long long k, const cf* next)
     } else if ((rc = aisx_hdlc_batch_process(h->hd, h->d_bits[set], h->cap, h->d_prod[set], st)) != AISX_OK)
         return rc;
     AISX_HIPCHK(hipEventRecord(h->ev_tail[set], st));
+    if (h->std_nmea && h->t0 >= 0 && // the block's first item's second (a launch parameter of the stage: nothing waits)
+        (rc = aisx_nmea_batch_set_time(h->nm, h->t0 + (long long)floor((double)k * h->block_items / h->rate))) != AISX_OK)
+        return rc;
     if ((rc = aisx_nmea_batch_process(h->nm, h->d_hd_pdus, h->d_hd_bytes, h->d_hd_count + 1, h->d_hd_count, st)) != AISX_OK)
         return rc;
     hipLaunchKernelGGL(k_rx_meta, dim3(1), dim3(256), 0, st, h->d_msk_status, rows, h->d_hd_count, h->d_nm_count, h->d_ml_flag, h->d_meta);
@@ -633,6 +644,74 @@ extern "C" int aisx_rx_pop_messages(aisx_rx* h, int wait, long long* block, char
     }
     return rx_pop(h, "aisx_rx_pop_messages", wait, block, text, text_cap, text_len, recs, rec_cap, nrecs, rec_cap > 0 ? cols : nullptr,
                   col_stride, strs, status);
+}
+
+extern "C" int aisx_rx_enable_standard_nmea(aisx_rx* h, const char* const* stations, int64_t t0)
+{
+    if (!h) {
+        set_err("aisx_rx_enable_standard_nmea: need a handle");
+        return AISX_ERR_INVALID;
+    }
+    if (h->failed != AISX_OK)
+        return rx_failed(h, "aisx_rx_enable_standard_nmea");
+    if (h->std_nmea || h->acquired || h->submitted > 0) {
+        set_err("aisx_rx_enable_standard_nmea: once, and only before the first acquire, submit or push");
+        return AISX_ERR_INVALID;
+    }
+    if (t0 < 0)
+        t0 = -1;
+    if (const int s = nms_bad_station(stations, h->ns); s >= 0 || !nms_time_ok(t0)) {
+        set_err("aisx_rx_enable_standard_nmea: stations of 0..%d bytes of A-Z a-z 0-9 _ - (station %d is none) and t0 < 10^18", NMS_STATION, s);
+        return AISX_ERR_INVALID;
+    }
+    OnDevice on(h->dev);
+    AISX_HIPCHK(on.err);
+    const int rows = h->ns * h->nch;
+    std::vector<const char*> des((size_t)rows), sta((size_t)rows);
+    int max_slen = 0;
+    for (int r = 0; r < rows; r++) {
+        des[r] = h->des[r % h->nch].c_str();
+        sta[r] = stations ? stations[r / h->nch] : "";
+        max_slen = (int)strlen(sta[r]) > max_slen ? (int)strlen(sta[r]) : max_slen;
+    }
+    // the text grows: nothing is in flight yet, so the result slots are simply made again, what lies behind the text
+    // (the message table, the repair marks) moved up by a multiple of 16 bytes
+    const long long text_cap = (long long)h->max_pdus * (nms_text_len(RX_LMAX - 1, h->max_dlen, nms_tag_len(max_slen, NMS_TIME_DIGITS)) + 1);
+    const size_t grow = ((size_t)(text_cap - h->text_cap) + 15) & ~(size_t)15;
+    PinnedBuf<char> slots[RX_NRES];
+    aisx_nmea_batch* made = nullptr;
+    int rc = aisx_nmea_batch_create_std(&made, des.data(), sta.data(), rows, h->max_pdus, RX_LMAX, (long)text_cap);
+    HandlePtr<aisx_nmea_batch, aisx_nmea_batch_destroy> nm(made);
+    for (int i = 0; rc == AISX_OK && i < RX_NRES; i++)
+        if ((rc = slots[i].alloc(h->res_bytes + grow)) != AISX_OK)
+            set_err("aisx_rx_enable_standard_nmea: %zu bytes of pinned memory for result slot %d could not be had", h->res_bytes + grow, i);
+    const aisx_pdu* d_recs = nullptr;
+    const char* d_text = nullptr;
+    const int* d_count = nullptr;
+    if (rc == AISX_OK)
+        rc = aisx_nmea_batch_results_device(nm.get(), &d_recs, &d_text, &d_count);
+    if (rc != AISX_OK) { // (the handle stays as it was; what is released on the way out must not replace the message)
+        const std::string msg = aisx_last_error();
+        nm.reset();
+        set_err("%s", msg.c_str());
+        return rc;
+    }
+    for (int i = 0; i < RX_NRES; i++)
+        h->h_res[i] = std::move(slots[i]);
+    if (h->mg)
+        h->msg_off += grow;
+    if (h->d_fix)
+        h->fix_off += grow;
+    h->res_bytes += grow;
+    h->text_cap = text_cap;
+    (void)aisx_nmea_batch_destroy(h->nm);
+    h->nm = nm.release();
+    h->d_nm_recs = d_recs;
+    h->d_nm_text = d_text;
+    h->d_nm_count = d_count;
+    h->std_nmea = true;
+    h->t0 = t0;
+    return AISX_OK;
 }
 
 extern "C" int aisx_rx_enable_repair(aisx_rx* h, const aisx_hdlc_rule* rules, int nrules)

@@ -296,7 +296,7 @@ struct NmeaBufs {
     const unsigned char* dlen;
     HdlcRec* out;
     char* text;
-    int* count; // [0] found, [1] records written, [2] bad-input flag
+    int* count; // [0] found, [1] records written, [2] bad-input flag, [3] the standard form's message-id counter
 };
 
 struct NmeaCall {
@@ -339,9 +339,8 @@ struct NmeaPlan {
         count = { 4, true };
     }
 
-    template <class Launch>
-    bool process(const NmeaBufs& b, const HdlcRec* pdus, const unsigned char* bytes, const int* npdus, const int* nfound,
-                 Launch&& launch) const
+    // a call's kernel arguments (the standard form's plan, k_nmea_std.h, starts from them too)
+    NmeaCall call(const NmeaBufs& b, const HdlcRec* pdus, const unsigned char* bytes, const int* npdus, const int* nfound) const
     {
         NmeaCall c;
         NmeaScanParams& s = c.s;
@@ -364,6 +363,14 @@ struct NmeaPlan {
         w.dlen = b.dlen;
         w.text = b.text;
         w.nwaves = write_groups * (write_t / 64);
+        return c;
+    }
+
+    template <class Launch>
+    bool process(const NmeaBufs& b, const HdlcRec* pdus, const unsigned char* bytes, const int* npdus, const int* nfound,
+                 Launch&& launch) const
+    {
+        const NmeaCall c = call(b, pdus, bytes, npdus, nfound);
         return launch(PlanLaunch{ NM_K_SCAN, 1, 1, scan_t, (2 * (scan_t / 64) + 2) * 4 }, c) &&
                launch(PlanLaunch{ NM_K_WRITE, write_groups, 1, write_t, 0 }, c);
     }

@@ -626,6 +626,22 @@ int aisx_hdlc_work_repair(aisx_hdlc* h, const uint8_t* bits, int nbits, uint8_t*
  * writes the NUL-terminated !AIVDM sentence(s) (fragments separated by '\n');
  * returns the string length. */
 int aisx_pdu_to_nmea(const char* designator, const uint8_t* pdu, int len, char* out, int cap);
+/* The same PDU as STANDARD sentences (aisx_pdu_to_nmea keeps three defects of the reference: a wrong last payload
+ * character when len % 3 != 0, the fill count on every fragment, no message id).  With P = ceil(8 len / 6) payload
+ * characters, fill = 6 P - 8 len and F = ceil(P / 56) <= 9 fragments (len <= 378), sentence f of F is
+ *     [tag]!AIVDM,F,f,S,designator,chars,fill_f*HH
+ * character k: message bits 6k .. 6k + 5, most significant first, zero from bit 8 len on (message bit i is bit
+ * 7 - i % 8 of octet i / 8), as v + 48 for v < 40, else v + 56 -- the inverse of the parser's rule below; S the one
+ * digit seq (0..9) when F > 1, else empty; fill_f = fill for f == F, else 0; HH the upper-case hex XOR of the bytes
+ * between '!' and '*'; fragments separated by '\n'.  tag, before every fragment, is \fields*HH\ with fields =
+ * "s:" station (if not empty), ',' (if both), "c:" time in decimal (if time >= 0) and HH the XOR of the field bytes; no
+ * tag block for an empty station and time < 0.  station: NULL or 0..15 bytes of A-Z a-z 0-9 _ -; time: -1 or
+ * 0 .. 10^18 - 1 (the parser reads 18 digits).  Not done: talkers other than AI, VDO, g: group fields, more than nine
+ * fragments.  Writes the NUL-terminated text and returns its length; AISX_ERR_INVALID for anything outside the above. */
+int aisx_pdu_to_nmea_std(const char* designator, const uint8_t* pdu, int len, int seq, const char* station, int64_t time,
+                         char* out, int cap);
+/* the length aisx_pdu_to_nmea_std returns, from the lengths alone (len = 0 gives 0) */
+int aisx_nmea_std_text_len(int len, int dlen, int slen, int64_t time);
 
 /* ------------------------------------------------------------------------ */
 /* batched HDLC deframer on the device: for every channel of a chain step,   */
@@ -711,6 +727,23 @@ int aisx_nmea_batch_results_device(const aisx_nmea_batch* h, const aisx_pdu** d_
  * previous read met bad input (the flag is then cleared). */
 int aisx_nmea_batch_read(aisx_nmea_batch* h, aisx_pdu* recs, int rec_cap, char* text, long text_cap, int* nrecs,
                          int* nfound, void* stream);
+/* A handle in the STANDARD form: per record the text of aisx_pdu_to_nmea_std, byte for byte, with the station of the
+ * record's channel (stations: [nchan], or NULL for none), the handle's time and message ids.  length_max - 1 <= 378;
+ * text_cap = 0 is this form's worst case (the longest designator and station, an 18-digit time, the id digit).
+ * process, results_device, read and destroy work on it as on any handle; records, text layout, counts and flag are
+ * the same.  Ids: one counter per handle, in device memory, 0 after create; a written record of more than one
+ * sentence gets (counter + the written multi-sentence records before it in the list) mod 10, and the call advances
+ * the counter by its written multi-sentence records (records cut by text_cap, refused records and empty payloads take
+ * no id, so the text never skips one). */
+int aisx_nmea_batch_create_std(aisx_nmea_batch** h, const char* const* designators, const char* const* stations, int nchan,
+                               int max_pdus, int length_max, long text_cap);
+/* the c: value of the following process calls' tag blocks (-1, the initial value: none; else 0 .. 10^18 - 1).  A launch
+ * parameter: no synchronisation, no upload.  The three calls below refuse a handle that is not in the standard form. */
+int aisx_nmea_batch_set_time(aisx_nmea_batch* h, int64_t time);
+/* counter = 0 and time = -1; waits for the handle's queued work */
+int aisx_nmea_batch_reset(aisx_nmea_batch* h);
+/* *id = the id the next multi-sentence record will get (synchronises `stream`) */
+int aisx_nmea_batch_next_id(aisx_nmea_batch* h, int* id, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* !AIVDM text back into PDUs: on the host (the specification), and batched   */
@@ -1039,6 +1072,14 @@ int aisx_rx_read_changed_tracks(aisx_rx* h, int* idx, int32_t* cols, long col_st
  * acquire, submit or push (AISX_ERR_INVALID afterwards, and for bt outside [0.1, 1]); a handle on which this was never
  * called allocates, queues and copies nothing more. */
 int aisx_rx_enable_mlse(aisx_rx* h, double bt);
+/* Opt-in: the NMEA stage writes the STANDARD form (aisx_nmea_batch_create_std) in place of the reference's text: rows
+ * s * nchan_per_stream + c carry stations[s] (stations: [nstreams], or NULL for none) in their tag blocks, and block b's
+ * time is t0 + floor((double)b * block_items / rate), evaluated in double -- or none when t0 < 0.  The message ids run
+ * over the handle's blocks in order.  aisx_rx_geometry then reports the larger text capacity of this form; records,
+ * decoder, repair, vessel table and detector work as before.  Once, and only before the first acquire, submit or push
+ * (AISX_ERR_INVALID afterwards, and for a station that is none); a handle on which this was never called runs what it
+ * ran before. */
+int aisx_rx_enable_standard_nmea(aisx_rx* h, const char* const* stations, int64_t t0);
 /* from the next submitted block on (aisx_xlate_set_center_freq of the handle's filter) */
 int aisx_rx_set_center_freq(aisx_rx* h, int stream, int chan, double center_freq);
 /* A failed block (a HIP error, the chain refusing) makes every later call but destroy return that block's error. */
