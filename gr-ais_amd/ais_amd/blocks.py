@@ -865,6 +865,9 @@ class ais_rx:
     ids, tag blocks) where the default, "reference", is the reference's text byte for byte.  stations: None, one str for
     every stream or nstreams str, the s: field of every sentence of that stream; t0: the second of block 0's first
     item, block b's sentences carry c: t0 + floor(b * block_items / rate) -- or no time for t0 < 0.
+
+    Each of these options is also an enable_*() method for a receiver that has not yet taken a slot or a block; the order
+    of the calls does not matter, and one that raises leaves the receiver as it was.
     """
 
     def __init__(self, freq, rate, designator, nstreams=1, fmt="cf32", scale=1.0, bias=0.0, block_items=None,
@@ -912,20 +915,12 @@ class ais_rx:
             raise ValueError("ais_rx: nmea is 'reference' or 'standard'")
         if nmea == "reference" and (stations is not None or t0 >= 0):
             raise ValueError("ais_rx: stations and t0 belong to nmea='standard'")
-        self.nmea = nmea
-        if nmea == "standard":  # (before the geometry is read: the text of a block can be longer)
-            if stations is None or isinstance(stations, (str, bytes)):
-                stations = [stations or ""] * self.nstreams
-            sta = [x.encode() if isinstance(x, str) else bytes(x) for x in stations]
-            if len(sta) != self.nstreams:
-                raise ValueError("ais_rx: %d stations for %d streams" % (len(sta), self.nstreams))
-            check(_lib.lib().aisx_rx_enable_standard_nmea(h, (C.c_char_p * len(sta))(*sta), int(t0)), "ais_rx")
-        d, T, nch, nin, nres, tc = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_long()
-        check(_lib.lib().aisx_rx_geometry(h, C.byref(d), C.byref(T), C.byref(nch), C.byref(nin), C.byref(nres), C.byref(tc)),
-              "ais_rx")
-        self.items_per_block, self.nchan, self.input_slots, self.result_slots = T.value, nch.value, nin.value, nres.value
+        self.nmea = "reference"
+        if nmea == "standard":
+            self.enable_standard_nmea(stations, t0)  # (reads the geometry itself: the text of a block can be longer)
+        else:
+            self._read_geometry()
         self._recs = np.zeros(int(max_pdus_per_block), dtype=PDU_DTYPE)
-        self._text = np.zeros(max(tc.value, 1), dtype=np.uint8)
         self.status = 0  # of the block popped last (AISX_MSK_ST_* | AISX_RX_ST_*)
         self.decode = False
         self._cols = self._strs = None
@@ -949,6 +944,27 @@ class ais_rx:
 
     def _shape(self):
         return (self.nstreams, self.block_items) if self.fmt == _lib.AISX_FMT_CF32 else (self.nstreams, self.block_items, 2)
+
+    def _read_geometry(self):
+        """the handle's geometry, and a text buffer for the longest text a block can give"""
+        d, T, nch, nin, nres, tc = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_long()
+        check(_lib.lib().aisx_rx_geometry(self._h, C.byref(d), C.byref(T), C.byref(nch), C.byref(nin), C.byref(nres), C.byref(tc)),
+              "ais_rx")
+        self.items_per_block, self.nchan, self.input_slots, self.result_slots = T.value, nch.value, nin.value, nres.value
+        self._text = np.zeros(max(tc.value, 1), dtype=np.uint8)
+
+    def enable_standard_nmea(self, stations=None, t0=-1):
+        """what nmea="standard", stations=, t0= does: from the first block on the text is the standard form, which can be
+        longer (the text buffer is made again for it).  ValueError the second time, once a slot has been taken or a block
+        pushed, and for a station the tag block cannot carry."""
+        if stations is None or isinstance(stations, (str, bytes)):
+            stations = [stations or ""] * self.nstreams
+        sta = [x.encode() if isinstance(x, str) else bytes(x) for x in stations]
+        if len(sta) != self.nstreams:
+            raise ValueError("ais_rx: %d stations for %d streams" % (len(sta), self.nstreams))
+        check(_lib.lib().aisx_rx_enable_standard_nmea(self._h, (C.c_char_p * len(sta))(*sta), int(t0)), "ais_rx")
+        self.nmea = "standard"
+        self._read_geometry()
 
     def slot(self):
         """the pinned host slot of the next block as a numpy view ([nstreams][block_items] complex64, or
@@ -987,14 +1003,27 @@ class ais_rx:
         """(block, records, text) of the oldest finished block not yet popped -- records a PDU_DTYPE array (chan,
         end_bit, offset / len of each sentence in text), text the NMEA bytes, '\n' after every sentence -- or None when
         none has finished (wait=True: blocks until the next issued block has; None when none is issued)"""
+        return self._pop(wait, False)
+
+    def _pop(self, wait, messages):
+        """pop() or pop_messages(): one call of the handle's, then the popped block out of the buffers"""
+        from .framing import msg_table
+
         b, tl, nr, st = C.c_longlong(-1), C.c_long(0), C.c_int(0), C.c_int(0)
-        check(_lib.lib().aisx_rx_pop(self._h, 1 if wait else 0, C.byref(b), self._text.ctypes.data_as(C.c_void_p), self._text.size,
-                                     C.byref(tl), self._recs.ctypes.data_as(C.c_void_p), self._recs.size, C.byref(nr),
-                                     C.byref(st)), "ais_rx.pop")
+        args = (self._h, 1 if wait else 0, C.byref(b), self._text.ctypes.data_as(C.c_void_p), self._text.size, C.byref(tl),
+                self._recs.ctypes.data_as(C.c_void_p), self._recs.size, C.byref(nr))
+        if not messages:
+            check(_lib.lib().aisx_rx_pop(*args, C.byref(st)), "ais_rx.pop")
+        else:
+            cols = self._cols.ctypes.data_as(C.c_void_p) if self.decode else None
+            strs = self._strs.ctypes.data_as(C.c_void_p) if self.decode else None
+            check(_lib.lib().aisx_rx_pop_messages(*args, cols, self._cols.shape[1] if self.decode else 0, strs, C.byref(st)),
+                  "ais_rx.pop_messages")
         if b.value < 0:
             return None
         self.status = st.value
-        return b.value, self._recs[: nr.value].copy(), self._text[: tl.value].tobytes()
+        r = (b.value, self._recs[: nr.value].copy(), self._text[: tl.value].tobytes())
+        return r + (msg_table(self._cols, self._strs, nr.value),) if messages else r
 
     def enable_messages(self):
         """what decode=True does: from the first block on, the field decoder runs behind the NMEA stage and
@@ -1010,34 +1039,17 @@ class ais_rx:
     def pop_messages(self, wait=False):
         """pop() plus the block's decoded messages: (block, records, text, messages), messages a MSG_DTYPE array
         with row i = ais_amd.msg_decode of record i's PDU.  Needs decode=True (ValueError otherwise)."""
-        from .framing import msg_table
-
-        b, tl, nr, st = C.c_longlong(-1), C.c_long(0), C.c_int(0), C.c_int(0)
-        cols = self._cols.ctypes.data_as(C.c_void_p) if self.decode else None
-        strs = self._strs.ctypes.data_as(C.c_void_p) if self.decode else None
-        check(_lib.lib().aisx_rx_pop_messages(self._h, 1 if wait else 0, C.byref(b), self._text.ctypes.data_as(C.c_void_p),
-                                              self._text.size, C.byref(tl), self._recs.ctypes.data_as(C.c_void_p), self._recs.size,
-                                              C.byref(nr), cols, self._cols.shape[1] if self.decode else 0, strs, C.byref(st)),
-              "ais_rx.pop_messages")
-        if b.value < 0:
-            return None
-        self.status = st.value
-        return (b.value, self._recs[: nr.value].copy(), self._text[: tl.value].tobytes(),
-                msg_table(self._cols, self._strs, nr.value))
+        return self._pop(wait, True)
 
     def enable_repair(self, rules, events=1):
         """what repair=rules, repair_events=events does: the deframer repairs single-bit errors (events: the error events
         of the mask) by these rules from the first block on.  ValueError once a slot has been taken or a block pushed,
         and for rules the deframer (11, 64) cannot take or a bad mask."""
-        from .framing import REPAIR_SINGLE, repair_rules
+        from .framing import repair_rules
 
         r = repair_rules(rules)
-        if events == REPAIR_SINGLE:
-            rc = _lib.lib().aisx_rx_enable_repair(self._h, r.ctypes.data_as(C.c_void_p) if r.size else None, r.size)
-        else:
-            rc = _lib.lib().aisx_rx_enable_repair_events(self._h, r.ctypes.data_as(C.c_void_p) if r.size else None, r.size,
-                                                        int(events))
-        check(rc, "ais_rx.enable_repair")
+        check(_lib.lib().aisx_rx_enable_repair_events(self._h, r.ctypes.data_as(C.c_void_p) if r.size else None, r.size, int(events)),
+              "ais_rx.enable_repair")
         self.repair = True
 
     def enable_detector(self, detector="mlse", bt=0.4):

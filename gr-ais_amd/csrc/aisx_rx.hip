@@ -1,10 +1,9 @@
 // aisx_rx.hip -- C ABI of the host-fed receiver (include/aisx.h, aisx_rx_*): python/radio.py's ais_rx as one handle
 // for nstreams sources, fed from pinned host memory in the source's own sample format.  Nothing here computes: the
-// handle owns the filter (aisx_xlate), the four stage handles and their chain, the deframer and the NMEA stage (and,
-// once aisx_rx_enable_messages asked for it, the field decoder behind that, after aisx_rx_enable_tracks the vessel
-// table behind the decoder, and after aisx_rx_enable_mlse the sequence detector between the chain step and the
-// deframer), and the rings, streams and events that
-// order them (INTEGRATION.md states the rules; this file is their one home).
+// handle owns the filter (aisx_xlate), the four stage handles and their chain, the tail behind the chain step (RxTail:
+// the deframer and the NMEA stage and, where the aisx_rx_enable_* calls asked for them, the sequence detector before the
+// deframer, the field decoder behind the NMEA stage and the vessel table behind the decoder), and the rings, streams
+// and events that order them (INTEGRATION.md states the rules; this file is their one home).
 //
 //   block b, submitted:   copy stream    pinned slot b % NPIN -> raw buffer b % NRAW      (after filter b - NRAW)
 //                         filter stream  raw buffer -> row buffer b % NROW                (after wait_input(b - NROW))
@@ -87,59 +86,104 @@ __global__ __launch_bounds__(256) void k_rx_meta(const int* __restrict__ msk_sta
     }
 }
 
+// what the aisx_rx_enable_* calls have asked for; a new receiver has the default record
+struct RxOptions {
+    bool messages = false;              // the field decoder behind the NMEA stage
+    bool tracks = false;                // the vessel table behind the decoder,
+    int capacity = 0;                   // of so many vessels (the table's create judges the number)
+    std::vector<aisx_hdlc_rule> rules;  // the deframer's repair: on with at least one rule,
+    int events = AISX_HDLC_EV_SINGLE;   // and the error events to look for
+    bool detector = false;              // the sequence detector between the chain step and the deframer,
+    double bt = 0.0;                    // of this BT
+    bool std_nmea = false;              // the NMEA stage writes the standard form, with
+    std::vector<std::string> stations;  // these stations, one per stream,
+    long long t0 = -1;                  // and its tag blocks' time counted from here (-1: none)
+};
+
+// a pinned result slot: byte offsets of its areas in this order, the optional ones 16-byte aligned, and its size
+struct RxLayout {
+    size_t recs = 0; // aisx_pdu recs[max_pdus], behind int meta[RX_META] at 0
+    size_t text = 0; // char text[text_cap]
+    size_t cols = 0; // with messages: int32 cols[AISX_MSG_NCOL][max_pdus],
+    size_t strs = 0; // char strs[max_pdus][AISX_MSG_STR]
+    size_t fix = 0;  // with repair: int32 fix_bits[max_pdus]
+    size_t bytes = 0;
+};
+
+static RxLayout rx_layout(int max_pdus, long long text_cap, bool messages, bool repair)
+{
+    const auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t n = (size_t)max_pdus;
+    RxLayout l;
+    l.recs = sizeof(int) * RX_META;
+    l.text = l.recs + sizeof(aisx_pdu) * n;
+    l.bytes = l.text + (size_t)text_cap;
+    if (messages) {
+        l.cols = up16(l.bytes);
+        l.strs = l.cols + sizeof(int32_t) * AISX_MSG_NCOL * n;
+        l.bytes = l.strs + (size_t)AISX_MSG_STR * n;
+    }
+    if (repair) {
+        l.fix = up16(l.bytes);
+        l.bytes = l.fix + sizeof(int32_t) * n;
+    }
+    return l;
+}
+
+// everything behind the chain step, made whole from one RxOptions by rx_make_tail.  What an option does not ask for stays
+// empty: nothing is allocated, queued or copied for it.  (The stage handles stand last: destroyed before the buffers.)
+struct RxTail {
+    long long text_cap = 0;
+    RxLayout lay;
+    PinnedBuf<char> h_res[RX_NRES];
+    int mstride = 0;                 // row stride of d_mbits: cap + what the detector carries
+    DevBuf<cf> d_syms[RX_NOUT];      // [ns * nch][cap], only with the detector
+    DevBuf<uint8_t> d_mbits;         // [ns * nch][mstride] the detector's bits (read by the deframer behind it on the tail stream)
+    DevBuf<int> d_mnb;
+    const int* d_ml_flag = nullptr;
+    const aisx_pdu *d_hd_pdus = nullptr, *d_nm_recs = nullptr;
+    const uint8_t* d_hd_bytes = nullptr;
+    const char* d_nm_text = nullptr;
+    const int *d_hd_count = nullptr, *d_nm_count = nullptr, *d_mg_count = nullptr;
+    const int32_t* d_fix = nullptr;  // the deframer's marks, only with repair
+    const int32_t* d_mg_cols = nullptr;
+    const char* d_mg_strs = nullptr;
+    HandlePtr<aisx_mlse_batch, aisx_mlse_batch_destroy> ml;
+    HandlePtr<aisx_hdlc_batch, aisx_hdlc_batch_destroy> hd;
+    HandlePtr<aisx_nmea_batch, aisx_nmea_batch_destroy> nm;
+    HandlePtr<aisx_msg_batch, aisx_msg_batch_destroy> mg;
+    HandlePtr<aisx_track_batch, aisx_track_batch_destroy> tk;
+};
+
 struct aisx_rx {
     int dev = 0;
     int fmt = 0, item_bytes = 0, ns = 0, nch = 0, D = 0, T = 0, block_items = 0, max_pdus = 0, cap = 0;
     float scale = 1.f, bias = 0.f;
-    long long text_cap = 0;
-    size_t raw_bytes = 0, res_bytes = 0;
+    size_t raw_bytes = 0;
     aisx_xlate* xl = nullptr;
     aisx_freqsync* fs = nullptr;
     aisx_agc* agc = nullptr;
     aisx_corr* corr = nullptr;
     aisx_msk* msk = nullptr;
     aisx_chain* chain = nullptr;
-    aisx_hdlc_batch* hd = nullptr;
-    aisx_nmea_batch* nm = nullptr;
     double rate = 0.0;
-    std::vector<std::string> des;      // the designators, one per centre (a NMEA stage made again gets them again)
+    std::vector<std::string> des;      // the designators, one per centre
     int max_dlen = 0;
-    bool std_nmea = false;             // only after aisx_rx_enable_standard_nmea: the NMEA stage writes the standard form,
-    long long t0 = -1;                 // its tag blocks' time counted from here (-1: none)
-    aisx_msg_batch* mg = nullptr;      // only after aisx_rx_enable_messages
-    size_t msg_off = 0;                // of the table in a result slot: int32 cols[AISX_MSG_NCOL][max_pdus], char strs[max_pdus][AISX_MSG_STR]
-    const int32_t* d_mg_cols = nullptr;
-    const char* d_mg_strs = nullptr;
-    const int* d_mg_count = nullptr;
-    aisx_track_batch* tk = nullptr;    // only after aisx_rx_enable_tracks: the vessel table, updated behind the decoder
-    const int32_t* d_fix = nullptr;    // only after aisx_rx_enable_repair: the deframer's marks,
-    size_t fix_off = 0;                // and where they go in a result slot: int32 fix_bits[max_pdus]
-    std::vector<int32_t> popped_fix;   // the marks of the block popped last
-    std::vector<aisx_hdlc_rule> rules; // what aisx_rx_enable_repair set (a deframer made again gets them again),
-    int events = AISX_HDLC_EV_SINGLE;  // and the error events to look for
-    aisx_mlse_batch* ml = nullptr;     // only after aisx_rx_enable_mlse: the detector between the chain step and the deframer
-    const int* d_ml_flag = nullptr;
-    int mstride = 0;                   // row stride of d_mbits: cap + what the detector carries
+    RxOptions opt;
+    std::vector<int32_t> popped_fix;   // the repair marks of the block popped last
     Stream s_copy, s_filt, s_tail;     // (before the buffers and events used on them: destroyed after those)
     PinnedBuf<char> h_in[RX_NPIN];     // pinned [ns][block_items] items
     DevBuf<char> d_raw[RX_NRAW];
     DevBuf<cf> d_row[RX_NROW];         // [ns * nch][T]
     DevBuf<uint8_t> d_bits[RX_NOUT];   // [ns * nch][cap]
     DevBuf<int> d_prod[RX_NOUT];
-    DevBuf<cf> d_syms[RX_NOUT];        // [ns * nch][cap], only with the detector
-    DevBuf<uint8_t> d_mbits;           // [ns * nch][mstride] the detector's bits (read by the deframer behind it on the tail stream)
-    DevBuf<int> d_mnb;
     DevBuf<int> d_meta;
-    PinnedBuf<char> h_res[RX_NRES];    // pinned: int meta[RX_META], aisx_pdu recs[max_pdus], char text[text_cap]
     Event ev_copy[RX_NPIN];            // the slot's copy to the device has finished
     Event ev_filt[RX_NRAW];            // the raw buffer's filter call has finished
     Event ev_tail[RX_NOUT];            // the deframer has read this set of bits / produced
     Event ev_res[RX_NRES];             // the result slot is complete
+    RxTail tail;                       // what opt asks for (behind every other owner: its stage handles are the first to go)
     const int* d_msk_status = nullptr;
-    const aisx_pdu *d_hd_pdus = nullptr, *d_nm_recs = nullptr;
-    const uint8_t* d_hd_bytes = nullptr;
-    const char* d_nm_text = nullptr;
-    const int *d_hd_count = nullptr, *d_nm_count = nullptr;
     long long submitted = 0, issued = 0, popped = 0; // blocks copied and filtered; steps issued; results taken
     bool acquired = false;
     int failed = AISX_OK;
@@ -173,18 +217,75 @@ extern "C" int aisx_rx_destroy(aisx_rx* h)
     }
     if (h->s_tail)
         (void)hipStreamSynchronize(h->s_tail);
-    (void)aisx_track_batch_destroy(h->tk);
-    (void)aisx_msg_batch_destroy(h->mg);
-    (void)aisx_nmea_batch_destroy(h->nm);
-    (void)aisx_hdlc_batch_destroy(h->hd);
-    (void)aisx_mlse_batch_destroy(h->ml);
     (void)aisx_msk_destroy(h->msk);
     (void)aisx_corr_destroy(h->corr);
     (void)aisx_agc_destroy(h->agc);
     (void)aisx_freqsync_destroy(h->fs);
     (void)aisx_xlate_destroy(h->xl);
-    // (the sub-handles are gone before the receiver's own buffers, events and, last, streams)
+    // (the tail's stage handles go first in here: every sub-handle is gone before the receiver's own buffers, events
+    // and, last, streams)
     delete h;
+    return AISX_OK;
+}
+
+// a stage's create into the owner of its handle
+template <class H, int (*Destroy)(H*), class... A, class... B>
+static int rx_make(HandlePtr<H, Destroy>& p, int (*create)(H**, A...), B... args)
+{
+    H* made = nullptr;
+    const int rc = create(&made, args...);
+    p.reset(made);
+    return rc;
+}
+
+// The tail `o` asks for, whole, into the empty *t: the one place that knows what an option needs of the stages and of a
+// result slot.  The stages refuse what they cannot take (a BT, a capacity, rules, a mask) with their own message.
+static int rx_make_tail(const aisx_rx* h, const RxOptions& o, const char* who, RxTail* t)
+{
+    int rc;
+    const int rows = h->ns * h->nch, cap = h->cap;
+    std::vector<const char*> des((size_t)rows), sta((size_t)rows);
+    int max_slen = 0;
+    for (int r = 0; r < rows; r++) {
+        des[r] = h->des[r % h->nch].c_str();
+        sta[r] = o.std_nmea ? o.stations[r / h->nch].c_str() : "";
+        max_slen = std::max(max_slen, (int)strlen(sta[r]));
+    }
+    if (o.detector) { // the step's symbols -> the detector's bits and counts, a step's and the carried ones
+        t->mstride = cap + MLSE_EXTRA;
+        if ((rc = rx_make(t->ml, aisx_mlse_batch_create, o.bt, rows, cap)) != AISX_OK ||
+            (rc = aisx_mlse_batch_status_device(t->ml.get(), &t->d_ml_flag)) != AISX_OK ||
+            (rc = t->d_mbits.alloc((size_t)rows * t->mstride, false)) != AISX_OK || (rc = t->d_mnb.alloc((size_t)rows)) != AISX_OK)
+            return rc;
+        for (auto& b : t->d_syms)
+            if ((rc = b.alloc((size_t)rows * cap, false)) != AISX_OK)
+                return rc;
+    }
+    if ((rc = rx_make(t->hd, aisx_hdlc_batch_create, RX_LMIN, RX_LMAX, rows, o.detector ? t->mstride : cap, h->max_pdus)) != AISX_OK ||
+        (rc = aisx_hdlc_batch_results_device(t->hd.get(), &t->d_hd_pdus, &t->d_hd_bytes, &t->d_hd_count)) != AISX_OK)
+        return rc;
+    if (!o.rules.empty() && ((rc = aisx_hdlc_batch_set_repair_events(t->hd.get(), o.rules.data(), (int)o.rules.size(), o.events)) != AISX_OK ||
+                             (rc = aisx_hdlc_batch_repairs_device(t->hd.get(), &t->d_fix)) != AISX_OK))
+        return rc;
+    const int sentence = o.std_nmea ? nms_text_len(RX_LMAX - 1, h->max_dlen, nms_tag_len(max_slen, NMS_TIME_DIGITS))
+                                    : nm_text_len(RX_LMAX - 1, h->max_dlen);
+    t->text_cap = (long long)h->max_pdus * (sentence + 1);
+    rc = o.std_nmea ? rx_make(t->nm, aisx_nmea_batch_create_std, des.data(), sta.data(), rows, h->max_pdus, RX_LMAX, (long)t->text_cap)
+                    : rx_make(t->nm, aisx_nmea_batch_create, des.data(), rows, h->max_pdus, RX_LMAX, (long)t->text_cap);
+    if (rc != AISX_OK || (rc = aisx_nmea_batch_results_device(t->nm.get(), &t->d_nm_recs, &t->d_nm_text, &t->d_nm_count)) != AISX_OK)
+        return rc;
+    if (o.messages && ((rc = rx_make(t->mg, aisx_msg_batch_create, rows, h->max_pdus, RX_LMAX)) != AISX_OK ||
+                       (rc = aisx_msg_batch_results_device(t->mg.get(), &t->d_mg_cols, nullptr, &t->d_mg_strs, &t->d_mg_count)) != AISX_OK))
+        return rc;
+    if (o.tracks && (rc = rx_make(t->tk, aisx_track_batch_create, o.capacity, h->max_pdus)) != AISX_OK)
+        return rc;
+    t->lay = rx_layout(h->max_pdus, t->text_cap, o.messages, !o.rules.empty());
+    for (int i = 0; i < RX_NRES; i++)
+        if ((rc = t->h_res[i].alloc(t->lay.bytes)) != AISX_OK) {
+            set_err("%s: %zu bytes of pinned memory for result slot %d could not be had", who, t->lay.bytes, i);
+            return rc;
+        }
+    AISX_HIPCHK(hipDeviceSynchronize()); // (the buffers were zeroed on the null stream, which the handle's streams do not follow)
     return AISX_OK;
 }
 
@@ -204,21 +305,12 @@ static int rx_build(aisx_rx* h, double rate, const double* center_freqs, const c
         (rc = aisx_chain_create(&h->chain, h->fs, h->agc, h->corr, h->msk, rows, T, RX_FFTLEN)) != AISX_OK)
         return rc;
     h->cap = aisx_msk_out_capacity(h->msk);
-    std::vector<const char*> des((size_t)rows);
-    for (int r = 0; r < rows; r++)
-        des[r] = designators[r % h->nch];
     h->rate = rate;
     h->des.assign(designators, designators + h->nch);
     h->max_dlen = max_dlen;
-    h->text_cap = (long long)h->max_pdus * (nm_text_len(RX_LMAX - 1, max_dlen) + 1);
-    if ((rc = aisx_hdlc_batch_create(&h->hd, RX_LMIN, RX_LMAX, rows, h->cap, h->max_pdus)) != AISX_OK ||
-        (rc = aisx_nmea_batch_create(&h->nm, des.data(), rows, h->max_pdus, RX_LMAX, (long)h->text_cap)) != AISX_OK ||
-        (rc = aisx_msk_status_device(h->msk, &h->d_msk_status)) != AISX_OK ||
-        (rc = aisx_hdlc_batch_results_device(h->hd, &h->d_hd_pdus, &h->d_hd_bytes, &h->d_hd_count)) != AISX_OK ||
-        (rc = aisx_nmea_batch_results_device(h->nm, &h->d_nm_recs, &h->d_nm_text, &h->d_nm_count)) != AISX_OK)
+    if ((rc = aisx_msk_status_device(h->msk, &h->d_msk_status)) != AISX_OK)
         return rc;
     h->raw_bytes = (size_t)h->ns * h->block_items * h->item_bytes;
-    h->res_bytes = sizeof(int) * RX_META + sizeof(aisx_pdu) * (size_t)h->max_pdus + (size_t)h->text_cap;
     for (auto& b : h->d_raw)
         if ((rc = b.alloc(h->raw_bytes, false)) != AISX_OK)
             return rc;
@@ -233,9 +325,6 @@ static int rx_build(aisx_rx* h, double rate, const double* center_freqs, const c
     for (auto& b : h->h_in)
         if ((rc = b.alloc(h->raw_bytes)) != AISX_OK)
             return rc;
-    for (auto& b : h->h_res)
-        if ((rc = b.alloc(h->res_bytes)) != AISX_OK)
-            return rc;
     for (Stream* s : { &h->s_copy, &h->s_filt, &h->s_tail })
         if ((rc = s->create_nonblocking()) != AISX_OK)
             return rc;
@@ -248,8 +337,7 @@ static int rx_build(aisx_rx* h, double rate, const double* center_freqs, const c
     if ((rc = make(h->ev_copy, RX_NPIN)) != AISX_OK || (rc = make(h->ev_filt, RX_NRAW)) != AISX_OK ||
         (rc = make(h->ev_tail, RX_NOUT)) != AISX_OK || (rc = make(h->ev_res, RX_NRES)) != AISX_OK)
         return rc;
-    AISX_HIPCHK(hipDeviceSynchronize()); // (the buffers were zeroed on the null stream, which the handle's streams do not follow)
-    return AISX_OK;
+    return rx_make_tail(h, h->opt, "aisx_rx_create", &h->tail); // (last: it waits for the zero fills of the buffers above too)
 }
 
 extern "C" int aisx_rx_create(aisx_rx** out, double rate, int nstreams, int nchan_per_stream, const double* center_freqs,
@@ -334,7 +422,7 @@ extern "C" int aisx_rx_geometry(const aisx_rx* h, int* decim, int* items_per_blo
     if (result_slots)
         *result_slots = RX_NRES;
     if (text_cap)
-        *text_cap = (long)h->text_cap;
+        *text_cap = (long)h->tail.text_cap;
     return AISX_OK;
 }
 
@@ -362,12 +450,14 @@ extern "C" int aisx_rx_acquire(aisx_rx* h, void** slot, long* stride_items)
 static int rx_issue(aisx_rx* h, long long k, const cf* next)
 {
     int rc;
+    const RxTail& t = h->tail;
+    const RxLayout& lay = t.lay;
     const int set = (int)(k % RX_NOUT), res = (int)(k % RX_NRES), rows = h->ns * h->nch, T = h->T;
     if (k >= RX_NOUT) // the deframer has read this set's bits of step k - NOUT
         AISX_HIPCHK(hipStreamWaitEvent(h->s_filt, h->ev_tail[set], 0));
     long long step = -1;
     if ((rc = aisx_chain_step(h->chain, (const aisx_cf32*)h->d_row[k % RX_NROW].get(), T, T, (const aisx_cf32*)next, T, next ? T : 0,
-                              h->ml ? (aisx_cf32*)h->d_syms[set].get() : nullptr, h->d_bits[set], h->cap, h->d_prod[set], h->s_filt, &step)) != AISX_OK)
+                              t.ml ? (aisx_cf32*)t.d_syms[set].get() : nullptr, h->d_bits[set], h->cap, h->d_prod[set], h->s_filt, &step)) != AISX_OK)
         return rc;
     if (step != k) {
         set_err("aisx_rx: the chain numbered block %lld as step %lld", k, step);
@@ -376,45 +466,43 @@ static int rx_issue(aisx_rx* h, long long k, const cf* next)
     hipStream_t st = h->s_tail;
     if ((rc = aisx_chain_wait(h->chain, k, st, 0)) != AISX_OK)
         return rc;
-    if (h->ml) { // the step's symbols -> the detector's bits and counts -> the deframer
-        if ((rc = aisx_mlse_batch_process(h->ml, (const aisx_cf32*)h->d_syms[set].get(), h->cap, h->d_prod[set], h->d_mbits, h->mstride,
-                                          h->d_mnb, st)) != AISX_OK ||
-            (rc = aisx_hdlc_batch_process(h->hd, h->d_mbits, h->mstride, h->d_mnb, st)) != AISX_OK)
+    if (t.ml) { // the step's symbols -> the detector's bits and counts -> the deframer
+        if ((rc = aisx_mlse_batch_process(t.ml.get(), (const aisx_cf32*)t.d_syms[set].get(), h->cap, h->d_prod[set], t.d_mbits, t.mstride,
+                                          t.d_mnb, st)) != AISX_OK ||
+            (rc = aisx_hdlc_batch_process(t.hd.get(), t.d_mbits, t.mstride, t.d_mnb, st)) != AISX_OK)
             return rc;
-    } else if ((rc = aisx_hdlc_batch_process(h->hd, h->d_bits[set], h->cap, h->d_prod[set], st)) != AISX_OK)
+    } else if ((rc = aisx_hdlc_batch_process(t.hd.get(), h->d_bits[set], h->cap, h->d_prod[set], st)) != AISX_OK)
         return rc;
     AISX_HIPCHK(hipEventRecord(h->ev_tail[set], st));
-    if (h->std_nmea && h->t0 >= 0 && // the block's first item's second (a launch parameter of the stage: nothing waits)
-        (rc = aisx_nmea_batch_set_time(h->nm, h->t0 + (long long)floor((double)k * h->block_items / h->rate))) != AISX_OK)
+    if (h->opt.std_nmea && h->opt.t0 >= 0 && // the block's first item's second (a launch parameter of the stage: nothing waits)
+        (rc = aisx_nmea_batch_set_time(t.nm.get(), h->opt.t0 + (long long)floor((double)k * h->block_items / h->rate))) != AISX_OK)
         return rc;
-    if ((rc = aisx_nmea_batch_process(h->nm, h->d_hd_pdus, h->d_hd_bytes, h->d_hd_count + 1, h->d_hd_count, st)) != AISX_OK)
+    if ((rc = aisx_nmea_batch_process(t.nm.get(), t.d_hd_pdus, t.d_hd_bytes, t.d_hd_count + 1, t.d_hd_count, st)) != AISX_OK)
         return rc;
-    hipLaunchKernelGGL(k_rx_meta, dim3(1), dim3(256), 0, st, h->d_msk_status, rows, h->d_hd_count, h->d_nm_count, h->d_ml_flag, h->d_meta);
+    hipLaunchKernelGGL(k_rx_meta, dim3(1), dim3(256), 0, st, h->d_msk_status, rows, t.d_hd_count, t.d_nm_count, t.d_ml_flag, h->d_meta);
     AISX_HIPCHK(hipGetLastError());
     // (the bad-input flags are this block's: cleared behind the record that took them)
-    AISX_HIPCHK(hipMemsetAsync((void*)(h->d_hd_count + 2), 0, sizeof(int), st));
-    AISX_HIPCHK(hipMemsetAsync((void*)(h->d_nm_count + 2), 0, sizeof(int), st));
-    if (h->d_ml_flag)
-        AISX_HIPCHK(hipMemsetAsync((void*)h->d_ml_flag, 0, sizeof(int), st));
-    char* r = h->h_res[res];
-    if (h->mg) { // the rows of the records the NMEA stage kept; its bad-input flag goes into the record's spare word
-        if ((rc = aisx_msg_batch_process(h->mg, h->d_hd_pdus, h->d_hd_bytes, h->d_nm_count + 1, h->d_hd_count, st)) != AISX_OK)
+    AISX_HIPCHK(hipMemsetAsync((void*)(t.d_hd_count + 2), 0, sizeof(int), st));
+    AISX_HIPCHK(hipMemsetAsync((void*)(t.d_nm_count + 2), 0, sizeof(int), st));
+    if (t.d_ml_flag)
+        AISX_HIPCHK(hipMemsetAsync((void*)t.d_ml_flag, 0, sizeof(int), st));
+    char* r = t.h_res[res];
+    if (t.mg) { // the rows of the records the NMEA stage kept; its bad-input flag goes into the record's spare word
+        if ((rc = aisx_msg_batch_process(t.mg.get(), t.d_hd_pdus, t.d_hd_bytes, t.d_nm_count + 1, t.d_hd_count, st)) != AISX_OK)
             return rc;
-        if (h->tk && (rc = aisx_track_batch_process(h->tk, h->d_mg_cols, h->max_pdus, h->d_mg_strs, h->d_hd_pdus, h->d_mg_count + 1,
-                                                    (int32_t)k, st)) != AISX_OK)
+        if (t.tk && (rc = aisx_track_batch_process(t.tk.get(), t.d_mg_cols, h->max_pdus, t.d_mg_strs, t.d_hd_pdus, t.d_mg_count + 1,
+                                                   (int32_t)k, st)) != AISX_OK)
             return rc;
-        AISX_HIPCHK(hipMemcpyAsync(h->d_meta + 7, h->d_mg_count + 2, sizeof(int), hipMemcpyDeviceToDevice, st));
-        AISX_HIPCHK(hipMemsetAsync((void*)(h->d_mg_count + 2), 0, sizeof(int), st));
-        const size_t cols_bytes = sizeof(int32_t) * AISX_MSG_NCOL * (size_t)h->max_pdus, strs_bytes = (size_t)AISX_MSG_STR * h->max_pdus;
-        AISX_HIPCHK(hipMemcpyAsync(r + h->msg_off, h->d_mg_cols, cols_bytes, hipMemcpyDeviceToHost, st));
-        AISX_HIPCHK(hipMemcpyAsync(r + h->msg_off + cols_bytes, h->d_mg_strs, strs_bytes, hipMemcpyDeviceToHost, st));
+        AISX_HIPCHK(hipMemcpyAsync(h->d_meta + 7, t.d_mg_count + 2, sizeof(int), hipMemcpyDeviceToDevice, st));
+        AISX_HIPCHK(hipMemsetAsync((void*)(t.d_mg_count + 2), 0, sizeof(int), st));
+        AISX_HIPCHK(hipMemcpyAsync(r + lay.cols, t.d_mg_cols, lay.strs - lay.cols, hipMemcpyDeviceToHost, st));
+        AISX_HIPCHK(hipMemcpyAsync(r + lay.strs, t.d_mg_strs, (size_t)AISX_MSG_STR * h->max_pdus, hipMemcpyDeviceToHost, st));
     }
-    if (h->d_fix)
-        AISX_HIPCHK(hipMemcpyAsync(r + h->fix_off, h->d_fix, sizeof(int32_t) * (size_t)h->max_pdus, hipMemcpyDeviceToHost, st));
+    if (t.d_fix)
+        AISX_HIPCHK(hipMemcpyAsync(r + lay.fix, t.d_fix, sizeof(int32_t) * (size_t)h->max_pdus, hipMemcpyDeviceToHost, st));
     AISX_HIPCHK(hipMemcpyAsync(r, h->d_meta, sizeof(int) * RX_META, hipMemcpyDeviceToHost, st));
-    AISX_HIPCHK(hipMemcpyAsync(r + sizeof(int) * RX_META, h->d_nm_recs, sizeof(aisx_pdu) * (size_t)h->max_pdus, hipMemcpyDeviceToHost, st));
-    AISX_HIPCHK(hipMemcpyAsync(r + sizeof(int) * RX_META + sizeof(aisx_pdu) * (size_t)h->max_pdus, h->d_nm_text, (size_t)h->text_cap,
-                               hipMemcpyDeviceToHost, st));
+    AISX_HIPCHK(hipMemcpyAsync(r + lay.recs, t.d_nm_recs, lay.text - lay.recs, hipMemcpyDeviceToHost, st));
+    AISX_HIPCHK(hipMemcpyAsync(r + lay.text, t.d_nm_text, (size_t)t.text_cap, hipMemcpyDeviceToHost, st));
     AISX_HIPCHK(hipEventRecord(h->ev_res[res], st));
     h->issued = k + 1;
     return AISX_OK;
@@ -515,10 +603,14 @@ extern "C" int aisx_rx_flush(aisx_rx* h)
     return rc != AISX_OK ? rx_fail(h, rc) : AISX_OK;
 }
 
-// aisx_rx_pop, and with cols / strs aisx_rx_pop_messages (the arguments have been checked)
-static int rx_pop(aisx_rx* h, const char* who, int wait, long long* block, char* text, long text_cap, long* text_len, aisx_pdu* recs,
-                  int rec_cap, int* nrecs, int32_t* cols, long col_stride, char* strs, int* status)
+// aisx_rx_pop, and with cols / strs aisx_rx_pop_messages; `extra_ok`: what the caller needs beyond the shared argument rule
+static int rx_pop(aisx_rx* h, const char* who, const char* need, bool extra_ok, int wait, long long* block, char* text, long text_cap,
+                  long* text_len, aisx_pdu* recs, int rec_cap, int* nrecs, int32_t* cols, long col_stride, char* strs, int* status)
 {
+    if (!h || !block || !text_len || !nrecs || text_cap < 0 || rec_cap < 0 || (text_cap > 0 && !text) || (rec_cap > 0 && !recs) || !extra_ok) {
+        set_err("%s: need a handle, outputs for the block number and the counts, %s", who, need);
+        return AISX_ERR_INVALID;
+    }
     if (h->failed != AISX_OK)
         return rx_failed(h, who);
     *block = -1;
@@ -543,10 +635,10 @@ static int rx_pop(aisx_rx* h, const char* who, int wait, long long* block, char*
             return rx_fail(h, AISX_ERR_HIP);
         }
     }
-    const char* r = h->h_res[res];
+    const RxLayout& lay = h->tail.lay;
+    const char* r = h->tail.h_res[res];
     const int* meta = (const int*)r;
-    const aisx_pdu* rr = (const aisx_pdu*)(r + sizeof(int) * RX_META);
-    const char* tt = r + sizeof(int) * RX_META + sizeof(aisx_pdu) * (size_t)h->max_pdus;
+    const aisx_pdu* rr = (const aisx_pdu*)(r + lay.recs);
     int k = meta[5]; // records the NMEA stage wrote
     if (k < 0 || k > h->max_pdus)
         k = 0;
@@ -561,15 +653,15 @@ static int rx_pop(aisx_rx* h, const char* who, int wait, long long* block, char*
     if (k > 0)
         memcpy(recs, rr, sizeof(aisx_pdu) * (size_t)k);
     if (nt > 0)
-        memcpy(text, tt, (size_t)nt);
+        memcpy(text, r + lay.text, (size_t)nt);
     if (cols && k > 0) {
-        const int32_t* cc = (const int32_t*)(r + h->msg_off);
+        const int32_t* cc = (const int32_t*)(r + lay.cols);
         for (int c = 0; c < AISX_MSG_NCOL; c++)
             memcpy(cols + (size_t)c * col_stride, cc + (size_t)c * h->max_pdus, sizeof(int32_t) * (size_t)k);
-        memcpy(strs, r + h->msg_off + sizeof(int32_t) * AISX_MSG_NCOL * (size_t)h->max_pdus, (size_t)AISX_MSG_STR * k);
+        memcpy(strs, r + lay.strs, (size_t)AISX_MSG_STR * k);
     }
-    if (h->d_fix) // (the NMEA stage's records are the first k of the deframer's)
-        h->popped_fix.assign((const int32_t*)(r + h->fix_off), (const int32_t*)(r + h->fix_off) + k);
+    if (h->tail.d_fix) // (the NMEA stage's records are the first k of the deframer's)
+        h->popped_fix.assign((const int32_t*)(r + lay.fix), (const int32_t*)(r + lay.fix) + k);
     if (status)
         *status = meta[0] | (meta[1] > meta[2] ? AISX_RX_ST_HDLC_OVERFLOW : 0) | (meta[5] < meta[2] ? AISX_RX_ST_NMEA_OVERFLOW : 0) |
                   ((meta[3] || meta[6] || meta[7]) ? AISX_RX_ST_BAD_COUNT : 0);
@@ -580,138 +672,80 @@ static int rx_pop(aisx_rx* h, const char* who, int wait, long long* block, char*
 extern "C" int aisx_rx_pop(aisx_rx* h, int wait, long long* block, char* text, long text_cap, long* text_len, aisx_pdu* recs,
                            int rec_cap, int* nrecs, int* status)
 {
-    if (!h || !block || !text_len || !nrecs || text_cap < 0 || rec_cap < 0 || (text_cap > 0 && !text) || (rec_cap > 0 && !recs)) {
-        set_err("aisx_rx_pop: need a handle, outputs for the block number and the counts, and buffers for their capacities");
-        return AISX_ERR_INVALID;
-    }
-    return rx_pop(h, "aisx_rx_pop", wait, block, text, text_cap, text_len, recs, rec_cap, nrecs, nullptr, 0, nullptr, status);
-}
-
-extern "C" int aisx_rx_enable_messages(aisx_rx* h)
-{
-    if (!h) {
-        set_err("aisx_rx_enable_messages: need a handle");
-        return AISX_ERR_INVALID;
-    }
-    if (h->failed != AISX_OK)
-        return rx_failed(h, "aisx_rx_enable_messages");
-    if (h->mg)
-        return AISX_OK;
-    if (h->acquired || h->submitted > 0) {
-        set_err("aisx_rx_enable_messages: only before the first acquire, submit or push");
-        return AISX_ERR_INVALID;
-    }
-    OnDevice on(h->dev);
-    AISX_HIPCHK(on.err);
-    // the result slots grow by the table: nothing is in flight yet, so they are simply made again
-    const size_t msg_off = (h->res_bytes + 15) & ~(size_t)15;
-    const size_t bytes = msg_off + (sizeof(int32_t) * AISX_MSG_NCOL + AISX_MSG_STR) * (size_t)h->max_pdus;
-    PinnedBuf<char> slots[RX_NRES];
-    aisx_msg_batch* made = nullptr;
-    int rc = aisx_msg_batch_create(&made, h->ns * h->nch, h->max_pdus, RX_LMAX);
-    HandlePtr<aisx_msg_batch, aisx_msg_batch_destroy> mg(made);
-    for (int i = 0; rc == AISX_OK && i < RX_NRES; i++)
-        if ((rc = slots[i].alloc(bytes)) != AISX_OK)
-            set_err("aisx_rx_enable_messages: %zu bytes of pinned memory for result slot %d could not be had", bytes, i);
-    if (rc == AISX_OK)
-        rc = aisx_msg_batch_results_device(mg.get(), &h->d_mg_cols, nullptr, &h->d_mg_strs, &h->d_mg_count);
-    if (rc != AISX_OK) { // (the handle stays as it was; what is released on the way out must not replace the message)
-        const std::string msg = aisx_last_error();
-        mg.reset();
-        set_err("%s", msg.c_str());
-        return rc;
-    }
-    for (int i = 0; i < RX_NRES; i++)
-        h->h_res[i] = std::move(slots[i]);
-    h->msg_off = msg_off;
-    h->res_bytes = bytes;
-    h->mg = mg.release();
-    return AISX_OK;
+    return rx_pop(h, "aisx_rx_pop", "and buffers for their capacities", true, wait, block, text, text_cap, text_len, recs, rec_cap, nrecs,
+                  nullptr, 0, nullptr, status);
 }
 
 extern "C" int aisx_rx_pop_messages(aisx_rx* h, int wait, long long* block, char* text, long text_cap, long* text_len, aisx_pdu* recs,
                                     int rec_cap, int* nrecs, int32_t* cols, long col_stride, char* strs, int* status)
 {
-    if (h && !h->mg) {
+    if (h && !h->tail.mg) {
         set_err("aisx_rx_pop_messages: aisx_rx_enable_messages was not called on this handle");
         return AISX_ERR_INVALID;
     }
-    if (!h || !block || !text_len || !nrecs || text_cap < 0 || rec_cap < 0 || (text_cap > 0 && !text) || (rec_cap > 0 && !recs) ||
-        (rec_cap > 0 && (!cols || !strs)) || col_stride < rec_cap) {
-        set_err("aisx_rx_pop_messages: need a handle, outputs for the block number and the counts, buffers for their "
-                "capacities and a table of rec_cap rows (col_stride >= rec_cap)");
+    return rx_pop(h, "aisx_rx_pop_messages", "buffers for their capacities and a table of rec_cap rows (col_stride >= rec_cap)",
+                  (rec_cap <= 0 || (cols && strs)) && col_stride >= rec_cap, wait, block, text, text_cap, text_len, recs, rec_cap, nrecs,
+                  rec_cap > 0 ? cols : nullptr, col_stride, strs, status);
+}
+
+// What every aisx_rx_enable_* is: `change` puts the call's wish into a copy of the options (or refuses its arguments
+// with a message), and the tail those ask for is made beside the one in use, which it replaces only when all of it
+// exists.  Until then the handle stays as it was.  `refused`: the call's own rule says no; `rule` words that rule.
+template <class Change>
+static int rx_reconfigure(aisx_rx* h, const char* who, bool refused, const char* rule, Change change)
+{
+    if (!h) {
+        set_err("%s: need a handle", who);
         return AISX_ERR_INVALID;
     }
-    return rx_pop(h, "aisx_rx_pop_messages", wait, block, text, text_cap, text_len, recs, rec_cap, nrecs, rec_cap > 0 ? cols : nullptr,
-                  col_stride, strs, status);
+    if (h->failed != AISX_OK)
+        return rx_failed(h, who);
+    if (refused || h->acquired || h->submitted > 0) {
+        set_err("%s: %sonly before the first acquire, submit or push", who, rule);
+        return AISX_ERR_INVALID;
+    }
+    RxOptions opt = h->opt;
+    int rc = change(opt);
+    if (rc != AISX_OK)
+        return rc;
+    OnDevice on(h->dev);
+    AISX_HIPCHK(on.err);
+    RxTail tail;
+    if ((rc = rx_make_tail(h, opt, who, &tail)) != AISX_OK) { // (what is released on the way out must not replace the message)
+        const std::string msg = aisx_last_error();
+        tail = RxTail();
+        set_err("%s", msg.c_str());
+        return rc;
+    }
+    h->tail = std::move(tail);
+    h->opt = std::move(opt);
+    return AISX_OK;
+}
+
+extern "C" int aisx_rx_enable_messages(aisx_rx* h)
+{
+    if (h && h->failed == AISX_OK && h->opt.messages)
+        return AISX_OK;
+    return rx_reconfigure(h, "aisx_rx_enable_messages", false, "", [](RxOptions& o) {
+        o.messages = true;
+        return AISX_OK;
+    });
 }
 
 extern "C" int aisx_rx_enable_standard_nmea(aisx_rx* h, const char* const* stations, int64_t t0)
 {
-    if (!h) {
-        set_err("aisx_rx_enable_standard_nmea: need a handle");
-        return AISX_ERR_INVALID;
-    }
-    if (h->failed != AISX_OK)
-        return rx_failed(h, "aisx_rx_enable_standard_nmea");
-    if (h->std_nmea || h->acquired || h->submitted > 0) {
-        set_err("aisx_rx_enable_standard_nmea: once, and only before the first acquire, submit or push");
-        return AISX_ERR_INVALID;
-    }
-    if (t0 < 0)
-        t0 = -1;
-    if (const int s = nms_bad_station(stations, h->ns); s >= 0 || !nms_time_ok(t0)) {
-        set_err("aisx_rx_enable_standard_nmea: stations of 0..%d bytes of A-Z a-z 0-9 _ - (station %d is none) and t0 < 10^18", NMS_STATION, s);
-        return AISX_ERR_INVALID;
-    }
-    OnDevice on(h->dev);
-    AISX_HIPCHK(on.err);
-    const int rows = h->ns * h->nch;
-    std::vector<const char*> des((size_t)rows), sta((size_t)rows);
-    int max_slen = 0;
-    for (int r = 0; r < rows; r++) {
-        des[r] = h->des[r % h->nch].c_str();
-        sta[r] = stations ? stations[r / h->nch] : "";
-        max_slen = (int)strlen(sta[r]) > max_slen ? (int)strlen(sta[r]) : max_slen;
-    }
-    // the text grows: nothing is in flight yet, so the result slots are simply made again, what lies behind the text
-    // (the message table, the repair marks) moved up by a multiple of 16 bytes
-    const long long text_cap = (long long)h->max_pdus * (nms_text_len(RX_LMAX - 1, h->max_dlen, nms_tag_len(max_slen, NMS_TIME_DIGITS)) + 1);
-    const size_t grow = ((size_t)(text_cap - h->text_cap) + 15) & ~(size_t)15;
-    PinnedBuf<char> slots[RX_NRES];
-    aisx_nmea_batch* made = nullptr;
-    int rc = aisx_nmea_batch_create_std(&made, des.data(), sta.data(), rows, h->max_pdus, RX_LMAX, (long)text_cap);
-    HandlePtr<aisx_nmea_batch, aisx_nmea_batch_destroy> nm(made);
-    for (int i = 0; rc == AISX_OK && i < RX_NRES; i++)
-        if ((rc = slots[i].alloc(h->res_bytes + grow)) != AISX_OK)
-            set_err("aisx_rx_enable_standard_nmea: %zu bytes of pinned memory for result slot %d could not be had", h->res_bytes + grow, i);
-    const aisx_pdu* d_recs = nullptr;
-    const char* d_text = nullptr;
-    const int* d_count = nullptr;
-    if (rc == AISX_OK)
-        rc = aisx_nmea_batch_results_device(nm.get(), &d_recs, &d_text, &d_count);
-    if (rc != AISX_OK) { // (the handle stays as it was; what is released on the way out must not replace the message)
-        const std::string msg = aisx_last_error();
-        nm.reset();
-        set_err("%s", msg.c_str());
-        return rc;
-    }
-    for (int i = 0; i < RX_NRES; i++)
-        h->h_res[i] = std::move(slots[i]);
-    if (h->mg)
-        h->msg_off += grow;
-    if (h->d_fix)
-        h->fix_off += grow;
-    h->res_bytes += grow;
-    h->text_cap = text_cap;
-    (void)aisx_nmea_batch_destroy(h->nm);
-    h->nm = nm.release();
-    h->d_nm_recs = d_recs;
-    h->d_nm_text = d_text;
-    h->d_nm_count = d_count;
-    h->std_nmea = true;
-    h->t0 = t0;
-    return AISX_OK;
+    return rx_reconfigure(h, "aisx_rx_enable_standard_nmea", h && h->opt.std_nmea, "once, and ", [&](RxOptions& o) {
+        o.t0 = t0 < 0 ? -1 : t0;
+        if (const int s = nms_bad_station(stations, h->ns); s >= 0 || !nms_time_ok(o.t0)) {
+            set_err("aisx_rx_enable_standard_nmea: stations of 0..%d bytes of A-Z a-z 0-9 _ - (station %d is none) and t0 < 10^18", NMS_STATION, s);
+            return AISX_ERR_INVALID;
+        }
+        o.std_nmea = true;
+        o.stations.assign((size_t)h->ns, std::string());
+        for (int s = 0; stations && s < h->ns; s++)
+            o.stations[s] = stations[s];
+        return AISX_OK;
+    });
 }
 
 extern "C" int aisx_rx_enable_repair(aisx_rx* h, const aisx_hdlc_rule* rules, int nrules)
@@ -721,113 +755,35 @@ extern "C" int aisx_rx_enable_repair(aisx_rx* h, const aisx_hdlc_rule* rules, in
 
 extern "C" int aisx_rx_enable_repair_events(aisx_rx* h, const aisx_hdlc_rule* rules, int nrules, int events)
 {
-    if (!h) {
-        set_err("aisx_rx_enable_repair: need a handle");
-        return AISX_ERR_INVALID;
-    }
-    if (h->failed != AISX_OK)
-        return rx_failed(h, "aisx_rx_enable_repair");
-    if (h->acquired || h->submitted > 0 || nrules < 1) {
-        set_err("aisx_rx_enable_repair: at least one rule, and only before the first acquire, submit or push");
-        return AISX_ERR_INVALID;
-    }
-    OnDevice on(h->dev);
-    AISX_HIPCHK(on.err);
-    // the result slots grow by the marks: nothing is in flight yet, so they are simply made again
-    const bool first = h->d_fix == nullptr;
-    const size_t fix_off = first ? (h->res_bytes + 15) & ~(size_t)15 : h->fix_off;
-    const size_t bytes = first ? fix_off + sizeof(int32_t) * (size_t)h->max_pdus : h->res_bytes;
-    PinnedBuf<char> slots[RX_NRES];
-    int rc = AISX_OK;
-    for (int i = 0; first && rc == AISX_OK && i < RX_NRES; i++)
-        if ((rc = slots[i].alloc(bytes)) != AISX_OK)
-            set_err("aisx_rx_enable_repair: %zu bytes of pinned memory for result slot %d could not be had", bytes, i);
-    const int32_t* d_fix = nullptr;
-    if (rc != AISX_OK || (rc = aisx_hdlc_batch_set_repair_events(h->hd, rules, nrules, events)) != AISX_OK ||
-        (rc = aisx_hdlc_batch_repairs_device(h->hd, &d_fix)) != AISX_OK)
-        return rc; // (the handle stays as it was)
-    if (first) {
-        for (int i = 0; i < RX_NRES; i++)
-            h->h_res[i] = std::move(slots[i]);
-        h->fix_off = fix_off;
-        h->res_bytes = bytes;
-    }
-    h->d_fix = d_fix;
-    h->rules.assign(rules, rules + nrules);
-    h->events = events;
-    return AISX_OK;
+    return rx_reconfigure(h, "aisx_rx_enable_repair", nrules < 1 || !rules, "at least one rule, and ", [&](RxOptions& o) {
+        // (at most one rule more than a deframer takes: it is the deframer that judges rules and mask)
+        o.rules.assign(rules, rules + std::min(nrules, AISX_HDLC_MAX_RULES + 1));
+        o.events = events;
+        return AISX_OK;
+    });
 }
 
 extern "C" int aisx_rx_enable_mlse(aisx_rx* h, double bt)
 {
-    if (!h) {
-        set_err("aisx_rx_enable_mlse: need a handle");
-        return AISX_ERR_INVALID;
-    }
-    if (h->failed != AISX_OK)
-        return rx_failed(h, "aisx_rx_enable_mlse");
-    if (h->ml || h->acquired || h->submitted > 0) {
-        set_err("aisx_rx_enable_mlse: once, and only before the first acquire, submit or push");
-        return AISX_ERR_INVALID;
-    }
-    OnDevice on(h->dev);
-    AISX_HIPCHK(on.err);
-    const int rows = h->ns * h->nch, mstride = h->cap + MLSE_EXTRA;
-    // everything is made beside what the handle has, and put in its place only when all of it exists
-    aisx_mlse_batch* made_ml = nullptr;
-    int rc = aisx_mlse_batch_create(&made_ml, bt, rows, h->cap);
-    HandlePtr<aisx_mlse_batch, aisx_mlse_batch_destroy> ml(made_ml);
-    aisx_hdlc_batch* made_hd = nullptr; // a deframer for the detector's calls: a step's symbols and the carried ones
-    if (rc == AISX_OK)
-        rc = aisx_hdlc_batch_create(&made_hd, RX_LMIN, RX_LMAX, rows, mstride, h->max_pdus);
-    HandlePtr<aisx_hdlc_batch, aisx_hdlc_batch_destroy> hd(made_hd);
-    if (rc == AISX_OK && !h->rules.empty())
-        rc = aisx_hdlc_batch_set_repair_events(hd.get(), h->rules.data(), (int)h->rules.size(), h->events);
-    DevBuf<cf> syms[RX_NOUT];
-    DevBuf<uint8_t> mbits;
-    DevBuf<int> mnb;
-    for (int i = 0; rc == AISX_OK && i < RX_NOUT; i++)
-        rc = syms[i].alloc((size_t)rows * h->cap, false);
-    if (rc == AISX_OK && (rc = mbits.alloc((size_t)rows * mstride, false)) == AISX_OK)
-        rc = mnb.alloc((size_t)rows);
-    const aisx_pdu* pdus = nullptr;
-    const uint8_t* bytes = nullptr;
-    const int *count = nullptr, *flag = nullptr;
-    const int32_t* d_fix = nullptr;
-    if (rc == AISX_OK && (rc = aisx_hdlc_batch_results_device(hd.get(), &pdus, &bytes, &count)) == AISX_OK &&
-        (rc = aisx_mlse_batch_status_device(ml.get(), &flag)) == AISX_OK && h->d_fix)
-        rc = aisx_hdlc_batch_repairs_device(hd.get(), &d_fix);
-    if (rc == AISX_OK && hipDeviceSynchronize() != hipSuccess) { // (the zero fills ran on the null stream)
-        set_err("aisx_rx_enable_mlse: hipDeviceSynchronize failed");
-        rc = AISX_ERR_HIP;
-    }
-    if (rc != AISX_OK) { // (the handle stays as it was; what is released on the way out must not replace the message)
-        const std::string msg = aisx_last_error();
-        hd.reset();
-        ml.reset();
-        set_err("%s", msg.c_str());
-        return rc;
-    }
-    (void)aisx_hdlc_batch_destroy(h->hd);
-    h->hd = hd.release();
-    h->d_hd_pdus = pdus;
-    h->d_hd_bytes = bytes;
-    h->d_hd_count = count;
-    if (h->d_fix)
-        h->d_fix = d_fix;
-    for (int i = 0; i < RX_NOUT; i++)
-        h->d_syms[i] = std::move(syms[i]);
-    h->d_mbits = std::move(mbits);
-    h->d_mnb = std::move(mnb);
-    h->mstride = mstride;
-    h->d_ml_flag = flag;
-    h->ml = ml.release();
-    return AISX_OK;
+    return rx_reconfigure(h, "aisx_rx_enable_mlse", h && h->opt.detector, "once, and ", [&](RxOptions& o) {
+        o.detector = true;
+        o.bt = bt;
+        return AISX_OK;
+    });
+}
+
+extern "C" int aisx_rx_enable_tracks(aisx_rx* h, int capacity)
+{
+    return rx_reconfigure(h, "aisx_rx_enable_tracks", h && h->opt.tracks, "once, and ", [&](RxOptions& o) {
+        o.tracks = o.messages = true;
+        o.capacity = capacity;
+        return AISX_OK;
+    });
 }
 
 extern "C" int aisx_rx_popped_repairs(aisx_rx* h, int32_t* fix_bits, int cap, int* n)
 {
-    if (!h || !h->d_fix || !n || cap < 0 || (cap > 0 && !fix_bits)) {
+    if (!h || !h->tail.d_fix || !n || cap < 0 || (cap > 0 && !fix_bits)) {
         set_err("aisx_rx_popped_repairs: need a handle on which aisx_rx_enable_repair was called, a count and a buffer for its capacity");
         return AISX_ERR_INVALID;
     }
@@ -842,39 +798,10 @@ extern "C" int aisx_rx_popped_repairs(aisx_rx* h, int32_t* fix_bits, int cap, in
     return AISX_OK;
 }
 
-extern "C" int aisx_rx_enable_tracks(aisx_rx* h, int capacity)
-{
-    if (!h) {
-        set_err("aisx_rx_enable_tracks: need a handle");
-        return AISX_ERR_INVALID;
-    }
-    if (h->failed != AISX_OK)
-        return rx_failed(h, "aisx_rx_enable_tracks");
-    if (h->tk || h->acquired || h->submitted > 0) {
-        set_err("aisx_rx_enable_tracks: once, and only before the first acquire, submit or push");
-        return AISX_ERR_INVALID;
-    }
-    OnDevice on(h->dev);
-    AISX_HIPCHK(on.err);
-    aisx_track_batch* made = nullptr;
-    int rc = aisx_track_batch_create(&made, capacity, h->max_pdus);
-    HandlePtr<aisx_track_batch, aisx_track_batch_destroy> tk(made);
-    if (rc == AISX_OK)
-        rc = aisx_rx_enable_messages(h);
-    if (rc != AISX_OK) { // (the handle stays as it was)
-        const std::string msg = aisx_last_error();
-        tk.reset();
-        set_err("%s", msg.c_str());
-        return rc;
-    }
-    h->tk = tk.release();
-    return AISX_OK;
-}
-
 // the two reads of the table, on the tail stream: behind the update of every block issued so far
 static int rx_tracks_ready(aisx_rx* h, const char* who, long long* block)
 {
-    if (!h || !h->tk) {
+    if (!h || !h->tail.tk) {
         set_err("%s: need a handle on which aisx_rx_enable_tracks was called", who);
         return AISX_ERR_INVALID;
     }
@@ -889,14 +816,14 @@ extern "C" int aisx_rx_read_tracks(aisx_rx* h, int first, int n, int32_t* cols, 
                                    long long* block)
 {
     const int rc = rx_tracks_ready(h, "aisx_rx_read_tracks", block);
-    return rc != AISX_OK ? rc : aisx_track_batch_read(h->tk, first, n, cols, col_stride, strs, nvessels, (hipStream_t)h->s_tail);
+    return rc != AISX_OK ? rc : aisx_track_batch_read(h->tail.tk.get(), first, n, cols, col_stride, strs, nvessels, (hipStream_t)h->s_tail);
 }
 
 extern "C" int aisx_rx_read_changed_tracks(aisx_rx* h, int* idx, int32_t* cols, long col_stride, char* strs, int cap, int* nchanged,
                                            long long* block)
 {
     const int rc = rx_tracks_ready(h, "aisx_rx_read_changed_tracks", block);
-    return rc != AISX_OK ? rc : aisx_track_batch_read_changed(h->tk, idx, cols, col_stride, strs, cap, nchanged, (hipStream_t)h->s_tail);
+    return rc != AISX_OK ? rc : aisx_track_batch_read_changed(h->tail.tk.get(), idx, cols, col_stride, strs, cap, nchanged, (hipStream_t)h->s_tail);
 }
 
 extern "C" int aisx_rx_set_center_freq(aisx_rx* h, int stream, int chan, double center_freq)

@@ -1025,17 +1025,21 @@ int aisx_rx_flush(aisx_rx* h);
  * buffers are too small: AISX_ERR_OVERFLOW with *nrecs / *text_len = what is needed, and the block stays. */
 int aisx_rx_pop(aisx_rx* h, int wait, long long* block, char* text, long text_cap, long* text_len, aisx_pdu* recs,
                 int rec_cap, int* nrecs, int* status);
+/* The aisx_rx_enable_* calls below are the handle's options.  They may come in any order: the handle that results is the
+ * same.  A call that returns an error leaves the handle as it was, options set earlier included. */
 /* Opt-in: from the first block on, the tail stream queues the field decoder (aisx_msg_batch_*) behind the NMEA stage
  * and every result slot also carries the kept records' table.  Only before the first acquire, submit or push
- * (AISX_ERR_INVALID afterwards); a handle on which this was never called allocates, queues and copies nothing more. */
+ * (AISX_ERR_INVALID afterwards) -- but on a handle that has messages enabled the call returns AISX_OK at any time and
+ * does nothing.  A handle on which this was never called allocates, queues and copies nothing more. */
 int aisx_rx_enable_messages(aisx_rx* h);
 /* aisx_rx_pop plus the block's table: cols [AISX_MSG_NCOL][col_stride] (col_stride >= rec_cap), strs
  * [rec_cap][AISX_MSG_STR], row i for record i.  The same waiting and overflow rules (the table needs rec_cap rows).
  * AISX_ERR_INVALID on a handle without messages enabled. */
 int aisx_rx_pop_messages(aisx_rx* h, int wait, long long* block, char* text, long text_cap, long* text_len, aisx_pdu* recs,
                          int rec_cap, int* nrecs, int32_t* cols, long col_stride, char* strs, int* status);
-/* Opt-in: aisx_hdlc_batch_set_repair on the handle's deframer, and every result slot also carries the block's marks.
- * Only before the first acquire, submit or push (AISX_ERR_INVALID afterwards, and for bad rules or none); a handle on
+/* Opt-in: the handle's deframer repairs by these rules as aisx_hdlc_batch_set_repair describes, and every result slot
+ * also carries the block's marks.  Only before the first acquire, submit or push (AISX_ERR_INVALID afterwards, and for
+ * bad rules or none); until then it may be called again, and the rules (and events) of the last call hold.  A handle on
  * which this was never called allocates, queues and copies nothing more.  The same as aisx_rx_enable_repair_events
  * with AISX_HDLC_EV_SINGLE. */
 int aisx_rx_enable_repair(aisx_rx* h, const aisx_hdlc_rule* rules, int nrules);
@@ -1064,8 +1068,9 @@ int aisx_rx_read_changed_tracks(aisx_rx* h, int* idx, int32_t* cols, long col_st
 /* Opt-in: the bits the deframer reads are decided by the 4-state sequence detector (aisx_mlse_batch_*, below) of BT = bt
  * GMSK instead of the one-symbol slicer.  From the first block on every chain step also writes its symbols (one of
  * AISX_CHAIN_DEPTH buffers of the handle's), and the tail stream queues the detector between the step and the deframer,
- * which is made again for the detector's longer calls (max_bits + 79; rules and events set by aisx_rx_enable_repair / _events are kept).
- * Deframer, repair, NMEA, decoder and vessel table work as before behind it, and a record's end_bit counts the same
+ * which takes the detector's longer calls (max_bits + 79).  Deframer, repair (the rules and events of
+ * aisx_rx_enable_repair / _events, set before or after this call), NMEA, decoder and vessel table work behind it as they do
+ * without it, and a record's end_bit counts the same
  * bits: bit n belongs to symbol n.  The detector decides a symbol once 80 to 143 later ones have arrived, so the last
  * 16 to 79 symbols of a channel stay undecided until more input follows; aisx_rx_flush does not flush the detector
  * (input may follow), and a burst that ends within them appears with the next block.  Only before the first

@@ -14,14 +14,14 @@ import numpy as np
 import pytest
 
 import nmea_cases as nc
+from rx_scene import BLOCK, DES, FS, NBLOCKS
+from rx_scene import make_rx as _rx
+from rx_scene import run as _run
 
 pytestmark = pytest.mark.gpu
 
-FS, DECIM, ITEMS, NBLOCKS = 250e3, 5, 4096, 3
-BLOCK = ITEMS * DECIM
 T0 = 1700000000
 STATIONS = ["rx-North_1", ""]
-DES = ("A", "B")
 
 
 @pytest.fixture(scope="module")
@@ -34,58 +34,12 @@ def ais():
     return ais_amd
 
 
-def _payload(rng, n):
-    """n random octets under the message type that has this length: 1 (21 octets), 24 part A (20), 5 (53)"""
-    p = bytearray(rng.integers(0, 256, n, dtype=np.uint8).tobytes())
-    p[0] = ({21: 1, 20: 24, 53: 5}[n] << 2) | (p[0] & 3)
-    if n == 20:
-        p[4] &= 0xFC  # (bits 38, 39: part number 0)
-    return bytes(p)
-
-
 @pytest.fixture(scope="module")
 def scene(ais):
     """raw cs16 blocks [2][NBLOCKS * BLOCK][2] and the payloads per lane (= stream * 2 + centre)"""
-    import synth
+    import rx_scene
 
-    rng = np.random.default_rng(61)
-    sps, T = FS / 9600.0, NBLOCKS * BLOCK
-    pay, chan, start, cfo, lanes = [], [], [], [], {}
-    for lane in range(4):
-        for n, s0 in ((21, 1500), (20, 10000), (53, 19000), (53, 34000), (21, 49000)):
-            p = _payload(rng, n)
-            pay.append(p)
-            chan.append(lane // 2)
-            start.append(s0 + 137 * lane)
-            cfo.append(((-25e3, 25e3)[lane % 2] + float(rng.uniform(-300, 300))) / FS)
-            lanes.setdefault(lane, []).append(p)
-    x = ais.gmsk_scene(pay, np.array(chan, np.int32), np.array(start, np.int64), sps, 2, 0, T, frac=rng.random(len(pay)).astype(np.float32) * 0.99,
-                       cfo=np.array(cfo, np.float32), phase=rng.uniform(-3, 3, len(pay)).astype(np.float32))
-    sigma = float(np.sqrt(sps / 100.0 / 2.0))  # 20 dB in the channel's bandwidth, as test_gpu_tx.py's loop-back
-    x = x + (rng.normal(0, sigma, x.shape) + 1j * rng.normal(0, sigma, x.shape)).astype(np.complex64)
-    raw = np.rint(np.stack([x.real, x.imag], axis=-1) * 2.0 ** 13).astype(np.int16)
-    tmpl = synth.resampled_template(synth.gmsk_waveform(np.array([1 if b else -1 for b in synth.sync_bits("P")], float), 40)[: 28 * 40],
-                                    40, FS / DECIM / 9600.0)
-    return dict(raw=raw, lanes=lanes, tmpl=tmpl)
-
-
-def _rx(ais, scene, **kw):
-    return ais.ais_rx((-25e3, 25e3), FS, DES, nstreams=2, fmt="cs16", scale=2.0 ** -13, block_items=BLOCK,
-                      preamble_symbols=scene["tmpl"], max_pdus_per_block=256, **kw)
-
-
-def _run(rx, scene, messages=False):
-    """every block pushed, flushed, popped: [(block, recs, text[, messages])]; the status words are kept in rx.statuses"""
-    out, rx.statuses = [], []
-    pop = rx.pop_messages if messages else rx.pop
-    for k in range(NBLOCKS):
-        assert rx.push(scene["raw"][:, k * BLOCK:(k + 1) * BLOCK]) == k
-    rx.flush()
-    while (r := pop(wait=True)) is not None:
-        rx.statuses.append(rx.status)
-        out.append(r)
-    assert [r[0] for r in out] == list(range(NBLOCKS))
-    return out
+    return rx_scene.build(ais)
 
 
 @pytest.fixture(scope="module")
