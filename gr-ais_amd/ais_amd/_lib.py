@@ -280,6 +280,19 @@ def lib(device=True):
     sig("aisx_rx_enable_tracks", i32, [vp, i32])
     sig("aisx_rx_read_tracks", i32, [vp, i32, i32, vp, lng, vp, pi32, pll])
     sig("aisx_rx_read_changed_tracks", i32, [vp, vp, vp, lng, vp, i32, pi32, pll])
+    sig("aisx_dedup_key", i32, [vp, i32, C.POINTER(u64)])
+    sig("aisx_dedup_create", i32, [pvp, i32, i32])
+    sig("aisx_dedup_destroy", i32, [vp])
+    sig("aisx_dedup_reset", i32, [vp])
+    sig("aisx_dedup_update", i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp])
+    sig("aisx_dedup_batch_create", i32, [pvp, i32, i32, i32])
+    sig("aisx_dedup_batch_destroy", i32, [vp])
+    sig("aisx_dedup_batch_reset", i32, [vp])
+    sig("aisx_dedup_batch_process", i32, [vp, vp, vp, vp, vp, vp, i32, vp])
+    sig("aisx_dedup_batch_results_device", i32, [vp, pvp, pvp, pvp, pvp, pvp, pvp])
+    sig("aisx_dedup_batch_read", i32, [vp, vp, vp, vp, i32, vp, i32, vp, pi32, vp])
+    sig("aisx_rx_enable_dedup", i32, [vp, i32])
+    sig("aisx_rx_popped_dedup", i32, [vp, vp])
     i64 = C.c_int64
     sig("aisx_hdlc_frame", i32, [vp, i32, i32, i32, i32, vp, i32, pi32])
     sig("aisx_tx_render_host", i32, [f64, f64, i32, i32, i32, i32, vp, i32, vp, i64, i64, i64, vp, i64, i32])

@@ -840,3 +840,112 @@ class vessel_table_batch:
         TRACK_CHANGED_DTYPE array (field "vessel" = the index)"""
         idx, cols, strs = self.changed_arrays(cap, stream)
         return _track_table(cols, strs, len(idx), idx)
+
+
+class pdu_dedup_batch:
+    """ais_amd.pdu_dedup in device memory (aisx_dedup_batch_*): the same kept records, first, copies, marks and counts,
+    bit for bit, for at most max_pdus records per call, by kernels queued between a producer of a PDU list (the deframer,
+    nmea_to_pdu_batch) and the stages behind it.  results_device() gives (pdus, bytes, count) as the deframer's does, so
+    those stages take this handle in the deframer's place:
+
+        dd = ais_amd.pdu_dedup_batch(window=2, max_pdus=max_pdus, length_max=64)
+        hd.work(r["bits"], r["produced"], stream=s)      # deframe step k on s
+        dd.work(hd, stamp=k, stream=s)                   # keep one copy of every payload
+        nm.work(dd, stream=s)                            # text of the kept records only
+        md.work(dd, stream=s)
+        vt.work(md, k, stream=s, deframer=dd)            # COUNT counts transmissions, not receptions
+
+    The handle holds window + 1 sets of remembered keys of 2 * max_pdus slots or more (8 bytes each)."""
+
+    def __init__(self, window, max_pdus, length_max=64):
+        h = C.c_void_p()
+        check(_lib.lib().aisx_dedup_batch_create(C.byref(h), int(window), int(max_pdus), int(length_max)), "pdu_dedup_batch")
+        self._h = h
+        self.window, self.max_pdus, self.length_max = int(window), int(max_pdus), int(length_max)
+        self.found = 0  # the last read's d_count[0]: records kept + what the producer found beyond what it handed over
+        self.counts = None
+        self._keep = None  # what the last call reads, kept alive until the next
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            _lib.lib().aisx_dedup_batch_destroy(h)
+            self._h = None
+
+    def reset(self):
+        check(_lib.lib().aisx_dedup_batch_reset(self._h), "pdu_dedup_batch.reset")
+
+    def work(self, producer, stamp, stream=None, marks=None):
+        """Takes the PDUs of the producer's last call -- anything with the deframer's results_device() -- queued on
+        `stream` (default the current one; nothing waits): records count + 1, PDUs found count + 0.  marks: an int32
+        device tensor with one entry per record, or a device address (hdlc_deframer_batch.repairs_device()), carried
+        along to the kept records.  IndexError when stamp is not above the previous call's (nothing is queued)."""
+        p, b, n = producer.results_device()
+        self._keep = (producer, marks)
+        if marks is not None and not isinstance(marks, int):
+            if marks.dtype != torch.int32 or not marks.is_cuda or not marks.is_contiguous():
+                raise ValueError("pdu_dedup_batch.work: marks must be a contiguous int32 device tensor or a device address")
+            marks = marks.data_ptr()
+        self.work_device(p, b, n + 4, n, stamp, marks, stream)
+
+    def work_device(self, pdus_ptr, bytes_ptr, npdus_ptr, nfound_ptr, stamp, marks_ptr=None, stream=None):
+        """Device addresses: records in the aisx_pdu layout, their payload bytes, ONE int = records, optionally ONE int =
+        PDUs the producer found and optionally int32 marks.  Queued on `stream`; the counts are read on the device."""
+        check(_lib.lib().aisx_dedup_batch_process(self._h, C.c_void_p(pdus_ptr), C.c_void_p(bytes_ptr), C.c_void_p(npdus_ptr),
+                                                  C.c_void_p(nfound_ptr) if nfound_ptr else None,
+                                                  C.c_void_p(marks_ptr) if marks_ptr else None, int(stamp), _stream_ptr(stream)),
+              "pdu_dedup_batch.work")
+
+    def _results(self):
+        v = [C.c_void_p() for _ in range(6)]
+        check(_lib.lib().aisx_dedup_batch_results_device(self._h, *[C.byref(x) for x in v]), "pdu_dedup_batch.results_device")
+        return tuple(x.value for x in v)
+
+    def results_device(self):
+        """device addresses of the last call's kept records (aisx_pdu [max_pdus]), the producer's bytes and the counts
+        (int [8]: found, kept, bad-count flag, then DEDUP_COUNTS), as hdlc_deframer_batch.results_device()"""
+        return self._results()[:3]
+
+    def extras_device(self):
+        """device addresses of first, copies and the kept records' marks (int32 [max_pdus] each)"""
+        return self._results()[3:]
+
+    def _read(self, stream, overflow_ok):
+        from .framing import DEDUP_COUNTS
+
+        recs = np.zeros(self.max_pdus, dtype=PDU_DTYPE)
+        copies, marks, first = (np.zeros(self.max_pdus, dtype=np.int32) for _ in range(3))
+        cnt = np.zeros(len(DEDUP_COUNTS), dtype=np.int32)
+        f = C.c_int(0)
+        rc = _lib.lib().aisx_dedup_batch_read(self._h, recs.ctypes.data_as(C.c_void_p), copies.ctypes.data_as(C.c_void_p),
+                                              marks.ctypes.data_as(C.c_void_p), self.max_pdus, first.ctypes.data_as(C.c_void_p),
+                                              self.max_pdus, cnt.ctypes.data_as(C.c_void_p), C.byref(f), _stream_ptr(stream))
+        self.found = f.value
+        self.counts = {k: int(v) for k, v in zip(DEDUP_COUNTS, cnt)}
+        if not (rc == _lib.AISX_ERR_OVERFLOW and overflow_ok):
+            check(rc, "pdu_dedup_batch")
+        k, n = self.counts["kept"], self.counts["in"]
+        return recs[:k], first[:n], copies[:k], marks[:k]
+
+    def pdus(self, stream=None, overflow_ok=False):
+        """the last call's kept records, a PDU_DTYPE array whose offsets point into the producer's bytes (synchronises
+        `stream`).  OverflowError when the producer found more than it handed over (overflow_ok=True: the records all the
+        same), ValueError when a call since the last read met a record count outside [0, max_pdus]."""
+        return self._read(stream, overflow_ok)[0]
+
+    def first(self, stream=None, overflow_ok=False):
+        """first[i] of every record of the last call, as pdu_dedup gives it (synchronises `stream`)"""
+        return self._read(stream, overflow_ok)[1]
+
+    def copies(self, stream=None, overflow_ok=False):
+        """copies[j] of every kept record of the last call (synchronises `stream`)"""
+        return self._read(stream, overflow_ok)[2]
+
+    def marks(self, stream=None, overflow_ok=False):
+        """the kept records' marks of the last call, where it was given marks (synchronises `stream`)"""
+        return self._read(stream, overflow_ok)[3]
+
+    def get_counts(self, stream=None):
+        """the last call's counts as a dict of DEDUP_COUNTS (synchronises `stream`)"""
+        self._read(stream, True)
+        return self.counts

@@ -866,13 +866,19 @@ class ais_rx:
     every stream or nstreams str, the s: field of every sentence of that stream; t0: the second of block 0's first
     item, block b's sentences carry c: t0 + floor(b * block_items / rate) -- or no time for t0 < 0.
 
+    dedup=window (0..15) puts the duplicate suppression (ais_amd.pdu_dedup_batch) between the deframer and the NMEA stage,
+    with stamp = the block's number: of the PDUs of a block that carry one payload -- one transmission heard on several
+    streams -- the first is kept, and a payload kept within the last `window` blocks is suppressed.  Records, text,
+    messages and popped_repairs() are those of the kept records, the vessel table counts transmissions, and
+    popped_dedup() gives the stage's counts for the block popped last.
+
     Each of these options is also an enable_*() method for a receiver that has not yet taken a slot or a block; the order
     of the calls does not matter, and one that raises leaves the receiver as it was.
     """
 
     def __init__(self, freq, rate, designator, nstreams=1, fmt="cf32", scale=1.0, bias=0.0, block_items=None,
                  preamble_symbols=None, taps=None, max_pdus_per_block=1 << 16, decode=False, tracks=None, repair=None,
-                 detector=None, bt=0.4, repair_events=1, nmea="reference", stations=None, t0=-1):
+                 detector=None, bt=0.4, repair_events=1, nmea="reference", stations=None, t0=-1, dedup=None):
         from .batch_framing import PDU_DTYPE
         from .modulate import gmsk_mod, modulate_vector_bc
 
@@ -935,6 +941,9 @@ class ais_rx:
             self.enable_messages()
         if tracks:
             self.enable_tracks(tracks)
+        self.dedup = None
+        if dedup is not None:
+            self.enable_dedup(dedup)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -1071,6 +1080,21 @@ class ais_rx:
         check(_lib.lib().aisx_rx_popped_repairs(self._h, fix.ctypes.data_as(C.c_void_p), fix.size, C.byref(n)),
               "ais_rx.popped_repairs")
         return fix[: n.value].copy()
+
+    def enable_dedup(self, window):
+        """what dedup=window does.  ValueError the second time, once a slot has been taken or a block pushed, and for a
+        window outside [0, 15]."""
+        check(_lib.lib().aisx_rx_enable_dedup(self._h, int(window)), "ais_rx.enable_dedup")
+        self.dedup = int(window)
+
+    def popped_dedup(self):
+        """the duplicate suppression's counts for the block popped last, a dict of ais_amd.DEDUP_COUNTS (in, kept,
+        dup_call, dup_window, bad_len).  Needs dedup= (ValueError otherwise)."""
+        from .framing import DEDUP_COUNTS
+
+        cnt = np.zeros(len(DEDUP_COUNTS), dtype=np.int32)
+        check(_lib.lib().aisx_rx_popped_dedup(self._h, cnt.ctypes.data_as(C.c_void_p)), "ais_rx.popped_dedup")
+        return {k: int(v) for k, v in zip(DEDUP_COUNTS, cnt)}
 
     def enable_tracks(self, capacity):
         """what tracks=capacity does: enable_messages(), and from the first block on the vessel table is updated

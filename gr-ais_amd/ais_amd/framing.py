@@ -265,6 +265,81 @@ class nmea_to_pdu:
         return recs, data[:nb].copy(), times[:k].copy(), {n: int(v) for n, v in zip(_lib.AISX_NMEAP_NAMES, cnt)}
 
 
+# what a duplicate suppression's call reports, in the order of include/aisx.h's AISX_DEDUP_CNT_*
+DEDUP_COUNTS = ("in", "kept", "dup_call", "dup_window", "bad_len")
+
+
+def dedup_key(payload):
+    """aisx_dedup_key: the 64-bit key two payloads share when the duplicate suppression takes them for the same"""
+    p = np.frombuffer(bytes(payload), dtype=np.uint8)
+    k = C.c_uint64(0)
+    check(_lib.lib(device=False).aisx_dedup_key(p.ctypes.data_as(C.c_void_p), p.size, C.byref(k)), "dedup_key")
+    return k.value
+
+
+class pdu_dedup:
+    """PDUs heard by several receivers, suppressed on the host (aisx_dedup_*, plain C++: the specification of
+    pdu_dedup_batch, include/aisx.h states the rule): of the records of a call that carry one payload the first is kept
+    and counts the others; a payload kept in one of the last `window` calls (0..15) is suppressed altogether, and a
+    suppressed payload does not renew what is remembered.  A record of more than length_max - 1 octets is passed
+    through.  Stamps must rise from call to call (IndexError otherwise, and nothing changes).
+
+        dd = ais_amd.pdu_dedup(window=2)
+        kept, first, copies = dd.work(payloads, stamp)   # payloads[k] for k in kept: what to deliver
+        dd.counts                                        # {"in", "kept", "dup_call", "dup_window", "bad_len"}
+
+    first[i]: the position in `kept` of the record that stands for payload i, or -1 - age when it was kept `age` calls
+    ago; copies[j]: how many records of this call kept[j] stands for."""
+
+    def __init__(self, window, length_max=64):
+        h = C.c_void_p()
+        check(_lib.lib(device=False).aisx_dedup_create(C.byref(h), int(window), int(length_max)), "pdu_dedup")
+        self._h = h
+        self.window, self.length_max = int(window), int(length_max)
+        self.counts = dict.fromkeys(DEDUP_COUNTS, 0)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            _lib.lib(device=False).aisx_dedup_destroy(h)
+            self._h = None
+
+    def reset(self):
+        check(_lib.lib(device=False).aisx_dedup_reset(self._h), "pdu_dedup.reset")
+
+    def work_records(self, recs, data, stamp, marks=None):
+        """recs: a PDU_DTYPE array whose offset / len point into data (uint8); marks: one int32 per record, carried along.
+        Returns (kept records, first, copies, kept marks or None) and sets self.counts."""
+        r = np.ascontiguousarray(recs, dtype=_PDU_DTYPE)
+        d = np.ascontiguousarray(data, dtype=np.uint8)
+        n = len(r)
+        m = np.ascontiguousarray(marks, dtype=np.int32) if marks is not None else None
+        if m is not None and len(m) < n:
+            raise ValueError("pdu_dedup.work_records: %d marks for %d records" % (len(m), n))
+        out, first = np.zeros(max(n, 1), dtype=_PDU_DTYPE), np.zeros(max(n, 1), dtype=np.int32)
+        copies, om = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+        cnt = np.zeros(len(DEDUP_COUNTS), dtype=np.int32)
+        check(_lib.lib(device=False).aisx_dedup_update(self._h, r.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), n,
+                                                       m.ctypes.data_as(C.c_void_p) if m is not None else None, int(stamp),
+                                                       out.ctypes.data_as(C.c_void_p), first.ctypes.data_as(C.c_void_p),
+                                                       copies.ctypes.data_as(C.c_void_p), om.ctypes.data_as(C.c_void_p),
+                                                       cnt.ctypes.data_as(C.c_void_p)), "pdu_dedup.work")
+        self.counts = {k: int(v) for k, v in zip(DEDUP_COUNTS, cnt)}
+        k = int(cnt[1])
+        return out[:k].copy(), first[:n].copy(), copies[:k].copy(), om[:k].copy() if m is not None else None
+
+    def work(self, payloads, stamp):
+        """payloads: a sequence of bytes.  Returns (kept_indices, first, copies) as int32 arrays and sets self.counts."""
+        payloads = [bytes(p) for p in payloads]
+        recs = np.zeros(len(payloads), dtype=_PDU_DTYPE)
+        recs["len"] = [len(p) for p in payloads]
+        recs["offset"] = np.concatenate([[0], np.cumsum(recs["len"])[:-1]]) if len(payloads) else []
+        recs["end_bit"] = np.arange(len(payloads))  # (carried along: which input record a kept one was)
+        data = np.frombuffer(b"".join(payloads) + b"\0", dtype=np.uint8)
+        out, first, copies, _ = self.work_records(recs, data, stamp)
+        return out["end_bit"].astype(np.int32), first, copies
+
+
 # the columns of a decoded message, in the order of include/aisx.h's AISX_MSG_COL_*
 MSG_COLUMNS = ("TYPE", "REPEAT", "MMSI", "FLAGS", "NAV_STATUS", "ROT", "SOG", "ACCURACY", "LON", "LAT", "COG", "HEADING",
                "SECOND", "MANEUVER", "RAIM", "RADIO", "IMO", "AIS_VERSION", "SHIPTYPE", "TO_BOW", "TO_STERN", "TO_PORT",

@@ -373,6 +373,11 @@ struct DevCtx {
     __device__ __forceinline__ int atomic_add_i32(int* p, int v) const { return atomicAdd(p, v); }
     // k_track.h: the value before; the swap stores `desired` only where *p == expect
     __device__ __forceinline__ int atomic_cas_i32(int* p, int expect, int desired) const { return atomicCAS(p, expect, desired); }
+    // k_dedup.h: the same on a 64-bit key
+    __device__ __forceinline__ unsigned long long atomic_cas_u64(unsigned long long* p, unsigned long long expect, unsigned long long desired) const
+    {
+        return atomicCAS(p, expect, desired);
+    }
     __device__ __forceinline__ int atomic_min_i32(int* p, int v) const { return atomicMin(p, v); }
     __device__ __forceinline__ int atomic_max_i32(int* p, int v) const { return atomicMax(p, v); }
 

@@ -2,13 +2,14 @@
 // for nstreams sources, fed from pinned host memory in the source's own sample format.  Nothing here computes: the
 // handle owns the filter (aisx_xlate), the four stage handles and their chain, the tail behind the chain step (RxTail:
 // the deframer and the NMEA stage and, where the aisx_rx_enable_* calls asked for them, the sequence detector before the
-// deframer, the field decoder behind the NMEA stage and the vessel table behind the decoder), and the rings, streams
-// and events that order them (INTEGRATION.md states the rules; this file is their one home).
+// deframer, the duplicate suppression behind it, the field decoder behind the NMEA stage and the vessel table behind the
+// decoder), and the rings, streams and events that order them (INTEGRATION.md states the rules; this file is their one
+// home).
 //
 //   block b, submitted:   copy stream    pinned slot b % NPIN -> raw buffer b % NRAW      (after filter b - NRAW)
 //                         filter stream  raw buffer -> row buffer b % NROW                (after wait_input(b - NROW))
 //                         chain          step b - 1 with d_in_next = row buffer b % NROW  (after tail b - 1 - DEPTH)
-//                         tail stream    wait(step b - 1), [detector,] deframer, NMEA, status, results -> pinned result slot
+//                         tail stream    wait(step b - 1), [detector,] deframer, [dedup,] NMEA, status, results -> pinned result slot
 //
 // so the copy of block b + 1 runs beside the compute of block b, and the host never waits for the device in submit.
 #include <string.h>
@@ -32,7 +33,8 @@ constexpr int RX_NROW = AISX_CHAIN_DEPTH + 1;  // row buffers (the filter's outp
 constexpr int RX_NOUT = AISX_CHAIN_DEPTH;      // sets of bits / produced (aisx_chain_step: one per step in flight)
 constexpr int RX_NRES = 8;                     // pinned result slots
 constexpr int RX_FFTLEN = 1024, RX_LMIN = 11, RX_LMAX = 64;
-constexpr int RX_META = 8;                     // ints: msk status, deframer count[3], NMEA count[3], spare
+constexpr int RX_META = 16;                    // ints: msk status, deframer count[3], NMEA count[3], spare, the dedup stage's counts
+static_assert(8 + AISX_DEDUP_NCNT <= RX_META && RX_META % 2 == 0, "the counts fit, and the records behind stay 8-byte aligned");
 
 // filter.firdes.low_pass(gain 1, fs, cutoff, transition) with the Hamming window (radio.py:51)
 std::vector<float> low_pass(double fs, double cutoff, double transition)
@@ -60,9 +62,11 @@ std::vector<float> low_pass(double fs, double cutoff, double transition)
 
 // one workgroup: the recovery's status words or-ed over the channels, and the deframer's and the NMEA stage's counts,
 // gathered into one record for the copy back
-// (ml_flag: the detector's bad-count word or nullptr; it counts as the deframer's)
+// (ml_flag: the detector's bad-count word or nullptr; it counts as the deframer's, and so does the flag of dd_count, the
+// duplicate suppression's count words or nullptr)
 __global__ __launch_bounds__(256) void k_rx_meta(const int* __restrict__ msk_status, int nchan, const int* __restrict__ hd_count,
-                                                 const int* __restrict__ nm_count, const int* __restrict__ ml_flag, int* __restrict__ meta)
+                                                 const int* __restrict__ nm_count, const int* __restrict__ ml_flag, const int* __restrict__ dd_count,
+                                                 int* __restrict__ meta)
 {
     __shared__ int acc;
     if (threadIdx.x == 0)
@@ -83,6 +87,10 @@ __global__ __launch_bounds__(256) void k_rx_meta(const int* __restrict__ msk_sta
         if (ml_flag)
             meta[3] |= *ml_flag;
         meta[7] = 0;
+        for (int i = 0; i < AISX_DEDUP_NCNT; i++)
+            meta[8 + i] = dd_count ? dd_count[3 + i] : 0;
+        if (dd_count)
+            meta[3] |= dd_count[2];
     }
 }
 
@@ -98,6 +106,8 @@ struct RxOptions {
     bool std_nmea = false;              // the NMEA stage writes the standard form, with
     std::vector<std::string> stations;  // these stations, one per stream,
     long long t0 = -1;                  // and its tag blocks' time counted from here (-1: none)
+    bool dedup = false;                 // the duplicate suppression between the deframer and the NMEA stage,
+    int window = 0;                     // remembering so many blocks
 };
 
 // a pinned result slot: byte offsets of its areas in this order, the optional ones 16-byte aligned, and its size
@@ -146,10 +156,14 @@ struct RxTail {
     const char* d_nm_text = nullptr;
     const int *d_hd_count = nullptr, *d_nm_count = nullptr, *d_mg_count = nullptr;
     const int32_t* d_fix = nullptr;  // the deframer's marks, only with repair
+    const aisx_pdu* d_ls_pdus = nullptr; // the list NMEA stage, decoder and table read: the deframer's, or the kept records
+    const int* d_ls_count = nullptr;     // of the duplicate suppression, with that list's count words
+    const int32_t* d_ls_fix = nullptr;   // and that list's marks
     const int32_t* d_mg_cols = nullptr;
     const char* d_mg_strs = nullptr;
     HandlePtr<aisx_mlse_batch, aisx_mlse_batch_destroy> ml;
     HandlePtr<aisx_hdlc_batch, aisx_hdlc_batch_destroy> hd;
+    HandlePtr<aisx_dedup_batch, aisx_dedup_batch_destroy> dd;
     HandlePtr<aisx_nmea_batch, aisx_nmea_batch_destroy> nm;
     HandlePtr<aisx_msg_batch, aisx_msg_batch_destroy> mg;
     HandlePtr<aisx_track_batch, aisx_track_batch_destroy> tk;
@@ -171,6 +185,7 @@ struct aisx_rx {
     int max_dlen = 0;
     RxOptions opt;
     std::vector<int32_t> popped_fix;   // the repair marks of the block popped last
+    int popped_dd[AISX_DEDUP_NCNT] = {}; // and the duplicate suppression's counts of that block
     Stream s_copy, s_filt, s_tail;     // (before the buffers and events used on them: destroyed after those)
     PinnedBuf<char> h_in[RX_NPIN];     // pinned [ns][block_items] items
     DevBuf<char> d_raw[RX_NRAW];
@@ -267,6 +282,17 @@ static int rx_make_tail(const aisx_rx* h, const RxOptions& o, const char* who, R
     if (!o.rules.empty() && ((rc = aisx_hdlc_batch_set_repair_events(t->hd.get(), o.rules.data(), (int)o.rules.size(), o.events)) != AISX_OK ||
                              (rc = aisx_hdlc_batch_repairs_device(t->hd.get(), &t->d_fix)) != AISX_OK))
         return rc;
+    t->d_ls_pdus = t->d_hd_pdus;
+    t->d_ls_count = t->d_hd_count;
+    t->d_ls_fix = t->d_fix;
+    if (o.dedup) { // the stages behind read the kept records, their count words and their marks
+        const int32_t* marks = nullptr;
+        if ((rc = rx_make(t->dd, aisx_dedup_batch_create, o.window, h->max_pdus, RX_LMAX)) != AISX_OK ||
+            (rc = aisx_dedup_batch_results_device(t->dd.get(), &t->d_ls_pdus, nullptr, &t->d_ls_count, nullptr, nullptr, &marks)) != AISX_OK)
+            return rc;
+        if (t->d_fix)
+            t->d_ls_fix = marks;
+    }
     const int sentence = o.std_nmea ? nms_text_len(RX_LMAX - 1, h->max_dlen, nms_tag_len(max_slen, NMS_TIME_DIGITS))
                                     : nm_text_len(RX_LMAX - 1, h->max_dlen);
     t->text_cap = (long long)h->max_pdus * (sentence + 1);
@@ -474,23 +500,28 @@ static int rx_issue(aisx_rx* h, long long k, const cf* next)
     } else if ((rc = aisx_hdlc_batch_process(t.hd.get(), h->d_bits[set], h->cap, h->d_prod[set], st)) != AISX_OK)
         return rc;
     AISX_HIPCHK(hipEventRecord(h->ev_tail[set], st));
+    if (t.dd && (rc = aisx_dedup_batch_process(t.dd.get(), t.d_hd_pdus, t.d_hd_bytes, t.d_hd_count + 1, t.d_hd_count, t.d_fix, (int32_t)k, st)) != AISX_OK)
+        return rc;
     if (h->opt.std_nmea && h->opt.t0 >= 0 && // the block's first item's second (a launch parameter of the stage: nothing waits)
         (rc = aisx_nmea_batch_set_time(t.nm.get(), h->opt.t0 + (long long)floor((double)k * h->block_items / h->rate))) != AISX_OK)
         return rc;
-    if ((rc = aisx_nmea_batch_process(t.nm.get(), t.d_hd_pdus, t.d_hd_bytes, t.d_hd_count + 1, t.d_hd_count, st)) != AISX_OK)
+    if ((rc = aisx_nmea_batch_process(t.nm.get(), t.d_ls_pdus, t.d_hd_bytes, t.d_ls_count + 1, t.d_ls_count, st)) != AISX_OK)
         return rc;
-    hipLaunchKernelGGL(k_rx_meta, dim3(1), dim3(256), 0, st, h->d_msk_status, rows, t.d_hd_count, t.d_nm_count, t.d_ml_flag, h->d_meta);
+    hipLaunchKernelGGL(k_rx_meta, dim3(1), dim3(256), 0, st, h->d_msk_status, rows, t.d_hd_count, t.d_nm_count, t.d_ml_flag,
+                       t.dd ? t.d_ls_count : nullptr, h->d_meta);
     AISX_HIPCHK(hipGetLastError());
     // (the bad-input flags are this block's: cleared behind the record that took them)
     AISX_HIPCHK(hipMemsetAsync((void*)(t.d_hd_count + 2), 0, sizeof(int), st));
     AISX_HIPCHK(hipMemsetAsync((void*)(t.d_nm_count + 2), 0, sizeof(int), st));
     if (t.d_ml_flag)
         AISX_HIPCHK(hipMemsetAsync((void*)t.d_ml_flag, 0, sizeof(int), st));
+    if (t.dd)
+        AISX_HIPCHK(hipMemsetAsync((void*)(t.d_ls_count + 2), 0, sizeof(int), st));
     char* r = t.h_res[res];
     if (t.mg) { // the rows of the records the NMEA stage kept; its bad-input flag goes into the record's spare word
-        if ((rc = aisx_msg_batch_process(t.mg.get(), t.d_hd_pdus, t.d_hd_bytes, t.d_nm_count + 1, t.d_hd_count, st)) != AISX_OK)
+        if ((rc = aisx_msg_batch_process(t.mg.get(), t.d_ls_pdus, t.d_hd_bytes, t.d_nm_count + 1, t.d_ls_count, st)) != AISX_OK)
             return rc;
-        if (t.tk && (rc = aisx_track_batch_process(t.tk.get(), t.d_mg_cols, h->max_pdus, t.d_mg_strs, t.d_hd_pdus, t.d_mg_count + 1,
+        if (t.tk && (rc = aisx_track_batch_process(t.tk.get(), t.d_mg_cols, h->max_pdus, t.d_mg_strs, t.d_ls_pdus, t.d_mg_count + 1,
                                                    (int32_t)k, st)) != AISX_OK)
             return rc;
         AISX_HIPCHK(hipMemcpyAsync(h->d_meta + 7, t.d_mg_count + 2, sizeof(int), hipMemcpyDeviceToDevice, st));
@@ -498,8 +529,8 @@ static int rx_issue(aisx_rx* h, long long k, const cf* next)
         AISX_HIPCHK(hipMemcpyAsync(r + lay.cols, t.d_mg_cols, lay.strs - lay.cols, hipMemcpyDeviceToHost, st));
         AISX_HIPCHK(hipMemcpyAsync(r + lay.strs, t.d_mg_strs, (size_t)AISX_MSG_STR * h->max_pdus, hipMemcpyDeviceToHost, st));
     }
-    if (t.d_fix)
-        AISX_HIPCHK(hipMemcpyAsync(r + lay.fix, t.d_fix, sizeof(int32_t) * (size_t)h->max_pdus, hipMemcpyDeviceToHost, st));
+    if (t.d_ls_fix)
+        AISX_HIPCHK(hipMemcpyAsync(r + lay.fix, t.d_ls_fix, sizeof(int32_t) * (size_t)h->max_pdus, hipMemcpyDeviceToHost, st));
     AISX_HIPCHK(hipMemcpyAsync(r, h->d_meta, sizeof(int) * RX_META, hipMemcpyDeviceToHost, st));
     AISX_HIPCHK(hipMemcpyAsync(r + lay.recs, t.d_nm_recs, lay.text - lay.recs, hipMemcpyDeviceToHost, st));
     AISX_HIPCHK(hipMemcpyAsync(r + lay.text, t.d_nm_text, (size_t)t.text_cap, hipMemcpyDeviceToHost, st));
@@ -660,11 +691,12 @@ static int rx_pop(aisx_rx* h, const char* who, const char* need, bool extra_ok, 
             memcpy(cols + (size_t)c * col_stride, cc + (size_t)c * h->max_pdus, sizeof(int32_t) * (size_t)k);
         memcpy(strs, r + lay.strs, (size_t)AISX_MSG_STR * k);
     }
-    if (h->tail.d_fix) // (the NMEA stage's records are the first k of the deframer's)
+    if (h->tail.d_fix) // (the NMEA stage's records are the first k of the list it read: the deframer's, or the kept ones)
         h->popped_fix.assign((const int32_t*)(r + lay.fix), (const int32_t*)(r + lay.fix) + k);
     if (status)
-        *status = meta[0] | (meta[1] > meta[2] ? AISX_RX_ST_HDLC_OVERFLOW : 0) | (meta[5] < meta[2] ? AISX_RX_ST_NMEA_OVERFLOW : 0) |
+        *status = meta[0] | (meta[1] > meta[2] ? AISX_RX_ST_HDLC_OVERFLOW : 0) | (meta[5] < (h->tail.dd ? meta[8 + AISX_DEDUP_CNT_KEPT] : meta[2]) ? AISX_RX_ST_NMEA_OVERFLOW : 0) |
                   ((meta[3] || meta[6] || meta[7]) ? AISX_RX_ST_BAD_COUNT : 0);
+    memcpy(h->popped_dd, meta + 8, sizeof h->popped_dd);
     *block = h->popped++;
     return AISX_OK;
 }
@@ -779,6 +811,25 @@ extern "C" int aisx_rx_enable_tracks(aisx_rx* h, int capacity)
         o.capacity = capacity;
         return AISX_OK;
     });
+}
+
+extern "C" int aisx_rx_enable_dedup(aisx_rx* h, int window)
+{
+    return rx_reconfigure(h, "aisx_rx_enable_dedup", h && h->opt.dedup, "once, and ", [&](RxOptions& o) {
+        o.dedup = true;
+        o.window = window;
+        return AISX_OK;
+    });
+}
+
+extern "C" int aisx_rx_popped_dedup(aisx_rx* h, int* counts)
+{
+    if (!h || !h->tail.dd || !counts) {
+        set_err("aisx_rx_popped_dedup: need a handle on which aisx_rx_enable_dedup was called and somewhere to put the counts");
+        return AISX_ERR_INVALID;
+    }
+    memcpy(counts, h->popped_dd, sizeof h->popped_dd);
+    return AISX_OK;
 }
 
 extern "C" int aisx_rx_popped_repairs(aisx_rx* h, int32_t* fix_bits, int cap, int* n)

@@ -969,6 +969,84 @@ int aisx_track_batch_read_changed(aisx_track_batch* h, int* idx, int32_t* cols, 
                                   int* nchanged, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* PDUs heard by several receivers: keep the first copy of a payload, count   */
+/* the others -- on the host (the specification), and in device memory,       */
+/* queued between a producer of a PDU list and every stage behind it          */
+/* ------------------------------------------------------------------------ */
+/* The key of a payload, 64 bits, computed in arithmetic modulo 2^64:
+ *     h = 0x9E3779B97F4A7C15 ^ ((uint64_t)len * 0xFF51AFD7ED558CCD)
+ *     for k = 0 .. ceil(len / 8) - 1:   w = octets 8 k .. 8 k + 7 as one little-endian word (octets at or beyond len: 0)
+ *                                       h = (h ^ w) * 0x9FB21C651E98DF25;   h ^= h >> 32
+ *     h ^= h >> 29;   h *= 0xBF58476D1CE4E5B9;   h ^= h >> 32;   a result of 0 is replaced by 1
+ * (0 marks a free slot of the device form's hashes and is never a key.)  Every step is one-to-one in h and in w, so two
+ * payloads of one length that differ in octets of exactly one word share a key only where the replacement of 0 merges
+ * them; all other pairs share one with the probability of a 64-bit hash.  Two payloads are "the same" when their keys are equal: the bytes are not compared.
+ * AISX_ERR_INVALID for len < 0 or a missing pointer. */
+int aisx_dedup_key(const uint8_t* pdu, int len, uint64_t* key);
+/* what an update reports: int counts[AISX_DEDUP_NCNT] */
+enum {
+    AISX_DEDUP_CNT_IN = 0,     /* records of the call */
+    AISX_DEDUP_CNT_KEPT,       /* records kept (bad records included) */
+    AISX_DEDUP_CNT_DUP_CALL,   /* suppressed: the key was kept earlier in this call */
+    AISX_DEDUP_CNT_DUP_WINDOW, /* suppressed: the key is remembered from an earlier call inside the window */
+    AISX_DEDUP_CNT_BAD_LEN,    /* records whose len is outside [0, length_max - 1]: kept, not keyed */
+    AISX_DEDUP_NCNT
+};
+/* A handle remembers the keys it kept, each with the stamp of the call that kept it.  Calls carry a stamp that must be
+ * strictly greater than the previous call's (AISX_ERR_OUT_OF_RANGE otherwise: nothing changes, the outputs are not
+ * written); stamps are compared and subtracted in 64 bits, so any int32 values do.  0 <= window <= 15, 2 <= length_max
+ * <= 1024.  An update takes n records (aisx_pdu layout, offsets into `bytes`) in ascending order; for record i:
+ *   - len outside [0, length_max - 1]: kept as the next output record j, not keyed, counted in BAD_LEN;
+ *     first[i] = j, copies[j] = 1;
+ *   - else, its key is remembered from a call with stamp t in [stamp - window, stamp - 1] (there is at most one such
+ *     t): suppressed, first[i] = -1 - (stamp - t), counted in DUP_WINDOW;
+ *   - else, its key was kept earlier in this call as output record j: suppressed, first[i] = j, copies[j] grows by
+ *     one, counted in DUP_CALL;
+ *   - else kept as the next output record j: first[i] = j, copies[j] = 1, and the key is remembered with this stamp.
+ * A suppressed record never refreshes what is remembered: a payload repeated in every call is delivered once every
+ * window + 1 calls.  Outputs: out_pdus [n] the kept records, unchanged and in input order (their offsets still point
+ * into `bytes`); first [n]; copies [n] (the first KEPT entries written); with marks [n] (may be NULL: one int32 per
+ * record, carried along, for instance the deframer's repair marks) out_marks [n] the kept records' marks.  Any output
+ * pointer may be NULL.  Plain C++, no device. */
+typedef struct aisx_dedup aisx_dedup;
+int aisx_dedup_create(aisx_dedup** h, int window, int length_max);
+int aisx_dedup_destroy(aisx_dedup* h);
+int aisx_dedup_reset(aisx_dedup* h); /* nothing remembered, any stamp may follow */
+int aisx_dedup_update(aisx_dedup* h, const aisx_pdu* pdus, const uint8_t* bytes, int n, const int32_t* marks, int32_t stamp,
+                      aisx_pdu* out_pdus, int32_t* first, int32_t* copies, int32_t* out_marks, int* counts);
+
+typedef struct aisx_dedup_batch aisx_dedup_batch;
+/* The same on the device that was current here, for at most max_pdus (<= 2^24) records per call: records, first,
+ * copies, marks and counts equal the host form's, bit for bit, whatever order the device ran the records in.  The
+ * handle owns a ring of window + 1 sets of remembered keys, one per stamp (open addressing, at least 2 * max_pdus slots
+ * of 8 bytes each; the set being reused is cleared at the start of a call, a set whose stamp lies outside the window is
+ * not looked at), a hash of the same size for the call's own keys, and a workspace in proportion to max_pdus. */
+int aisx_dedup_batch_create(aisx_dedup_batch** h, int window, int max_pdus, int length_max);
+int aisx_dedup_batch_destroy(aisx_dedup_batch* h);
+int aisx_dedup_batch_reset(aisx_dedup_batch* h); /* as aisx_dedup_reset; waits for the work queued before */
+/* d_pdus / d_bytes / d_npdus / d_nfound as aisx_nmea_batch_process takes them; d_marks: int32 [records] on the device or
+ * NULL.  Queued on `stream`; no host sync, calls of one handle must be ordered.  The stamp rule is the host form's
+ * (AISX_ERR_OUT_OF_RANGE: nothing queued).  A record count outside [0, max_pdus] keeps nothing, as a call of no
+ * records does, and makes the next read say so. */
+int aisx_dedup_batch_process(aisx_dedup_batch* h, const aisx_pdu* d_pdus, const uint8_t* d_bytes, const int* d_npdus,
+                             const int* d_nfound, const int32_t* d_marks, int32_t stamp, void* stream);
+/* the last call's results in device memory: d_pdus [max_pdus] the kept records; d_bytes the producer's, unchanged;
+ * d_count [3 + AISX_DEDUP_NCNT]: [0] = found = records kept + what the producer found beyond the records it handed
+ * over (so a deframer's overflow still shows downstream), [1] = records kept, [2] != 0 after a bad count, [3 + c] =
+ * count c above; d_first [max_pdus], d_copies [max_pdus], d_marks [max_pdus] (the kept records' marks; not written by
+ * a call without marks).  The first three are what every stage behind the deframer takes. */
+int aisx_dedup_batch_results_device(const aisx_dedup_batch* h, const aisx_pdu** d_pdus, const uint8_t** d_bytes,
+                                    const int** d_count, const int32_t** d_first, const int32_t** d_copies,
+                                    const int32_t** d_marks);
+/* copies the last call's results to the host (synchronises `stream`): the first min(kept, pdu_cap) records, their
+ * copies and marks (either may be NULL), the first min(in, first_cap) entries of first (may be NULL with first_cap 0),
+ * counts [AISX_DEDUP_NCNT]; *nfound (may be NULL) as d_count[0].  AISX_ERR_OVERFLOW when not all kept records or not
+ * all of first were written, or when the producer found more than it handed over; AISX_ERR_INVALID when a call since
+ * the previous read met a bad count (the flag is then cleared). */
+int aisx_dedup_batch_read(aisx_dedup_batch* h, aisx_pdu* pdus, int32_t* copies, int32_t* marks, int pdu_cap, int32_t* first,
+                          int first_cap, int* counts, int* nfound, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* ais_rx (python/radio.py:40-73) as ONE handle, fed from host memory in the  */
 /* source's own sample format: freq_xlating_fir_filter_ccf -> ais_demod ->    */
 /* hdlc_deframer_bp -> pdu_to_nmea for nstreams sources at once               */
@@ -1085,6 +1163,18 @@ int aisx_rx_enable_mlse(aisx_rx* h, double bt);
  * (AISX_ERR_INVALID afterwards, and for a station that is none); a handle on which this was never called runs what it
  * ran before. */
 int aisx_rx_enable_standard_nmea(aisx_rx* h, const char* const* stations, int64_t t0);
+/* Opt-in: the tail stream queues the duplicate suppression (aisx_dedup_batch_*, max_pdus = max_pdus_per_block,
+ * remembering `window` blocks, 0..15) between the deframer and the NMEA stage, with stamp = the block's number (its low
+ * 32 bits) and, with repair enabled, the deframer's marks carried along.  NMEA stage, decoder and vessel table read the
+ * kept records in place of the deframer's: popped records, text, messages and aisx_rx_popped_repairs' marks are those
+ * of the kept records, and the table's COUNT counts transmissions, not receptions.  AISX_RX_ST_NMEA_OVERFLOW then means
+ * fewer records armoured than kept.  Once, and only before the first acquire, submit or push (AISX_ERR_INVALID
+ * afterwards, and for a window outside [0, 15]); a handle on which this was never called allocates and queues nothing
+ * for it. */
+int aisx_rx_enable_dedup(aisx_rx* h, int window);
+/* the duplicate suppression's counts [AISX_DEDUP_NCNT] of the block popped last (all 0 before the first pop).
+ * AISX_ERR_INVALID on a handle without dedup enabled. */
+int aisx_rx_popped_dedup(aisx_rx* h, int* counts);
 /* from the next submitted block on (aisx_xlate_set_center_freq of the handle's filter) */
 int aisx_rx_set_center_freq(aisx_rx* h, int stream, int chan, double center_freq);
 /* A failed block (a HIP error, the chain refusing) makes every later call but destroy return that block's error. */
