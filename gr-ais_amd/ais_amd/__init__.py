@@ -23,6 +23,7 @@ del _t
 
 from .framing import AIS_REPAIR_EVENTS, AIS_REPAIR_RULES, REPAIR_PAIR, REPAIR_SINGLE, REPAIR_SKIP, repair_mark  # noqa: F401
 from .framing import MSG_COLUMNS, MSG_DTYPE, MSG_NA, hdlc_deframer_bp, mlse_detector, msg_decode, nmea_to_pdu, pdu_to_nmea  # noqa: F401
+from .framing import MSG_ENC_BAD_CHAR, MSG_ENC_BAD_ROW, MSG_ENC_NO_LAYOUT, MSG_ENC_NO_MMSI, MSG_ENC_RANGE, msg_encode  # noqa: F401
 from .framing import DEDUP_COUNTS, dedup_key, pdu_dedup  # noqa: F401
 from .modulate import gmsk_mod, modulate_vector_bc  # noqa: F401
 from .transmit import BURST_DTYPE, gmsk_burst, gmsk_scene, hdlc_framer  # noqa: F401
@@ -38,7 +39,7 @@ def __getattr__(name):
 
         return getattr(blocks, name)
     if name in ("hdlc_deframer_batch", "pdu_to_nmea_batch", "pdu_decode_batch", "PDU_DTYPE", "vessel_table", "vessel_table_batch",
-                "TRACK_COLUMNS", "TRACK_COUNTS", "TRACK_DTYPE", "mlse_detector_batch", "nmea_to_pdu_batch", "pdu_dedup_batch"):
+                "TRACK_COLUMNS", "TRACK_COUNTS", "TRACK_DTYPE", "mlse_detector_batch", "nmea_to_pdu_batch", "pdu_dedup_batch", "pdu_encode_batch"):
         from . import batch_framing
 
         return getattr(batch_framing, name)

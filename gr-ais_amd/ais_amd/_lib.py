@@ -29,6 +29,8 @@ AISX_HDLC_EV_SINGLE, AISX_HDLC_EV_PAIR, AISX_HDLC_EV_SKIP = 1, 2, 4  # error eve
 AISX_MLSE_ST_BAD_COUNT = 1
 MLSE_BLOCK, MLSE_OVERLAP = 64, 16  # symbols a block of the sequence detector decides, and its window's overlap
 AISX_MSG_FL_COMPLETE, AISX_MSG_FL_NO_LAYOUT, AISX_MSG_FL_BAD_RECORD = 1, 2, 4
+AISX_MSG_ENC_NO_MMSI, AISX_MSG_ENC_NO_LAYOUT, AISX_MSG_ENC_RANGE, AISX_MSG_ENC_BAD_CHAR, AISX_MSG_ENC_BAD_ROW = 1, 2, 4, 8, 16
+AISX_MSG_ENC_PITCH = 56  # octets between the payloads of two records of aisx_msg_enc_batch's list
 AISX_NMEA_PARSE_REF_TAIL = 1
 # what a call of the NMEA parsers reports (include/aisx.h, AISX_NMEAP_*), in order
 AISX_NMEAP_NAMES = ("FOUND", "KEPT", "BAD_INPUT", "LINES", "SENTENCES", "REJ_FORMAT", "REJ_CHECKSUM", "REJ_CHANNEL",
@@ -260,6 +262,12 @@ def lib(device=True):
     sig("aisx_msg_batch_process", i32, [vp, vp, vp, vp, vp, vp])
     sig("aisx_msg_batch_results_device", i32, [vp, pvp, plng, pvp, pvp])
     sig("aisx_msg_batch_read", i32, [vp, vp, lng, vp, i32, pi32, pi32, vp])
+    sig("aisx_msg_encode", i32, [vp, vp, i32, i32, vp, i32, pi32, pi32])
+    sig("aisx_msg_enc_batch_create", i32, [pvp, i32, i32, i32])
+    sig("aisx_msg_enc_batch_destroy", i32, [vp])
+    sig("aisx_msg_enc_batch_process", i32, [vp, vp, lng, vp, vp, vp, vp, i32, i32, vp])
+    sig("aisx_msg_enc_batch_results_device", i32, [vp, pvp, pvp, pvp, pvp])
+    sig("aisx_msg_enc_batch_read", i32, [vp, vp, vp, i32, vp, lng, pi32, vp, vp])
     sig("aisx_rx_enable_messages", i32, [vp])
     sig("aisx_rx_pop_messages", i32, [vp, i32, pll, vp, lng, plng, vp, i32, pi32, vp, lng, vp, pi32])
     sig("aisx_track_create", i32, [pvp, i32])

@@ -842,6 +842,140 @@ class vessel_table_batch:
         return _track_table(cols, strs, len(idx), idx)
 
 
+ENCODE_COUNTS = ("found", "records", "bad_input", "encoded", "refused")
+
+
+class pdu_encode_batch:
+    """ais_amd.msg_encode for every row of a table in device memory at once (aisx_msg_enc_batch_*): the inverse of
+    pdu_decode_batch.  Record i of the list it makes is exactly msg_encode(row i) -- or of row idx[i] with an index
+    list --, at most max_rows records per call from a table of table_rows rows (the decoder's max_pdus, the vessel
+    table's capacity) on nchan channels.  The list has the layout every stage behind the deframer takes: record i has
+    end_bit = i, offset = 56 * i and the length msg_encode gives, 0 for a refused row (status() tells why), for which
+    the armouring stage writes nothing.  results_device() gives (pdus, bytes, count) as the deframer's does.
+
+    A snapshot of the vessel table as !AIVDM text, without the table leaving the device:
+
+        vt = ais_amd.vessel_table_batch(capacity, max_pdus)
+        enc = ais_amd.pdu_encode_batch(nchan, capacity, capacity)
+        nm = ais_amd.pdu_to_nmea_batch("A", nchan, capacity, 64, standard=True)
+        enc.work(vt, as_type=1, stream=s)                # every vessel as a position report (as_type=5: static data)
+        nm.work_device(*enc.results_device(), stream=s)  # pdus, bytes, count: all records, none found beyond them
+        recs, text = nm.sentences(stream=s)
+
+    and what a step changed, on their channels: enc.work(vt, as_type=1, changed_only=True, chan="table", stream=s).
+    A vessel that lacks a column gets the protocol's "not available" value; one whose columns do not fit the type
+    (a class-B vessel's missing NAV_STATUS is fine, a 30-bit IMO is not asked for by type 1) is refused, not truncated."""
+
+    def __init__(self, nchan, max_rows, table_rows):
+        h = C.c_void_p()
+        check(_lib.lib().aisx_msg_enc_batch_create(C.byref(h), int(nchan), int(max_rows), int(table_rows)), "pdu_encode_batch")
+        self._h = h
+        self.nchan, self.max_rows, self.table_rows = int(nchan), int(max_rows), int(table_rows)
+        self.max_pdus = self.max_rows  # (what the stages behind call a list's capacity)
+        self.counts = dict.fromkeys(ENCODE_COUNTS, 0)
+        self._keep = None  # what the last call reads, kept alive until the next
+        self._recs = self._data = self._st = None  # read-back buffers, made on first use
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            _lib.lib().aisx_msg_enc_batch_destroy(h)
+            self._h = None
+
+    def work(self, table, as_type=0, as_part=-1, changed_only=False, chan=None, stream=None):
+        """Encodes the rows of `table` (queued on `stream`, default the current one; nothing waits):
+          - a pdu_decode_batch: the rows of its last call;
+          - a vessel_table_batch: every vessel, or with changed_only=True the last update's changed list, in its
+            order; chan="table" takes each vessel's CHAN column as its channel;
+          - device tensors (cols int32 [ncol][col_stride], strs uint8 [rows][48] or None, nrows int32 [1][, idx int32
+            [rows]]).
+        chan: None (channel 0) or an int32 device tensor, indexed by record without an index list and by table row with
+        one."""
+        idx = None
+        if isinstance(table, pdu_decode_batch):
+            c, stride, s, n = table.results_device()
+            n += 4
+        elif isinstance(table, vessel_table_batch):
+            r = table.results_device()
+            c, stride, s = r["cols"].data_ptr(), r["cols"].shape[1], r["strs"].data_ptr()
+            n = r["count"].data_ptr() + 4 * TRACK_COUNTS.index("changed" if changed_only else "vessels")
+            idx = r["changed"].data_ptr() if changed_only else None
+            if isinstance(chan, str):
+                if chan != "table":
+                    raise ValueError("pdu_encode_batch.work: chan is None, \"table\" or an int32 device tensor")
+                chan = r["cols"][TRACK_COLUMNS.index("CHAN")]
+        else:
+            cols, strs, nrows = table[:3]
+            it = table[3] if len(table) > 3 else None
+            for name, t, dt in (("cols", cols, torch.int32), ("strs", strs, torch.uint8), ("nrows", nrows, torch.int32), ("idx", it, torch.int32)):
+                if t is not None and (t.dtype != dt or not t.is_cuda or not t.is_contiguous()):
+                    raise ValueError("pdu_encode_batch.work: %s must be a contiguous %s device tensor" % (name, dt))
+            if cols.dim() != 2 or cols.shape[0] < len(TRACK_COLUMNS) - 4 or nrows.numel() != 1:
+                raise ValueError("pdu_encode_batch.work: need cols [ncol][col_stride] and ONE row count")
+            c, stride, s, n = cols.data_ptr(), cols.shape[1], strs.data_ptr() if strs is not None else None, nrows.data_ptr()
+            idx = it.data_ptr() if it is not None else None
+        if changed_only and not isinstance(table, vessel_table_batch):
+            raise ValueError("pdu_encode_batch.work: changed_only belongs to a vessel_table_batch")
+        if chan is not None and (isinstance(chan, str) or chan.dtype != torch.int32 or not chan.is_cuda or not chan.is_contiguous()):
+            raise ValueError("pdu_encode_batch.work: chan is None, \"table\" (of a vessel_table_batch) or an int32 device tensor")
+        self._keep = (table, chan)
+        self.work_device(c, stride, s, n, idx, chan.data_ptr() if chan is not None else None, as_type, as_part, stream)
+
+    def work_device(self, cols_ptr, col_stride, strs_ptr, nrows_ptr, idx_ptr=None, chan_ptr=None, as_type=0, as_part=-1, stream=None):
+        """Device addresses: int32 cols [ncol][col_stride] (col_stride >= table_rows), char strs [table_rows][48]
+        (4-byte aligned, or None), ONE int = records to make, optionally int32 idx [records] and int32 chan.  Queued
+        on `stream`; the count is read on the device."""
+        check(_lib.lib().aisx_msg_enc_batch_process(self._h, C.c_void_p(cols_ptr), int(col_stride),
+                                                    C.c_void_p(strs_ptr) if strs_ptr else None,
+                                                    C.c_void_p(idx_ptr) if idx_ptr else None, C.c_void_p(nrows_ptr),
+                                                    C.c_void_p(chan_ptr) if chan_ptr else None, int(as_type), int(as_part),
+                                                    _stream_ptr(stream)), "pdu_encode_batch.work")
+
+    def _results(self):
+        v = [C.c_void_p() for _ in range(4)]
+        check(_lib.lib().aisx_msg_enc_batch_results_device(self._h, *[C.byref(x) for x in v]), "pdu_encode_batch.results_device")
+        return tuple(x.value for x in v)
+
+    def results_device(self):
+        """device addresses of the last call's records (aisx_pdu [max_rows]), bytes and counts (int [5]: records twice,
+        the bad-count flag, rows encoded, rows refused), as hdlc_deframer_batch.results_device(); as the arguments of a
+        work_device() behind, (pdus, bytes, count) say: count + 0 records, none found beyond them"""
+        return self._results()[:3]
+
+    def status_device(self):
+        """device address of the last call's status (int32 [max_rows], entry i for record i)"""
+        return self._results()[3]
+
+    def _read(self, stream):
+        if self._recs is None:
+            self._recs = np.zeros(self.max_rows, dtype=PDU_DTYPE)
+            self._data = np.zeros(self.max_rows * _lib.AISX_MSG_ENC_PITCH, dtype=np.uint8)
+            self._st = np.zeros(self.max_rows, dtype=np.int32)
+        n = C.c_int(0)
+        cnt = np.zeros(len(ENCODE_COUNTS), dtype=np.int32)
+        rc = _lib.lib().aisx_msg_enc_batch_read(self._h, self._recs.ctypes.data_as(C.c_void_p), self._st.ctypes.data_as(C.c_void_p),
+                                                self.max_rows, self._data.ctypes.data_as(C.c_void_p), self._data.size, C.byref(n),
+                                                cnt.ctypes.data_as(C.c_void_p), _stream_ptr(stream))
+        self.counts = {k: int(v) for k, v in zip(ENCODE_COUNTS, cnt)}
+        check(rc, "pdu_encode_batch")
+        k = n.value
+        return self._recs[:k].copy(), self._data[: k * _lib.AISX_MSG_ENC_PITCH].copy(), self._st[:k].copy()
+
+    def pdus(self, stream=None, as_list=False):
+        """The last call's list on the host (synchronises `stream`): (records, bytes) with records a PDU_DTYPE array
+        (chan, end_bit = i, len, offset = 56 i into bytes), or with as_list=True a list of (chan, end_bit, payload
+        bytes).  self.counts has the call's counts.  ValueError when a call since the last read met a row count outside
+        [0, max_rows] (it made no records)."""
+        recs, data, _ = self._read(stream)
+        if as_list:
+            return [(int(r["chan"]), int(r["end_bit"]), bytes(data[r["offset"]:r["offset"] + r["len"]])) for r in recs]
+        return recs, data
+
+    def status(self, stream=None):
+        """the last call's status per record (synchronises `stream`): an int32 array, 0 or a sum of MSG_ENC_*"""
+        return self._read(stream)[2]
+
+
 class pdu_dedup_batch:
     """ais_amd.pdu_dedup in device memory (aisx_dedup_batch_*): the same kept records, first, copies, marks and counts,
     bit for bit, for at most max_pdus records per call, by kernels queued between a producer of a PDU list (the deframer,

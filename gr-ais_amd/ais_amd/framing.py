@@ -371,6 +371,43 @@ def msg_decode(payload):
     return out
 
 
+MSG_ENC_NO_MMSI, MSG_ENC_NO_LAYOUT, MSG_ENC_RANGE = _lib.AISX_MSG_ENC_NO_MMSI, _lib.AISX_MSG_ENC_NO_LAYOUT, _lib.AISX_MSG_ENC_RANGE
+MSG_ENC_BAD_CHAR, MSG_ENC_BAD_ROW = _lib.AISX_MSG_ENC_BAD_CHAR, _lib.AISX_MSG_ENC_BAD_ROW
+
+
+def msg_row(row):
+    """a msg_decode dict or one MSG_DTYPE record -> (int32 cols [ncol], uint8 strs [48]); a column the dict does not
+    name is MSG_NA, a string it does not name is empty"""
+    is_dict = isinstance(row, dict)
+    cols = np.full(len(MSG_COLUMNS), MSG_NA, dtype=np.int32)
+    strs = np.zeros(_lib.AISX_MSG_STR, dtype=np.uint8)
+    for k, c in enumerate(MSG_COLUMNS):
+        if not is_dict:
+            cols[k] = row[c.lower()]
+        elif c in row:
+            cols[k] = row[c]
+    for name, lo, w in (("callsign", 0, 7), ("name", 8, 20), ("destination", 28, 20)):
+        s = bytes(row[name]) if not is_dict or name in row else b""
+        if len(s) > w:
+            raise ValueError("msg_encode: %s holds %d characters, the slot %d" % (name, len(s), w))
+        strs[lo:lo + len(s)] = np.frombuffer(s, dtype=np.uint8)
+    return cols, strs
+
+
+def msg_encode(row, as_type=0, as_part=-1):
+    """aisx_msg_encode, the inverse of msg_decode: a msg_decode dict or one MSG_DTYPE record -> (payload bytes,
+    status).  The type is as_type when that is in 1..63, else the row's TYPE; for type 24 the part is as_part when
+    that is >= 0, else the row's PART.  A column that is MSG_NA takes the protocol's "not available" value.  status
+    is 0 or a sum of MSG_ENC_* (NO_MMSI, NO_LAYOUT, RANGE, BAD_CHAR); the payload of a refused row is b""."""
+    cols, strs = msg_row(row)
+    pdu = np.zeros(_lib.AISX_MSG_ENC_PITCH, dtype=np.uint8)
+    n, st = C.c_int(0), C.c_int(0)
+    check(_lib.lib(device=False).aisx_msg_encode(cols.ctypes.data_as(C.c_void_p), strs.ctypes.data_as(C.c_void_p), int(as_type),
+                                                 int(as_part), pdu.ctypes.data_as(C.c_void_p), pdu.size, C.byref(n), C.byref(st)),
+          "msg_encode")
+    return pdu[: n.value].tobytes(), st.value
+
+
 def msg_table(cols, strs, n):
     """int32 [ncol][>= n] and uint8 [>= n][48] on the host -> a MSG_DTYPE array of n rows"""
     out = np.zeros(n, dtype=MSG_DTYPE)

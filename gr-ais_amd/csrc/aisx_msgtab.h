@@ -1,5 +1,6 @@
 // aisx_msgtab.h -- the ITU-R M.1371 field layouts, written once: the host aisx_msg_decode (aisx_msg.cpp, the
-// specification) and the batched kernel (k_msg.h) read the same table through the same extraction helpers.
+// specification) and the batched kernel (k_msg.h) read the same table through the same extraction helpers, and the
+// writers (aisx_msg_encode, aisx_msg_enc.cpp, and k_msg_enc.h) run it the other way through their inverses, below.
 //
 // Message bit i is bit 7 - i % 8 of payload octet i / 8.  Both readers hold a payload as MSG_ROW big-endian 32-bit
 // words (octets 4k .. 4k + 3 in word k, zero beyond the payload, word MSG_ROW - 1 always zero), so message bit i is
@@ -279,6 +280,145 @@ AISX_HD uint32_t msg_str_word(const uint32_t* w, const uint32_t* lay, int nbits,
     for (int c = 0; c < n; c++)
         out |= msg_char(x >> (6 * (n - 1 - c)) & 63u) << (8 * c);
     return out;
+}
+
+// ------------------------------------------------------------------
+// The writer (aisx_msg_encode, aisx_msg_enc.cpp, and the batched kernel, k_msg_enc.h): the same table read the other
+// way.  A row of columns becomes the payload of its layout, ceil(MT_MIN_BITS / 8) octets, every bit that no column or
+// string covers zero.
+// ------------------------------------------------------------------
+constexpr int MSG_ENC_OCTETS = 56;             // the pitch of a record's payload in the device form's list
+constexpr int MSG_ENC_WORDS = MSG_ENC_OCTETS / 4; // = MSG_ROW - 1: the words of a staged payload that hold octets
+constexpr int MSG_ENC_NO_MMSI = 1, MSG_ENC_NO_LAYOUT = 2, MSG_ENC_RANGE = 4, MSG_ENC_BAD_CHAR = 8, MSG_ENC_BAD_ROW = 16;
+
+// what a column that is MSG_NA is written as, in class-A units: the protocol's "not available" where it has one
+struct MsgDefaults {
+    int32_t v[MSG_NCOL];
+};
+constexpr MsgDefaults msg_make_defaults()
+{
+    MsgDefaults d{};
+    d.v[MC_NAV_STATUS] = 15;
+    d.v[MC_ROT] = -128;
+    d.v[MC_SOG] = 1023;
+    d.v[MC_LON] = 181 * 600000;
+    d.v[MC_LAT] = 91 * 600000;
+    d.v[MC_COG] = 3600;
+    d.v[MC_HEADING] = 511;
+    d.v[MC_SECOND] = 60;
+    d.v[MC_HOUR] = 24;
+    d.v[MC_MINUTE] = 60;
+    d.v[MC_DTE] = 1;
+    return d;
+}
+// the table and the defaults as the writers hold them: MSG_ENC_TAB_WORDS words, the defaults behind the layouts
+constexpr int MSG_ENC_TAB_WORDS = MSG_TAB_WORDS + (int)MSG_NCOL;
+struct MsgEncTab {
+    MsgTab t;
+    MsgDefaults d;
+};
+constexpr MsgEncTab msg_make_enc_tab() { return MsgEncTab{ msg_make_tab(), msg_make_defaults() }; }
+
+// the inverse of msg_bits: ors the low n bits of x into bits [s, s + n) of the staged payload, 1 <= n <= 30
+AISX_HD void msg_put_bits(uint32_t* w, int s, int n, uint32_t x)
+{
+    const int a = s >> 5;
+    const uint64_t v = (uint64_t)(x & ((1u << n) - 1u)) << (64 - (s & 31) - n);
+    w[a] |= (uint32_t)(v >> 32);
+    w[a + 1] |= (uint32_t)v; // (a + 1 <= MSG_ROW - 1; no field reaches that word, so it stays zero)
+}
+
+// the inverse of msg_field for a column value v that is not MSG_NA: the field's bits in *x; false when the value does
+// not fit the field (nothing is ever truncated).  Type 27's three ops are undone in integers first, and the range
+// applies to the converted value.
+AISX_HD bool msg_unfield(uint32_t d, int32_t v, uint32_t* x)
+{
+    const int n = (int)(d >> 9 & 31u);
+    bool ok = true;
+    switch (d >> 15) {
+    case MSG_OP_X1000: // to nearest, halves away from zero
+        v = v >= 0 ? (int32_t)(((int64_t)v + 500) / 1000) : -(int32_t)((500 - (int64_t)v) / 1000);
+        break;
+    case MSG_OP_SOG27:
+        ok = v >= 0 && v <= 1023;
+        v = !ok ? 0 : v == 1023 ? 63 : v >= 615 ? 62 : (v + 5) / 10;
+        break;
+    case MSG_OP_COG27:
+        ok = v >= 0;
+        v = !ok ? 0 : v >= 3600 ? 511 : ((v + 5) / 10) % 360;
+        break;
+    }
+    const int32_t lim = (int32_t)1 << ((d >> 14 & 1u) ? n - 1 : n);
+    ok = ok && v < lim && v >= ((d >> 14 & 1u) ? -lim : 0);
+    *x = (uint32_t)v & ((1u << n) - 1u);
+    return ok;
+}
+
+// byte b of a string slot -> its six bits; false for a byte that has none (lower case included)
+AISX_HD bool msg_unchar(uint32_t b, uint32_t* six)
+{
+    *six = b & 63u;
+    return b >= 32u && b < 96u;
+}
+
+// One row -> the staged payload w[MSG_ROW] (zeroed here) and its length in octets; returns the status, 0 or a sum of
+// MSG_ENC_*.  v: the row's MSG_NCOL columns; str: its MSG_STR bytes as MSG_STR_WORDS words, the first byte lowest
+// (nullptr: all NUL); tab: MSG_ENC_TAB_WORDS words.  A refused row leaves w zero and *len 0.
+AISX_HD int msg_encode_row(const int32_t* v, const uint32_t* str, int as_type, int as_part, const uint32_t* tab, uint32_t* w, int* len)
+{
+    for (int k = 0; k < MSG_ROW; k++)
+        w[k] = 0;
+    *len = 0;
+    const int32_t type = as_type >= 1 && as_type <= 63 ? as_type : v[MC_TYPE];
+    int32_t part = as_part >= 0 ? as_part : v[MC_PART];
+    const int layout = type >= 1 && type <= 63 ? msg_layout(type, part) : ML_NONE;
+    if (layout == ML_24X && part == MSG_NA)
+        part = 3;
+    int st = layout == ML_NONE ? MSG_ENC_NO_LAYOUT : 0;
+    if (v[MC_MMSI] == MSG_NA)
+        st |= MSG_ENC_NO_MMSI;
+    else if (v[MC_MMSI] < 0 || v[MC_MMSI] >= 1 << 30) // (out of range: no MMSI, and a column that does not fit)
+        st |= MSG_ENC_NO_MMSI | MSG_ENC_RANGE;
+    const uint32_t* lay = tab + layout * MSG_TAB_ROW;
+    const int32_t* def = (const int32_t*)(tab + MSG_TAB_WORDS);
+    if (layout != ML_NONE) {
+#pragma unroll
+        for (int c = 0; c < MSG_NCOL; c++) { // (unrolled: the kernel holds v in registers)
+            const uint32_t d = lay[c];
+            if ((d >> 9 & 31u) == 0 || c == MC_FLAGS || c == MC_MMSI)
+                continue;
+            int32_t val = c == MC_TYPE ? type : c == MC_PART ? part : v[c];
+            if (val == MSG_NA)
+                val = def[c];
+            uint32_t x;
+            if (!msg_unfield(d, val, &x))
+                st |= MSG_ENC_RANGE;
+            msg_put_bits(w, (int)(d & 511u), (int)(d >> 9 & 31u), x);
+        }
+        msg_put_bits(w, 8, 30, (uint32_t)v[MC_MMSI]);
+        for (int slot = 0; slot < 3; slot++) {
+            const int s0 = (int)lay[MT_CALLSIGN + slot];
+            if (s0 == 0 || !str)
+                continue;
+            const int nch = slot == 0 ? 7 : 20, b0 = slot == 0 ? 0 : slot == 1 ? 8 : 28;
+            for (int k = 0; k < nch; k++) {
+                const uint32_t b = str[(b0 + k) >> 2] >> (8 * ((b0 + k) & 3)) & 255u;
+                if (b == 0)
+                    break; // (from the first NUL on, the slot is zeros)
+                uint32_t six;
+                if (!msg_unchar(b, &six))
+                    st |= MSG_ENC_BAD_CHAR;
+                msg_put_bits(w, s0 + 6 * k, 6, six);
+            }
+        }
+    }
+    if (st != 0) {
+        for (int k = 0; k < MSG_ROW; k++)
+            w[k] = 0;
+        return st;
+    }
+    *len = ((int)lay[MT_MIN_BITS] + 7) >> 3;
+    return 0;
 }
 
 } // namespace aisx

@@ -882,6 +882,63 @@ int aisx_msg_batch_results_device(const aisx_msg_batch* h, const int32_t** d_col
 int aisx_msg_batch_read(aisx_msg_batch* h, int32_t* cols, long col_stride, char* strs, int cap, int* nrecs, int* nfound,
                         void* stream);
 
+/* The inverse of aisx_msg_decode: a row of the column table -> the payload octets of its layout.  cols
+ * [AISX_MSG_NCOL] and strs [AISX_MSG_STR] exactly as aisx_msg_decode gives them (strs NULL: all NUL).
+ *   - The type is as_type when that is in 1..63, else cols[TYPE]; for type 24 the part is as_part when that is >= 0,
+ *     else cols[PART] (NA: the layout without a part, PART written as 3).
+ *   - *len = ceil(minimum bits / 8) octets of the layout: 21 (1-3, 4, 11, 18, 24B), 53 (5), 39 (19), 34 (21), 20 (24A
+ *     and 24 with another part), 12 (27).  Every column the layout carries is written at its place; bits that no
+ *     column or string covers (spares, type 24B's vendor id, type 21's name extension) are zero.
+ *   - TYPE and PART are the chosen ones, FLAGS is ignored; a column that is AISX_MSG_NA takes the protocol's "not
+ *     available" value (NAV_STATUS 15, ROT -128, SOG 1023, LON 181 deg, LAT 91 deg, COG 3600, HEADING 511, SECOND 60,
+ *     HOUR 24, MINUTE 60, DTE 1) and 0 where there is none.  Type 27's LON / LAT / SOG / COG are converted from
+ *     class-A units in integers: v / 1000 to nearest (halves away from zero); SOG 1023 -> 63, else min(62, (v + 5) /
+ *     10); COG >= 3600 -> 511, else ((v + 5) / 10) % 360.
+ *   - A string slot is written up to its first NUL ('@' from there on): bytes 64..95 as b - 64, 32..63 as b.
+ * *status is 0 or a sum of AISX_MSG_ENC_*; with a status other than 0 the row is refused: *len = 0, nothing written.
+ * Nothing is ever truncated: a value that does not fit its field (the converted value for type 27) is a range error.
+ * Returns AISX_OK in both cases, AISX_ERR_INVALID for a missing pointer, AISX_ERR_OVERFLOW when cap is below the
+ * length (nothing written).  Plain C++, no device. */
+enum {
+    AISX_MSG_ENC_NO_MMSI = 1,   /* MMSI is AISX_MSG_NA or outside [0, 2^30) (then with AISX_MSG_ENC_RANGE) */
+    AISX_MSG_ENC_NO_LAYOUT = 2, /* a type without a layout (AISX_MSG_FL_NO_LAYOUT's), AISX_MSG_NA or outside 1..63 */
+    AISX_MSG_ENC_RANGE = 4,     /* a column the layout carries does not fit its field */
+    AISX_MSG_ENC_BAD_CHAR = 8,  /* a string byte outside 32..95 before the slot's first NUL (lower case included) */
+    AISX_MSG_ENC_BAD_ROW = 16   /* device lists only: a row index outside the table or a channel outside [0, nchan) */
+};
+int aisx_msg_encode(const int32_t* cols, const char* strs, int as_type, int as_part, uint8_t* pdu, int cap, int* len,
+                    int* status);
+
+#define AISX_MSG_ENC_PITCH 56 /* octets between the payloads of two records of aisx_msg_enc_batch's list */
+typedef struct aisx_msg_enc_batch aisx_msg_enc_batch;
+/* at most max_rows records per call, made from a table of table_rows rows, on nchan channels.  The handle owns the
+ * records, AISX_MSG_ENC_PITCH * max_rows payload bytes and a status per record on the device that was current here. */
+int aisx_msg_enc_batch_create(aisx_msg_enc_batch** h, int nchan, int max_rows, int table_rows);
+int aisx_msg_enc_batch_destroy(aisx_msg_enc_batch* h);
+/* d_cols / col_stride / d_strs as aisx_msg_batch_results_device or aisx_track_batch_results_device gives them (d_strs
+ * 4-byte aligned, or NULL: all NUL); d_nrows: ONE int on the device, the records to make.  d_idx (may be NULL): int32
+ * [rows], record i is made from table row d_idx[i] -- the vessel table's d_changed with d_count + AISX_TRK_CNT_CHANGED,
+ * say; without it record i is row i.  d_chan (may be NULL: channel 0): int32, the channel of record i at d_chan[i]
+ * without d_idx and at d_chan[d_idx[i]] with it (a column of the table, then).  A row index outside [0, table_rows) or
+ * a channel outside [0, nchan) gives status AISX_MSG_ENC_BAD_ROW and the table is not read for that record.
+ * Record i: end_bit = i, offset = AISX_MSG_ENC_PITCH * i, len and status as aisx_msg_encode gives them (len 0 for a
+ * refused row, whose channel is written as 0 when it is the bad part), the bytes of its pitch beyond len zero.
+ * Queued on `stream`; no host sync.  A row count outside [0, max_rows] writes nothing and makes the next read say so. */
+int aisx_msg_enc_batch_process(aisx_msg_enc_batch* h, const int32_t* d_cols, long col_stride, const char* d_strs,
+                               const int32_t* d_idx, const int* d_nrows, const int32_t* d_chan, int as_type, int as_part,
+                               void* stream);
+/* the last call's list in device memory, in the layout every stage behind the deframer takes: d_pdus [max_rows],
+ * d_bytes, d_count[0] = d_count[1] = records, d_count[2] != 0 after a bad row count, d_count[3] = rows encoded,
+ * d_count[4] = rows refused; d_status int32 [max_rows] */
+int aisx_msg_enc_batch_results_device(const aisx_msg_enc_batch* h, const aisx_pdu** d_pdus, const uint8_t** d_bytes,
+                                      const int** d_count, const int32_t** d_status);
+/* copies the first min(records, cap) records, their status and their AISX_MSG_ENC_PITCH bytes each to the host
+ * (synchronises `stream`): pdus [cap], status [cap], bytes [bytes_cap]; *nrecs = records copied, counts (may be NULL)
+ * int [5] as d_count.  AISX_ERR_OVERFLOW when fewer were copied than there are (cap, or bytes_cap below the pitch times
+ * the records), AISX_ERR_INVALID when a call since the previous read met a bad row count (the flag is then cleared). */
+int aisx_msg_enc_batch_read(aisx_msg_enc_batch* h, aisx_pdu* pdus, int32_t* status, int cap, uint8_t* bytes, long bytes_cap,
+                            int* nrecs, int* counts, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* the vessel table: the latest state per MMSI, merged from decoded tables    */
 /* call by call -- on the host (the specification), and in device memory,     */
