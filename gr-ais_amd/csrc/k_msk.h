@@ -17,10 +17,14 @@
 // few lanes are enabled (tools/ubench), so the loop is written for instruction count:
 //  * the reference's iteration comes in two kinds, d_div even (emit a symbol) and
 //    d_div odd (run the loop filter).  While no lane is near an event, (even, odd) pairs
-//    run in lock step in a counted loop with no test inside: the number of pairs every
+//    run in lock step with no test inside: the number of pairs every
 //    lane can run follows from a per-lane bound fast_lim on iidx (end of this
 //    general_work call, data horizon, next time_est tag) and the proven maximum advance
-//    of a pair; the wave takes the minimum.  In a run two lanes share a channel's pair:
+//    of a pair; the wave takes the minimum.  The pairs of a run go in straight-line trips
+//    (msk_run_trips: 8 pairs of the hand-scheduled build, 4 of the compiler-scheduled ones,
+//    written out one behind the other, then 4 / 2 / 1 by the bits of what is left), because a
+//    loop step with its taken branch costs a lone wave as much as five instructions of the
+//    pair's seventy.  In a run two lanes share a channel's pair:
 //    one does the even iteration, the other the odd one at the same time (the even one
 //    has no feedback into mu), the squares cross over by a row swap;
 //  * lanes at an event run the reference's loop head in its order (events()) behind
@@ -57,6 +61,70 @@ constexpr int MSK_CHUNK = 64;   // samples per chunk
 constexpr int MSK_OFF = 192;    // ring slot of new-sample index s is (s + MSK_OFF) & 255
 constexpr int MSK_CARRY_MAX = 128;
 constexpr int MSK_PAIRS_MAX = 16; // pairs of iterations per check-free run (a power of two)
+// A run's pairs go in trips of TRIP pairs written out one behind the other, with no loop control between them (a lone
+// wave pays for s_add + s_cmp + a taken branch what it pays for five dependent instructions, tools/ubench/exec_width.hip);
+// what is left below a trip runs as TRIP / 2, ..., 1 pairs by the bits of the count.  TRIP = MSK_PAIRS_MAX: no loop at
+// all, one descending ladder of 16 pairs entered by a switch.  TRIP = 1: the counted loop of one pair per trip.
+// MSK_TRIP: the hand-scheduled pair (Ctx::pair_core).  MSK_TRIP_CXX: the pair as C++ statements, which the compiler
+// schedules across the pairs of a trip, not to its advantage beyond 4.  (-DMSK_TRIP=n -DMSK_TRIP_CXX=m rebuilds; the
+// trip lengths that lost: DESIGN_APPENDIX.md A.7)
+#ifndef MSK_TRIP
+#define MSK_TRIP 8
+#endif
+#ifndef MSK_TRIP_CXX
+#define MSK_TRIP_CXX 4
+#endif
+// f() N times, written out
+template <int N, class F>
+AISX_DI void msk_times(F& f)
+{
+    if constexpr (N > 0) {
+        f();
+        msk_times<N - 1>(f);
+    }
+}
+// f() n times, 0 <= n <= MSK_PAIRS_MAX, in straight-line trips of TRIP: the one structure of every build's plain pair loop
+template <int TRIP, class F>
+AISX_DI void msk_run_trips(int n, F& f)
+{
+    static_assert(TRIP == 1 || TRIP == 2 || TRIP == 4 || TRIP == 8 || TRIP == MSK_PAIRS_MAX, "pairs per trip");
+    if constexpr (TRIP == MSK_PAIRS_MAX) {
+        switch (n) {
+        case 16: f(); [[fallthrough]];
+        case 15: f(); [[fallthrough]];
+        case 14: f(); [[fallthrough]];
+        case 13: f(); [[fallthrough]];
+        case 12: f(); [[fallthrough]];
+        case 11: f(); [[fallthrough]];
+        case 10: f(); [[fallthrough]];
+        case 9: f(); [[fallthrough]];
+        case 8: f(); [[fallthrough]];
+        case 7: f(); [[fallthrough]];
+        case 6: f(); [[fallthrough]];
+        case 5: f(); [[fallthrough]];
+        case 4: f(); [[fallthrough]];
+        case 3: f(); [[fallthrough]];
+        case 2: f(); [[fallthrough]];
+        case 1: f(); [[fallthrough]];
+        default: break;
+        }
+    } else {
+        for (; n >= TRIP; n -= TRIP)
+            msk_times<TRIP>(f);
+        if constexpr (TRIP >= 8) {
+            if (n & 4)
+                msk_times<4>(f);
+        }
+        if constexpr (TRIP >= 4) {
+            if (n & 2)
+                msk_times<2>(f);
+        }
+        if constexpr (TRIP >= 2) {
+            if (n & 1)
+                f();
+        }
+    }
+}
 constexpr int MSK_TAPS_PITCH = 12; // floats per table row in LDS: 16-byte aligned rows, two 128-bit reads per FIR
 constexpr int msk_lds_ring(int lpw) { return MSK_SLOTS * lpw * 8; } // rings: [MSK_SLOTS][lpw] samples
 constexpr int MSK_ZERO_ROW = 129; // an all-zero tap row: where an out-of-range mu lands
@@ -211,11 +279,19 @@ AISX_HD int msk_forecast(float d_sps, int noutput_items)
 #ifdef MSK_EMU_STATS
 extern long msk_stats[8];
 #endif
+#ifdef MSK_EMU_RUN_STATS
+extern long msk_run_stats[MSK_PAIRS_MAX + 1]; // [k]: plain lock-step runs of k pairs (the lane-model build that defines it)
+#endif
 // whether a context brings the hand-scheduled pair (Ctx::pair_core): the device's does, the CPU lane model's does not
 template <class Ctx, class = void>
 struct msk_has_pair_core { static constexpr bool value = false; };
 template <class Ctx>
 struct msk_has_pair_core<Ctx, decltype((void)Ctx::has_pair_core)> { static constexpr bool value = Ctx::has_pair_core; };
+// whether the plain pair loop written as C++ statements stages a pair's symbol while the NEXT pair loads (the rotated
+// scheme) or at the end of its own pair: the first where lanes are free-running threads.  (A lane-model test build
+// specialises this for its context to run the loop the way the device's compiler-scheduled builds do.)
+template <class Ctx>
+struct msk_stage_rot { static constexpr bool value = !Ctx::wave_lds_coherent; };
 // AUX: the err / mu output ports are connected (:187-189).  OSPS2: osps == 2 (:186).
 // LPW: channels (active lanes) per wave; the LDS layouts are [.][LPW], so a build with few
 // channels per wave leaves most of the CU's LDS to whatever else runs there.
@@ -1252,7 +1328,7 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
                 // issue slots are free (the first pair of a run "stages" the entry value of acc in the spare row, the last
                 // symbol is staged at the run's exit).  `wat`: where the pair in progress will have its symbol staged.
                 // (the device's compiler-scheduled builds keep the write at the end of the pair: there it costs them no more)
-                constexpr bool ROT = STG && (CORE || !Ctx::wave_lds_coherent);
+                constexpr bool ROT = STG && (CORE || msk_stage_rot<Ctx>::value);
                 unsigned wat = stg_spare;
               if constexpr (CORE) {
                 typename Ctx::PairK kk;
@@ -1269,14 +1345,17 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
                 kk.rnd = 12582912.0f;
                 typename Ctx::v2f a2 = Ctx::tov(acc), e2 = Ctx::tov(sqE), o2 = Ctx::tov(sqO);
                 wat += cx.lds_addr(lds0);
-                for (int k = 0; k < npairs; k++)
-                    cx.pair_core(kk, d_mu, d_omega, sb, so, wat, a2, e2, o2, nl_prev);
+                auto pair = [&]() { cx.pair_core(kk, d_mu, d_omega, sb, so, wat, a2, e2, o2, nl_prev); };
+                msk_run_trips<MSK_TRIP>(npairs, pair);
                 wat -= cx.lds_addr(lds0);
                 acc = Ctx::tocf(a2);
                 sqE = Ctx::tocf(e2);
                 sqO = Ctx::tocf(o2);
               } else {
-                for (int k = 0; k < npairs; k++) {
+#ifdef MSK_EMU_RUN_STATS
+                if (l == 0 && q == 0) msk_run_stats[npairs]++;
+#endif
+                auto pair = [&]() {
 #ifdef MSK_EMU_STATS
                     if (l == 0 && q == 0) msk_stats[0]++;
 #endif
@@ -1333,7 +1412,8 @@ AISX_DI void msk_body(Ctx& cx, const MskParams& p)
                     sqE = sE;
                     sqO = s1;
                     nl_prev = nlO;
-                }
+                };
+                msk_run_trips<MSK_TRIP_CXX>(npairs, pair);
               }
                 if constexpr (ROT)
                     stage_at(wat, acc); // the run's last symbol

@@ -16,5 +16,5 @@ for f in csrc/*.hip; do
   o=$(basename "$f" .hip)
   if [ $o = $tu ]; then objs="$objs ../tools/scratch/obj/${tu}_${name}.o"; else objs="$objs build_exp/$o.hip.o"; fi
 done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../tools/scratch/libaisx_${name}.so $objs build_exp/aisx_framing.cpp.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../tools/scratch/libaisx_${name}.so $objs build_exp/*.cpp.o
 echo tools/scratch/libaisx_${name}.so

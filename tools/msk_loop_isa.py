@@ -7,8 +7,8 @@ Without --asm, compiles gr-ais_amd/csrc/aisx_msk.hip to assembly with the Makefi
 The loops are found by the compiler's loop comments: every innermost loop of the kernel that swaps rows
 (v_permlane16/32_swap) is a pair loop; the one of a single basic block is the plain lock-step loop, the one of several
 blocks (the tag tests branch) the tagged-run loop.  Reported per loop: VALU (packed counted apart), LDS, SALU, s_nop,
-v_mov, s_waitcnt, the total, and for the plain loop the longest chain of register dependences within one trip (each
-instruction one step; s_nop and s_waitcnt not counted).  --core: the build with the hand-scheduled pair, k_msk_core (its
+v_mov, s_waitcnt, the total, and for the plain loop the pairs written out per trip (k_msk.h: msk_run_trips), the counts per
+pair and the longest chain of register dependences within one trip (each instruction one step; s_nop and s_waitcnt not counted).  --core: the build with the hand-scheduled pair, k_msk_core (its
 inline assembly is part of the loop's block like any other instruction)."""
 import argparse
 import collections
@@ -175,7 +175,11 @@ def main():
     res = {"kernel": "k_msk_core" if a.core else "k_msk<false,false,%d>" % a.lpw}
     if plain:
         hdr, bs, ins = min(plain, key=lambda f: len(f[2]))
-        res["plain_pair_loop"] = dict(mix(ins), label=hdr, chain=chain(ins))
+        # (a trip of the loop is several pairs written out one behind the other, k_msk.h: msk_run_trips; a pair swaps rows twice)
+        pairs = max(1, sum(1 for i in ins if "permlane16_swap" in i or "permlane32_swap" in i) // 2)
+        m = mix(ins)
+        res["plain_pair_loop"] = dict(m, label=hdr, chain=chain(ins), pairs_per_trip=pairs,
+                                      per_pair={k: round(m[k] / pairs, 3) for k in ("total", "salu", "branch", "lds")})
     if tagged:
         hdr, bs, ins = min(tagged, key=lambda f: len(f[2]))
         res["tagged_pair_loop"] = dict(mix(ins), label=hdr, blocks=len(bs))
